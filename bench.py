@@ -7,14 +7,21 @@ One "step" = one pass of the hot path over one volume that is already resident i
 in HBM.  With N > 1 GPUs every rank builds the matrices of its own volume (batch mode shards cases, no collective:
 SURVEY.md section 8e), so scaling is "weak" and value = N * voxels * steps / max-over-ranks time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 512] [--dist uniform|smooth]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 512] [--dist uniform|smooth] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
 --master-addr 127.0.0.1` (one rank per GPU over RCCL) unless it already runs under such a launch.
 
-Rank 0 prints ONE JSON line: the headline (`value`, `roofline`), every other BASELINE config under `modes` (smooth
-headline variant, config 2 five matrices 256^3, config 3 filter stack 256^3, config 4 voxel maps 2-D and 3-D windows,
-config 5 batch of whole cases) and, at N = 1, `cpu_baseline` + `host_boundary`.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`).  `--full` adds everything else: the K steps once more right behind the W warm-up steps
+(`cold_ms_per_step`), the synchronous call, the `roofline` block (an instrumented pass of the loop and a copy-bandwidth
+run), property checks of the matrices, every other BASELINE config under `modes` (smooth headline variant, 64 levels,
+config 2 five matrices 256^3, config 3 filter stack 256^3, config 4 voxel maps 2-D and 3-D windows, config 5 batch of
+whole cases) and, at N = 1, `cpu_baseline` + `host_boundary`.
+
+`--dump-outputs DIR` writes what the last timed step of rank 0 computed -- DIR/glcm.npy [Ng, Ng, 13] and DIR/glrlm.npy
+[Ng, Nr, 13], float64 -- so that two builds can be compared output for output (the inputs are seeded: the same
+arguments give the same volume).
 """
 from __future__ import annotations
 
@@ -204,7 +211,7 @@ def headline_loop(engine, image, mask, Ng, Nr, steps, warmup, fence, outs, famil
     every event record costs the stream 3 - 6 us, and ten records per step -- what the library's full timing keeps --
     made a step 6 - 12 % slower than the product runs it (scripts/archive/r04_event_cost.py).  The other families (pack, x angle,
     finalize, whole call) come from a second, fully instrumented pass of the same loop AFTER the timed region.
-    Returns (seconds, per-family device ms per step, last outputs)."""
+    Returns (seconds, per-family device ms per step, outputs of the last timed step)."""
     state = {"n": 0, "g": None, "r": None}
 
     def step(deferred=True):
@@ -230,7 +237,9 @@ def headline_loop(engine, image, mask, Ng, Nr, steps, warmup, fence, outs, famil
     assert launches >= steps, (launches, steps)          # one walk launch per volume (pipeline mode: exactly `steps`)
     fam = {"sweep": engine.timing_ms("sweep") / launches, "sweep_launches": launches}
     engine.timing_end()
+    last = (state["g"], state["r"])   # what the last timed step computed
     if families:                      # instrumented pass, outside the timed region
+        last = tuple(t.clone() for t in last)          # (it reuses the output buffers)
         k = max(3, min(steps, 10))
         engine.timing_begin()
         for _ in range(k):
@@ -244,7 +253,7 @@ def headline_loop(engine, image, mask, Ng, Nr, steps, warmup, fence, outs, famil
         engine.timing_end()
     else:
         fam.update({"pack": 0.0, "rows": 0.0, "finalize": 0.0, "device": 0.0, "sweep_instrumented": 0.0})
-    return elapsed, fam, (state["g"], state["r"])
+    return elapsed, fam, last
 
 
 def mode_config2(device, engine, size=256, levels=32):
@@ -697,6 +706,24 @@ def host_boundary(image, mask, Ng: int, Nr: int):
                     "through the pinned staging ring (4 host threads), PCIe Gen5 x16"}
 
 
+def headline_line(args, world: int, nvox: int, elapsed: float, mode_name: str, prewarm_steps: int) -> dict:
+    """the keys of the JSON line that a plain run prints (elapsed: the K timed steps, max over ranks)"""
+    return {
+        "metric": "Mvoxels/s for GLCM+GLRLM build, %d^3 vol @%d bins" % (args.size, args.levels),
+        "value": round(world * nvox * args.steps / elapsed / 1e6, 1), "unit": "Mvoxels/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u8 levels / u32 counts / f64 out", "data": "synthetic",
+        "config": {"workload": "GLCM+GLRLM matrix build, %d^3 int32+uint8 volume resident in HBM, %d grey levels, "
+                               "full mask, 13 angles, %s levels; one volume per GPU (batch sharding, no collective)"
+                               % (args.size, args.levels, args.dist),
+                   "size": args.size, "levels": args.levels, "dist": args.dist, "deferred_mode": mode_name,
+                   "device_warmup": {"untimed_steps_before_the_W_warmup_steps": prewarm_steps, "ms": args.device_warmup_ms,
+                                     "why": "the first ~20 ms of GPU work of a process run 6 - 7 % slower than the steady state "
+                                            "(profiles/r05b_probes.md section 6); the timed region is the K steps after the W warm-up steps"}},
+    }
+
+
 def respawn_under_torchrun(n: int) -> None:
     """`python bench.py --gpus N` (N > 1) outside a torch.distributed launch: become that launch"""
     import socket
@@ -734,6 +761,11 @@ def main() -> None:
     ap.add_argument("--batch-cases", type=int, default=36, help="cases per rank in modes.batch")
     ap.add_argument("--cpu-voxels", type=int, default=160 * 512 * 512,
                     help="voxels in the single-threaded CPU sample (default: a 160-slice slab, ~5 s on one core)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side figures and checks (cold-start steps, synchronous call, roofline, modes, host boundary, "
+                         "CPU baseline); the --no-* options above thin out a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the matrices of the last timed step (rank 0) as DIR/glcm.npy and DIR/glrlm.npy (float64)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -790,18 +822,33 @@ def main() -> None:
     # 0.523, 0.488, 0.486, 0.487 ... ms per step; W = 3 - 5 steps are 2 ms of work), and the metric is the steady rate of
     # consecutive volumes.  Every later mode of this file ran warm already; --device-warmup-ms 0 switches it off.
     # ... and the same K steps measured the way rounds 1 - 5a measured them -- right behind W warm-up steps in a process that has
-    # done no other GPU work -- so that rounds stay comparable (`cold_ms_per_step` of the JSON line)
-    cold_elapsed, _cf, _co = headline_loop(engine, image, mask, Ng, Nr, args.steps, args.warmup, fence, outs, families=False)
-    cold_elapsed = max_over_ranks(cold_elapsed)
+    # done no other GPU work -- so that rounds stay comparable (`cold_ms_per_step` of the --full JSON line)
+    if args.full:
+        cold_elapsed, _cf, _co = headline_loop(engine, image, mask, Ng, Nr, args.steps, args.warmup, fence, outs, families=False)
+        cold_elapsed = max_over_ranks(cold_elapsed)
     prewarm_steps = 0
     if args.device_warmup_ms > 0:
         # (a fixed number of passes -- one per 10 ms asked for, 20 steps ~ 10 ms at 512^3 -- so that every rank meets the same fences)
         for _ in range(int(-(-args.device_warmup_ms // 10))):
             headline_loop(engine, image, mask, Ng, Nr, 20, 0, fence, outs, families=False)
             prewarm_steps += 20
-    elapsed, fam, (glcm, glrlm) = headline_loop(engine, image, mask, Ng, Nr, args.steps, args.warmup, fence, outs)
+    elapsed, fam, (glcm, glrlm) = headline_loop(engine, image, mask, Ng, Nr, args.steps, args.warmup, fence, outs,
+                                                families=args.full)
+    elapsed = max_over_ranks(elapsed)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("glcm", glcm), ("glrlm", glrlm)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.cpu().numpy().astype(np.float64, copy=False))
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_line(args, world, nvox, elapsed, mode_name, prewarm_steps)), flush=True)
+        if dist_on:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     assert torch.equal(glcm, g0) and torch.equal(glrlm, r0), "deferred and synchronous matrices differ"
-    timed_outputs = (glcm.clone(), glrlm.clone())      # what the timed pipeline left behind (the buffers are reused below)
+    timed_outputs = (glcm, glrlm)      # what the timed pipeline left behind (copies: the buffers are reused below)
     # the synchronous drop-in call (host waits for every volume and reads the status back), informational
     sync_steps = max(3, min(10, args.steps))
     fence()
@@ -810,7 +857,6 @@ def main() -> None:
         engine.glcm_glrlm(image, mask, Ng, Nr, out_glcm=outs[0][0], out_glrlm=outs[0][1])
     sync_ms = (time.perf_counter() - t1) / sync_steps * 1e3
     sync_fam = {f: engine.last_kernel_ms(f) for f in ("pack", "sweep", "rows", "finalize")}
-    elapsed = max_over_ranks(elapsed)
 
     modes = None
     if not args.no_modes:
@@ -921,7 +967,6 @@ def main() -> None:
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
-        value = world * nvox * args.steps / elapsed / 1e6
         sweep_ms = fam["sweep"]
         alg_bytes = ALG_BYTES_PER_VOXEL * nvox
         achieved = alg_bytes / (sweep_ms * 1e-3) / 1e9
@@ -935,21 +980,11 @@ def main() -> None:
         except (OSError, ValueError):
             prof = None
         inline = mode_name == "pipeline" and fam["pack"] < 0.02
-        out = {
-            "metric": "Mvoxels/s for GLCM+GLRLM build, %d^3 vol @%d bins" % (args.size, args.levels),
-            "value": round(value, 1), "unit": "Mvoxels/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms, 4), "cold_ms_per_step": round(cold_elapsed / args.steps * 1e3, 4),
+        out = headline_line(args, world, nvox, elapsed, mode_name, prewarm_steps)
+        out.update({
+            "cold_ms_per_step": round(cold_elapsed / args.steps * 1e3, 4),
             "sync_call_ms_per_step": round(sync_ms, 4),
-            "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u8 levels / u32 counts / f64 out", "data": "synthetic",
             "modes": modes,
-            "config": {"workload": "GLCM+GLRLM matrix build, %d^3 int32+uint8 volume resident in HBM, %d grey levels, "
-                                   "full mask, 13 angles, %s levels; one volume per GPU (batch sharding, no collective)"
-                                   % (args.size, args.levels, args.dist),
-                       "size": args.size, "levels": args.levels, "dist": args.dist, "deferred_mode": mode_name,
-                       "device_warmup": {"untimed_steps_before_the_W_warmup_steps": prewarm_steps, "ms": args.device_warmup_ms,
-                                         "why": "the first ~20 ms of GPU work of a process run 6 - 7 % slower than the steady state "
-                                                "(profiles/r05b_probes.md section 6); the timed region is the K steps after the W warm-up steps"}},
             "roofline": {
                 "bound": "hbm",
                 "kernel": "sweep_fw_kernel: the 12 line angles of one volume" +
@@ -976,7 +1011,7 @@ def main() -> None:
                         "job_* = 5 B/voxel over ms_per_step (wall, max over ranks)",
                 "kernel_ms_instrumented_pass": round(fam.get("sweep_instrumented", 0.0), 4),
             },
-        }
+        })
         if prof and "lds" in prof:
             t = sweep_ms * 1e-3
             out["roofline"]["secondary"] = {

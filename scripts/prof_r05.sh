@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r05
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-BA="--no-cpu-baseline --no-modes --no-host-boundary"
+BA="--full --no-cpu-baseline --no-modes --no-host-boundary"
 {
 echo "# r05 -- rocprofv3 --kernel-trace --stats of bench.py (scripts/prof_r05.sh), final source of round 5"
 echo

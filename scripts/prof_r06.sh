@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r06
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-BA="--no-cpu-baseline --no-modes --no-host-boundary"
+BA="--full --no-cpu-baseline --no-modes --no-host-boundary"
 {
 echo "# r06 -- rocprofv3 --kernel-trace --stats of bench.py (scripts/prof_r06.sh), final source of round 6 (HEAD ${PRAD_HEAD:-?} + working tree)"
 echo

@@ -2,7 +2,7 @@
 # round 6: is the two-table (64-level) walk bound by the size of its 16-bit level volume?  The 64- / 32-level step ratio at three
 # volume sizes: 16-bit volumes of 113, 180 and 268 MB against the 256 MB Infinity Cache.
 for sz in 384 448 512; do for lv in 32 64; do
-  python bench.py --no-cpu-baseline --no-modes --no-host-boundary --size $sz --levels $lv 2>/dev/null | grep '^{"metric"' > /tmp/l.json
+  python bench.py --full --no-cpu-baseline --no-modes --no-host-boundary --size $sz --levels $lv 2>/dev/null | grep '^{"metric"' > /tmp/l.json
   python - <<PY
 import json
 d = json.load(open("/tmp/l.json"))

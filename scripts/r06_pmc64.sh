@@ -1,6 +1,6 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06_pmc64; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-BA="--no-cpu-baseline --no-modes --no-host-boundary --levels 64"
+BA="--full --no-cpu-baseline --no-modes --no-host-boundary --levels 64"
 pass() { name=$1; shift; rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $O/pmc/$name -o $name -- python $R/bench.py --steps 4 --warmup 2 --device-warmup-ms 0 $BA > $O/pmc_$name.log 2>&1; }
 pass tcc1 FETCH_SIZE
 pass tcc2 WRITE_SIZE

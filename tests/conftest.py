@@ -23,14 +23,10 @@ def oracle_port():
 
 @pytest.fixture(scope="session")
 def oracle_ref():
-    """The reference's own cmatrices.c compiled unmodified (present when built in the dev container)."""
-    from oracle import binding
-    if not binding.have_ref():
-        if os.path.isdir("/root/reference/radiomics/src"):
-            binding.build()
-        if not binding.have_ref():
-            pytest.skip("oracle/_ref/libcmatrices_ref.so not available")
-    return binding.ref()
+    """The reference's own cmatrices.c compiled unmodified, as recorded under tests/golden/ (tests/helpers.py:
+    reference_oracle): every call the tests make of it, answered by oracle/_ref/libcmatrices_ref.so."""
+    from helpers import reference_oracle
+    return reference_oracle("cmatrices")
 
 
 @pytest.fixture(scope="session")

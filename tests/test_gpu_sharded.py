@@ -143,7 +143,7 @@ def test_bench_under_torchrun_with_rccl_one_rank():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29731", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--size", "256",
-           "--no-modes", "--no-cpu-baseline", "--no-host-boundary", "--backend", "nccl"]
+           "--full", "--no-modes", "--no-cpu-baseline", "--no-host-boundary", "--backend", "nccl"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -166,7 +166,7 @@ def test_bench_two_ranks_on_one_gpu_through_the_sharded_modes():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29741", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--size", "256",
-           "--batch-cases", "4", "--no-cpu-baseline", "--no-host-boundary", "--backend", "gloo"]
+           "--batch-cases", "4", "--full", "--no-cpu-baseline", "--no-host-boundary", "--backend", "gloo"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

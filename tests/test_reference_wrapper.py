@@ -10,14 +10,9 @@ import pytest
 
 @pytest.fixture(scope="module")
 def wrapper():
-    from oracle import binding
-    if not binding.have_ref_wrapper():
-        import os
-        if os.path.isdir("/root/reference/radiomics/src"):
-            binding.build()
-        if not binding.have_ref_wrapper():
-            pytest.skip("oracle/_ref/_cmatrices.so not available")
-    return binding.ref_wrapper()
+    """the module as recorded under tests/golden/ (tests/helpers.py: reference_oracle)"""
+    from helpers import reference_oracle
+    return reference_oracle("module")
 
 
 def _cases():
