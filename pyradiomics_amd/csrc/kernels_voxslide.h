@@ -42,7 +42,7 @@ namespace prad {
                                   // update the same few entries of their tables at once, and with an even stride (544 B until
                                   // round 6) every fourth table put that entry on the same LDS bank
 #define PRAD_VS_FIX 40            // fixed-point fraction bits of S
-#define PRAD_VS_LUT 104           // counts of a table entry <= 100 (pairs of one angle in a 5^3 window); the last entry: the absent pair
+#define PRAD_VS_LUT 104           // a real entry per count a table entry reaches (<= 100: VoxSlideLimits); the last entry: the absent pair
 #define PRAD_VS_NNZ_SHIFT 52      // S carries nnz above its 11 + 40 bits
 
 // WIDE (round 5): fourteen more features whose sums update pair by pair -- Autocorrelation, ClusterProminence / Shade / Tendency,
@@ -55,6 +55,9 @@ namespace prad {
 // the sum / difference distributions, Imc1 / Imc2, MCC, MaximumProbability.
 #define PRAD_VS_KMAX 64
 // Tuning knobs (the defaults are what profiles/r06_probes.md section 12 measured best; scripts/build_variant.sh builds others):
+#ifndef PRAD_VS_LEAVE_FIRST
+#define PRAD_VS_LEAVE_FIRST 1     // a sliding step applies the leaving plane's pairs before the entering plane's (VoxSlideLimits)
+#endif
 #ifndef PRAD_VS_CH
 #define PRAD_VS_CH 9              // pair positions in flight per stage where a lane per angle walks a 3-D plane (the WIDE sums)
 #endif
@@ -67,6 +70,30 @@ namespace prad {
 #ifndef PRAD_VS_BAL_R1
 #define PRAD_VS_BAL_R1 1          // 3^3 windows on the balanced schedule too (0: a lane per angle, 51 instead of 43 ms at 512^3)
 #endif
+// The largest count a table entry of one angle reaches.  At a centre an angle pairs up at most PZ D (D - 1) voxels (the
+// angle along x in a full window: 100 at radius 2, 3-D).  Within a sliding step the count goes through the state between the
+// two planes: with the leaving plane first it dips (100 -> 75 -> 100) and never exceeds the steady maximum; entering first it
+// would add the up to PZ D pairs of the entering plane on top (PZ D D, the voxels of the window: 100 -> 125 for (0, 0, 1),
+// 100 -> 120 for the dx = 0 angles, a uniform 5^3 window), past the 104 entries of the LUTs.  Every index the kernel forms --
+// a count c (off, dia), a pair count P (pt) -- must have a real entry, below the absent pair's.
+template <int R, bool TWO_D>
+constexpr int voxslide_max_count() {
+  constexpr int D = 2 * R + 1, PZ = TWO_D ? 1 : D;
+  return PZ * D * (D - 1) + (PRAD_VS_LEAVE_FIRST ? 0 : PZ * D);
+}
+constexpr int voxslide_bits(int n) { return n ? 1 + voxslide_bits(n >> 1) : 0; }     // bit width: n < 2^bits, log2 n < bits
+template <int R, bool TWO_D>
+struct VoxSlideLimits {
+  static constexpr int CMAX = voxslide_max_count<R, TWO_D>();
+  static_assert(CMAX < PRAD_VS_LUT - 1, "every count 0..CMAX has a real LUT entry below the absent pair's");
+  static_assert(CMAX <= 255, "the byte counters of a table do not wrap");
+  // S = sum of n log2 n over the entries, sum n = 2 CMAX: at most 2 CMAX log2 (2 CMAX) (all pairs on the diagonal), and
+  // below 2^11 in its 2^-40 fixed point so that nnz above PRAD_VS_NNZ_SHIFT stays apart (radius 2, 3-D: 200 x 8 = 1600)
+  static_assert((long long)(2 * CMAX) * voxslide_bits(2 * CMAX) < (1LL << (PRAD_VS_NNZ_SHIFT - PRAD_VS_FIX - 1)),
+                "S fits below the nnz bits");
+  static_assert((2 * CMAX) * (2 * CMAX) < (1 << 20), "sum n^2 fits below the pair count of EP");
+};
+
 struct VoxSlideLutK {            // g_f(k) * 2^40, f = Id, Idm, Idn, Idmn, InverseVariance (built per call: Idn / Idmn depend on Ng)
   long long g[5][PRAD_VS_KMAX];
 };
@@ -184,6 +211,7 @@ __global__ void __launch_bounds__(64 * WAVES) voxel_glcm_slide_kernel(const uint
                                                // two neighbouring planes = 16 banks each, side by side
   constexpr bool BAL = !TWO_D && !WIDE && (R == 2 || PRAD_VS_BAL_R1);        // the lane-balanced schedule (above)
   using BL = VoxSlideBal<R>;
+  static_assert(VoxSlideLimits<R, TWO_D>::CMAX > 0, "(instantiates the range checks of VoxSlideLimits for this window)");
   constexpr int NT = TWO_D ? 64 : 13 * NGR;    // count tables per wave (3-D: the 13 angle lanes of each group)
   static_assert(TB % 8 == 4 && (NT * TB) % 16 == 0, "tables: an odd number of words each, cleared 16 bytes at a time");
   static_assert(NP < PB, "a staged plane keeps a zero byte behind its voxels");
@@ -364,10 +392,13 @@ __global__ void __launch_bounds__(64 * WAVES) voxel_glcm_slide_kernel(const uint
 #pragma unroll
     for (int r = 0; r < NSEG; r++) { Sq[r] = 0; EPq[r] = 0; IJq[r] = 0; }
     // the pairs of entering plane s (base_p) and, with BOTH, of leaving plane s - D (base_m) in one straight line: the level
-    // reads of the leaving plane are under way while the entering plane's pairs are counted
+    // reads of the second plane are under way while the first plane's pairs are counted.  With BOTH the leaving plane comes
+    // first (PRAD_VS_LEAVE_FIRST): slots j < NSLOT are its pairs, then the entering plane's
     auto slots = [&](const unsigned char *base_p, const unsigned char *base_m, auto both_tag) __attribute__((always_inline)) {
-      constexpr int T = decltype(both_tag)::value ? 2 * NSLOT : NSLOT;
+      constexpr bool BOTH = decltype(both_tag)::value;
+      constexpr int T = BOTH ? 2 * NSLOT : NSLOT;
       constexpr int CH = T > PRAD_VS_CHB ? PRAD_VS_CHB : T;      // slots in flight
+      auto leaving = [](int j) constexpr { return BOTH && ((j < NSLOT) == (PRAD_VS_LEAVE_FIRST != 0)); };
 #pragma unroll
       for (int c0 = 0; c0 < T; c0 += CH) {
         int l1[CH], l2[CH], shf[CH];
@@ -378,18 +409,18 @@ __global__ void __launch_bounds__(64 * WAVES) voxel_glcm_slide_kernel(const uint
         for (int k = 0; k < CH; k++) {
           const int j = c0 + k, jj = j % NSLOT;
           if (j < T) {
-            l1[k] = j < NSLOT ? base_p[a1P[jj]] : base_m[a1M[jj]];
-            l2[k] = j < NSLOT ? base_p[a2P[jj]] : base_m[a2M[jj]];
+            l1[k] = leaving(j) ? base_m[a1M[jj]] : base_p[a1P[jj]];
+            l2[k] = leaving(j) ? base_m[a2M[jj]] : base_p[a2P[jj]];
           }
         }
 #pragma unroll
         for (int k = 0; k < CH; k++) {
-          const int j = c0 + k, SIGN = j < NSLOT ? 1 : -1;
+          const int j = c0 + k, SIGN = leaving(j) ? -1 : 1;
           if (j < T) PRAD_VS_STAGE2(k, tb[j % NSLOT])
         }
 #pragma unroll
         for (int k = 0; k < CH; k++) {
-          const int j = c0 + k, SIGN = j < NSLOT ? 1 : -1;
+          const int j = c0 + k, SIGN = leaving(j) ? -1 : 1;
           if (j < T) PRAD_VS_STAGE3(k)
         }
 #pragma unroll
@@ -398,7 +429,7 @@ __global__ void __launch_bounds__(64 * WAVES) voxel_glcm_slide_kernel(const uint
           if (j < T) {
             const int ij = JA && ok[k] ? l1[k] + l2[k] : 0;
             const int ep = LIGHT ? (ok[k] ? 1 : 0) : e[k].ep;      // (LIGHT: EPq counts the pairs)
-            if (j < NSLOT) { Sq[r] += e[k].g; EPq[r] += ep; IJq[r] += ij; }
+            if (!leaving(j)) { Sq[r] += e[k].g; EPq[r] += ep; IJq[r] += ij; }
             else { Sq[r] -= e[k].g; EPq[r] -= ep; IJq[r] -= ij; }
           }
         }
@@ -453,11 +484,13 @@ __global__ void __launch_bounds__(64 * WAVES) voxel_glcm_slide_kernel(const uint
     // has the plane of zeros there: no pairs) -- and, with BOTH, plane o = s - D leaves -- pairs inside it or with plane o + 1 --
     // in one straight line for the 2-D windows (the 5 x 5 window has 5 positions per plane: one sign at a time left four LDS
     // round trips per five pairs exposed)
-    // (MODE 0: the entering plane, 1: both, 2: the leaving plane)
+    // (MODE 0: the entering plane, 1: both -- the leaving plane's positions j < NP first (PRAD_VS_LEAVE_FIRST), then the
+    // entering plane's --, 2: the leaving plane)
     auto plane_pairs = [&](int s, auto mode_tag) __attribute__((always_inline)) {
       constexpr int MODE = decltype(mode_tag)::value;
       constexpr int J0 = MODE == 2 ? NP : 0, T = MODE == 0 ? NP : 2 * NP;
       constexpr int CH = T - J0 <= 10 ? T - J0 : PRAD_VS_CH;         // positions in flight
+      auto leaving = [](int j) constexpr { return MODE == 2 || (MODE == 1 && (j < NP) == (PRAD_VS_LEAVE_FIRST != 0)); };
       const int o = s - D;
       const unsigned char *pp_p = gp + (dx > 0 ? s - 1 : s) * PB, *pq_p = gp + (dx < 0 ? s - 1 : s) * PB;
       const unsigned char *pp_m = gp + (dx < 0 ? o + 1 : o) * PB, *pq_m = gp + (dx > 0 ? o + 1 : o) * PB;
@@ -471,23 +504,23 @@ __global__ void __launch_bounds__(64 * WAVES) voxel_glcm_slide_kernel(const uint
         for (int k = 0; k < CH; k++) {
           const int j = c0 + k, p = j % NP;
           if (j < T) {
-            l1[k] = j < NP ? pp_p[p] : pp_m[p];
-            l2[k] = j < NP ? pq_p[qa[p]] : pq_m[qa[p]];
+            l1[k] = leaving(j) ? pp_m[p] : pp_p[p];
+            l2[k] = leaving(j) ? pq_m[qa[p]] : pq_p[qa[p]];
           }
         }
 #pragma unroll
         for (int k = 0; k < CH; k++) {
-          const int j = c0 + k, SIGN = j < NP ? 1 : -1;
+          const int j = c0 + k, SIGN = leaving(j) ? -1 : 1;
           if (j < T) PRAD_VS_STAGE2(k, tbl32)
         }
 #pragma unroll
         for (int k = 0; k < CH; k++) {
-          const int j = c0 + k, SIGN = j < NP ? 1 : -1;
+          const int j = c0 + k, SIGN = leaving(j) ? -1 : 1;
           if (j < T) PRAD_VS_STAGE3(k)
         }
 #pragma unroll
         for (int k = 0; k < CH; k++) {
-          const int j = c0 + k, SIGN = j < NP ? 1 : -1;
+          const int j = c0 + k, SIGN = leaving(j) ? -1 : 1;
           if (j < T) {
             const int ij = JA && ok[k] ? l1[k] + l2[k] : 0;
             const int ep = LIGHT ? (ok[k] ? 1 : 0) : e[k].ep;      // (LIGHT: EP counts the pairs)
@@ -525,8 +558,9 @@ __global__ void __launch_bounds__(64 * WAVES) voxel_glcm_slide_kernel(const uint
       // (3-D windows come here with the WIDE sums only: 25 positions per plane at ~80 instructions each -- one sign at a time and
       // one copy of the code measured 4 % faster than the merged / peeled form)
       for (int s = 0; s < XL; s++) {
+        if (PRAD_VS_LEAVE_FIRST && s >= D) plane_pairs(s, std::integral_constant<int, 2>{});      // (wave-uniform)
         plane_pairs(s, std::integral_constant<int, 0>{});
-        if (s >= D) plane_pairs(s, std::integral_constant<int, 2>{});      // (wave-uniform)
+        if (!PRAD_VS_LEAVE_FIRST && s >= D) plane_pairs(s, std::integral_constant<int, 2>{});
         if (s >= 2 * R) emit(s, S, LIGHT ? EP << 20 : EP, IJ);
       }
     }

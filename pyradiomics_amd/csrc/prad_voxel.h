@@ -157,7 +157,7 @@ int voxel_glcm_features_dev(const int32_t *image, const uint8_t *mask, const int
           return (long long)std::llround((double)cnt * std::log2((double)cnt) * (double)(1LL << PRAD_VS_FIX));
         };
         for (int k = 0; k < PRAD_VS_LUT; k++) {
-          const bool absent = k == PRAD_VS_LUT - 1;            // (a count never gets there: <= 100 pairs per angle)
+          const bool absent = k == PRAD_VS_LUT - 1;            // (past every count a sliding step reaches: VoxSlideLimits)
           const long long nz = k == 0 ? 1LL << PRAD_VS_NNZ_SHIFT : 0;
           t.off[k] = absent ? VoxSlideLutE{0, 0, 0} : VoxSlideLutE{2 * (f(k + 1) - f(k)) + 2 * nz, (1 << 20) | (2 * (2 * k + 1)), 0};
           t.dia[k] = absent ? VoxSlideLutE{0, 0, 0} : VoxSlideLutE{f(2 * k + 2) - f(2 * k) + nz, (1 << 20) | (4 * (2 * k + 1)), 0};
