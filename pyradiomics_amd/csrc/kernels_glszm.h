@@ -9,7 +9,7 @@
 //                                 work list of pairs
 //       glszm_dense_init_kernel   parent[id] = id, zsize[id] = voxels of the tile component
 //       glszm_pairs_kernel        union-find over the dense ids along the work list (atomicMin on the larger root)
-//       glszm_rootsum_dense_kernel  counts folded into the zone roots, parent[] flattened
+//       glszm_rootsum_dense_kernel  counts folded into the zone roots, parent[] shortened (nearly flat: see the kernel)
 //       glszm_stats / fill kernels  walk the ids (a zone = an id with parent[id] == id; level in tinfo[id] >> 16)
 //     The ordered zone list (tempData parity, cmatrices.c:255-258) needs the first voxel of every zone: a scan of vid[]
 //     (glszm_zmin_kernel), on demand.
@@ -1073,7 +1073,10 @@ __global__ void __launch_bounds__(256) glszm_dense_init_kernel(const int *__rest
 
 // Counts of the tile components folded into their zone roots: one find per tile root in the dense array; contributions
 // to the same zone root are combined in an LDS hash table first (a zone that spans thousands of tiles would otherwise
-// receive thousands of atomics on one address).  parent[] is flat afterwards (every entry points at its zone root).
+// receive thousands of atomics on one address).  parent[] is NEARLY flat afterwards: every entry was pointed at its zone
+// root, but the path-halving stores of another lane's dn_find (a grandparent read before that) may land later and leave an
+// entry at an ancestor short of the root -- on chains of five and more tile components.  An entry j is a zone root iff
+// parent[j] == j; whoever needs the root of another entry walks the (short) rest of the chain (glszm_zmin_kernel).
 #define PRAD_RS_SLOTS 1024
 #ifndef PRAD_RS_PROBES
 #define PRAD_RS_PROBES 2      // (dense kernel; on noise the table fills up and every further probe is a wasted LDS atomic)
@@ -1510,7 +1513,8 @@ __global__ void __launch_bounds__(256) glszm_zmin_kernel(long long n, const int 
   for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += stride) {
     const int id = vid[v];
     if (id < 0) continue;
-    const int r = parent[id];
+    int r = parent[id];
+    for (int p = parent[r]; p != r; p = parent[r]) r = p;      // (parent[] is only nearly flat: glszm_rootsum_dense_kernel)
     if (zmin[r] > (int)v) atomicMin(zmin + r, (int)v);
   }
 }
