@@ -62,7 +62,8 @@ int prad_release_workspace(void);
  * lets tests assert that the fast kernels (not a fallback) produced a result. */
 const char *prad_last_path(void);
 /* which sweep kernels the plan of this thread's last GLCM / GLRLM call chose: "fw" (fixed window, fused table: <= 44 grey
- * levels, rows of 65..512 voxels), "fw2" (fixed window, two tables, 16-bit levels: 45+ levels), "lines" (wrapped lines). */
+ * levels, rows of 65..512 voxels), "fw2" (fixed window, two tables, 16-bit levels: 45+ levels), "lines" (wrapped lines);
+ * after prad_label_census*: "census-lds" or "census-global". */
 const char *prad_last_variant(void);
 /* Total device time (ms, HIP events on the work stream) of this thread's last calculate_* call, and
  * the time of its dominant kernel family; used by bench.py for the roofline figure. */
@@ -469,6 +470,22 @@ int prad_voxel_firstorder_dev(const void *image, int dtype, const uint8_t *mask,
  * prad_digitize_dev); size / start / step / newsize: HOST arrays of Nd (<= 3) entries. */
 int prad_resample_dev(const void *image, int dtype, const int *size, int Nd, const double *start, const double *step,
                       const int *newsize, int interpolator, void *out, void *stream);
+
+/* ---- label census: every label of a label map in one pass (no reference analogue: the reference extracts one label per
+ * execute() call and finds its ROI with sitk.LabelStatisticsImageFilter, imageoperations.py:407-445) ------------------
+ * mask: integer label map [size[0]]..[size[Nd-1]], Nd = 2 or 3, C-contiguous; dtype: 2 = int32, 3 = int16 (the codes of
+ * prad_digitize_dev) or 4 = uint8.  table: int64 [max_label + 1][1 + 2 Nd], row v = voxel count of label v, then lo[Nd] and
+ * hi[Nd], its inclusive index bounds in array (z, y, x) order.  Row 0 (background) is zero; values below 1 or above
+ * max_label are ignored; a label that does not occur has count 0, lo[d] = size[d], hi[d] = -1.  0 <= max_label <= 65535
+ * (PRAD_E_ARG beyond: the caller looks at such a map label by label).  The table need not be initialised.
+ * One pass over the map: a wave that finds one value in all of its lanes adds a whole row piece to a run it keeps in
+ * registers; tables of up to 12288 words are kept per workgroup in LDS and merged at its end (prad_last_variant:
+ * "census-lds"), larger ones are updated in global memory ("census-global").  Integer atomics: exact, order-independent.
+ * prad_label_census_dev: device pointers, synchronises `stream`; prad_label_census: host pointers, staged.
+ * prad_mask_max_dev: *max_value (HOST) = largest element of the n elements of `mask` (DEVICE), to size the table. */
+int prad_label_census_dev(const void *mask, int dtype, const int *size, int Nd, int max_label, long long *table, void *stream);
+int prad_label_census(const void *mask, int dtype, const int *size, int Nd, int max_label, long long *table);
+int prad_mask_max_dev(const void *mask, int dtype, long long n, long long *max_value, void *stream);
 
 /* ---- filter stack in front of the matrices (radiomics/imageoperations.py:756-970) ---------------------------
  * The arithmetic of both filters lives in third-party wheels (PyWavelets, SimpleITK/ITK) that are not part of

@@ -105,6 +105,9 @@ SYMBOLS = {
     "prad_voxel_firstorder_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _ip, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _ip,
                                             C.c_double, C.c_double, _ip, C.c_int, _vp, _vp]),
     "prad_level_counts_dev": (C.c_int, [_vp, _vp, C.c_longlong, C.c_int, C.POINTER(C.c_longlong), _vp]),
+    "prad_label_census_dev": (C.c_int, [_vp, C.c_int, _ip, C.c_int, C.c_int, _vp, _vp]),
+    "prad_label_census": (C.c_int, [_vp, C.c_int, _ip, C.c_int, C.c_int, _vp]),
+    "prad_mask_max_dev": (C.c_int, [_vp, C.c_int, C.c_longlong, C.POINTER(C.c_longlong), _vp]),
     "prad_swt_level1": (C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp]),
     "prad_swt_level1_dev": (C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp, _vp]),
     "prad_swt_level1_any_dev": (C.c_int, [_vp, C.c_int, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp, _vp]),

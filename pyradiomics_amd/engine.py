@@ -494,6 +494,60 @@ def resample(image: torch.Tensor, start, step, newsize, interpolator: int = 3) -
     return out
 
 
+MAX_CENSUS_LABEL = 65535
+
+
+class LabelRangeError(ValueError):
+    """label_census: the map holds (or the caller named) a label above MAX_CENSUS_LABEL -- PRAD_E_ARG of the library"""
+
+_LABEL_CODES = {torch.int32: 2, torch.int16: 3, torch.uint8: 4}
+
+
+def label_census(mask: torch.Tensor, max_label=None):
+    """Every label of an integer label map in one pass over it (prad_label_census_dev): -> (labels int64 [K], counts int64 [K],
+    lo int64 [K, Nd], hi int64 [K, Nd]) for the labels 1..max_label that occur, ascending; lo / hi are the inclusive index
+    bounds in array (z, y, x) order.  Nd is 2 or 3.  Without `max_label` the table is sized by the map's largest value
+    (prad_mask_max_dev).  Values below 1 or above max_label are ignored; max_label above 65535 raises LabelRangeError, a
+    ValueError (the caller then works on the host).  One device-to-host copy: the table."""
+    lib = _lib.load()
+    if not mask.is_cuda:
+        raise ValueError("engine.label_census expects a CUDA/HIP tensor")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    elif mask.dtype == torch.int8:
+        mask = mask.to(torch.int16)
+    elif mask.dtype == torch.int64:
+        # the operator boundary is 32-bit (Image.device_tensor narrows the same way, after the same range check): a value
+        # that does not fit must not wrap into the label range
+        if mask.numel() and (int(mask.max()) > 2**31 - 1 or int(mask.min()) < -2**31):
+            raise LabelRangeError("label census: int64 label map holds values outside the int32 range")
+        mask = mask.to(torch.int32)
+    if mask.dtype not in _LABEL_CODES:
+        raise ValueError("label census needs an integer label map, not %s" % mask.dtype)
+    mask = mask.contiguous()
+    nd = mask.dim()
+    dev = mask.device.index if mask.device.index is not None else torch.cuda.current_device()
+    _lib.raise_for(lib.prad_set_device(dev), "set_device")
+    code = _LABEL_CODES[mask.dtype]
+    if max_label is None:
+        top = C.c_longlong(0)
+        _lib.raise_for(lib.prad_mask_max_dev(C.c_void_p(mask.data_ptr()), code, mask.numel(), C.byref(top), _stream_ptr()),
+                       "mask max")
+        max_label = max(int(top.value), 0)
+    max_label = int(max_label)
+    size = np.array(mask.shape, dtype=np.intc)
+    rows = min(max(max_label, 0), MAX_CENSUS_LABEL) + 1       # (an inadmissible max_label is refused before the table is touched)
+    table = torch.empty((rows, 1 + 2 * nd), dtype=torch.int64, device=mask.device)
+    rc = lib.prad_label_census_dev(C.c_void_p(mask.data_ptr()), code, _iptr(size), nd, max_label,
+                                   C.c_void_p(table.data_ptr()), _stream_ptr())
+    if rc == _lib.PRAD_E_ARG and max_label > MAX_CENSUS_LABEL:
+        raise LabelRangeError("label census: %s" % _lib.last_error())
+    _lib.raise_for(rc, "label census")
+    t = table.cpu().numpy()
+    labels = np.flatnonzero(t[:, 0] > 0).astype(np.int64)
+    return labels, t[labels, 0].copy(), t[labels, 1:1 + nd].copy(), t[labels, 1 + nd:].copy()
+
+
 def workspace_bytes() -> int:
     """device bytes of scratch the library currently holds for this thread"""
     return int(_lib.load().prad_workspace_bytes())

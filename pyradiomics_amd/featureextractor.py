@@ -224,6 +224,84 @@ class RadiomicsFeatureExtractor:
                 if state is not None and state[0] is not None:
                     state[0].close()                 # (abandons what the unfinished case queued)
 
+    def executeLabels(self, imageFilepath, maskFilepath, labels=None, label_channel=None):
+        """Generator of (label, result) over the labels of ONE label map: every label the map holds, ascending, or `labels` in
+        their order.  Each result is execute(image, mask, label=l), key for key and bit for bit, diagnostics included; what
+        does not depend on the label is done once per call instead of once per label:
+          - image and mask are loaded and uploaded once;
+          - one census of the map (imageoperations.labelCensus: a single pass) gives every label's voxel count and bounding
+            box, so no label scans the map for its ROI;
+          - the derived images of the enabled image types (the wavelet's sub-bands, the LoG's sigmas ...) are produced once;
+          - each label's crops go through the per-image pipeline of execute() with its one-image look-ahead, and label i + 1's
+            first crop is queued before label i's last image is collected (as executeMany overlaps cases).
+        When a setting makes the IMAGE depend on the label -- `resampledPixelSpacing` with an interpolator, `preCrop`,
+        `resegmentRange` -- the derived images cannot be shared: the call still loads and counts once and then runs execute()'s
+        steps label by label (the same results; the filter stack is repeated per label).
+        Peak memory: the shared path keeps every derived image of the call alive until the last label is done (Wavelet: 8
+        full-size float64 sub-bands, LoG: one image per sigma -- 1.2 GB for a 256^3 case with Wavelet and one sigma), where
+        execute() holds the ones in flight.
+        With labels=None a label that fails an ROI check of execute() (minimumROIDimensions, minimumROISize, absent after
+        processing) is skipped with a logged warning; with an explicit list the ValueError of execute() is raised at that
+        label's position, after the results of the labels before it.  Segment-based extraction only."""
+        s = self.settings.copy()
+        if labels is not None:
+            labels = [l for l in labels]
+            if labels:
+                s["label"] = labels[0]        # (loadImage checks a vector mask for the label it is given)
+        if label_channel is not None:
+            s["label_channel"] = label_channel
+        # (without a label list no label is asked of the mask while loading: the channel of a vector mask is picked and a
+        # `correctMask` geometry check looks at the box of all labelled voxels)
+        image, mask = self.loadImage(imageFilepath, maskFilepath, **(dict(s, label=None) if labels is None else s))
+        on_dev = bool(s.get("deviceResident", True)) and getattr(backend.get(), "DEVICE_TENSORS", False)
+        s["deviceResident"] = on_dev
+        present = imageoperations.labelCensus(mask, deviceResident=on_dev)[0]
+        discover = labels is None
+        if discover:
+            labels = [int(l) for l in present]
+            if not labels:
+                raise ValueError("No labels found in this mask (i.e. nothing is segmented)!")
+        per_label_image = ((s.get("resampledPixelSpacing") is not None and s.get("interpolator") is not None)
+                           or s.get("preCrop", False) or s.get("resegmentRange") is not None)
+        shared = None
+        if not per_label_image:
+            s["label"] = self.settings.get("label", 1)
+            base = imageoperations.normalizeImage(image, **s) if s.get("normalize", False) else image
+            shared = (base, list(self._derivedImages(base, mask, s)))
+        prev, cur = None, None
+        try:
+            for lab in labels:
+                steps = self._executeSteps(image, mask, lab, label_channel, False, shared=shared)
+                failed = None
+                try:
+                    next(steps)                      # head of this label: ROI checks, its first crop queued
+                    cur = (lab, steps, None)
+                except StopIteration as done:
+                    cur = (lab, None, done.value)
+                except ValueError as e:
+                    if discover:
+                        logger.warning("label %s skipped: %s", lab, e)
+                        continue
+                    failed = e
+                if prev is not None:
+                    last, prev = prev, None
+                    yield last[0], self._finishSteps(last[1:])
+                if failed is not None:
+                    raise failed
+                if cur[1] is not None:
+                    try:
+                        next(cur[1])                 # the body: every image but the last collected
+                    except StopIteration as done:
+                        cur = (lab, None, done.value)
+                prev, cur = cur, None
+            if prev is not None:
+                last, prev = prev, None
+                yield last[0], self._finishSteps(last[1:])
+        finally:
+            for state in (prev, cur):
+                if state is not None and state[1] is not None:
+                    state[1].close()                 # (abandons what the unfinished label queued: _abandonFeatures)
+
     @staticmethod
     def _finishSteps(state):
         steps, value = state
@@ -235,10 +313,12 @@ class RadiomicsFeatureExtractor:
         except StopIteration as done:
             return done.value
 
-    def _executeSteps(self, imageFilepath, maskFilepath, label=None, label_channel=None, voxelBased=False):
+    def _executeSteps(self, imageFilepath, maskFilepath, label=None, label_channel=None, voxelBased=False, shared=None):
         """execute() as a generator that yields TWICE -- when the case's first derived image is queued (executeMany collects the
         previous case's last image there: at most two images of two cases in flight, the library's tickets are a ring of four) and
-        when everything is queued or collected except the values of the last derived image -- and returns what execute() returns"""
+        when everything is queued or collected except the values of the last derived image -- and returns what execute() returns.
+        `shared` (executeLabels): (image, derived) -- the image as it stands after the label-independent steps and the list of
+        (derived image, name, kwargs) of the enabled image types, produced once for all labels of the case"""
         s = self.settings.copy()
         if label is not None:
             s["label"] = label
@@ -263,23 +343,31 @@ class RadiomicsFeatureExtractor:
         def describe(stage, img, msk):
             """diagnostics_Image-<stage>_* / diagnostics_Mask-<stage>_* (generalinfo.py:97-190, the subset that needs
             no SimpleITK label statistics)"""
-            on = msk.on_device or (on_dev and stage != "original")
-            r = imageoperations.roiTensor(msk, label) if on else (msk.array == label)
-            try:
-                blo, bhi = imageoperations.boundingBox(r)
-            except ValueError:
-                raise ValueError("Label (%g) not present in mask" % label)
+            known = imageoperations.censusLookup(msk, label)      # (a census of this mask, when one was taken: no scan)
+            if known is not None:
+                nvox, blo, bhi = known
+                if nvox == 0:
+                    raise ValueError("Label (%g) not present in mask" % label)
+            else:
+                on = msk.on_device or (on_dev and stage != "original")
+                r = imageoperations.roiTensor(msk, label) if on else (msk.array == label)
+                try:
+                    blo, bhi = imageoperations.boundingBox(r)
+                except ValueError:
+                    raise ValueError("Label (%g) not present in mask" % label)
             info["diagnostics_Image-%s_Spacing" % stage] = img.GetSpacing()
             info["diagnostics_Image-%s_Size" % stage] = img.GetSize()
             info["diagnostics_Mask-%s_Spacing" % stage] = msk.GetSpacing()
             info["diagnostics_Mask-%s_Size" % stage] = msk.GetSize()
             info["diagnostics_Mask-%s_BoundingBox" % stage] = tuple(int(v) for v in blo[::-1]) + \
                 tuple(int(v) for v in (bhi - blo + 1)[::-1])
-            info["diagnostics_Mask-%s_VoxelNum" % stage] = int(r.sum())
+            info["diagnostics_Mask-%s_VoxelNum" % stage] = int(r.sum()) if known is None else nvox
 
         if s.get("additionalInfo", True):
             describe("original", image, mask)
-        if s.get("normalize", False):                  # featureextractor.py:432-433: before anything else sees the image
+        if shared is not None:
+            image = shared[0]                          # (normalised once for all labels)
+        elif s.get("normalize", False):                # featureextractor.py:432-433: before anything else sees the image
             image = imageoperations.normalizeImage(image, **s)
         # :436-440 (the reference's loadImage only resamples when BOTH the spacing and an interpolator are given)
         if s.get("resampledPixelSpacing") is not None and s.get("interpolator") is not None:
@@ -299,13 +387,19 @@ class RadiomicsFeatureExtractor:
             mask = imageoperations.resegmentMask(image, mask, **s)
             if s.get("additionalInfo", True):
                 describe("resegmented", image, mask)
-        roi = imageoperations.roiTensor(mask, label) if on_dev else (mask.array == label)
-        try:
-            lo, hi = imageoperations.boundingBox(roi)
-        except ValueError:
-            raise ValueError("Label (%g) not present in mask" % label)
+        known = imageoperations.censusLookup(mask, label)
+        if known is not None:
+            nroi, lo, hi = known
+            if nroi == 0:
+                raise ValueError("Label (%g) not present in mask" % label)
+        else:
+            roi = imageoperations.roiTensor(mask, label) if on_dev else (mask.array == label)
+            try:
+                lo, hi = imageoperations.boundingBox(roi)
+            except ValueError:
+                raise ValueError("Label (%g) not present in mask" % label)
+            nroi = int(roi.sum())
         mask._derived[("bbox", label)] = (lo, hi)
-        nroi = int(roi.sum())
         ndims = int(np.sum(hi - lo + 1 > 1))
         if ndims < s.get("minimumROIDimensions", 2):
             raise ValueError("mask has too few dimensions (number of dimensions %d, minimum required %d)"
@@ -318,11 +412,11 @@ class RadiomicsFeatureExtractor:
             out["diagnostics_Configuration_Settings"] = {k: v for k, v in s.items()}
             out["diagnostics_Configuration_EnabledImageTypes"] = dict(self.enabledImagetypes)
             out.update(info)
-        gens = []
-        for imageType, custom in self.enabledImagetypes.items():
-            args = s.copy()
-            args.update(custom)
-            gens = chain(gens, _IMAGE_TYPES[imageType](image, mask, **args))
+        if shared is not None:
+            # the derived images do not depend on the label; the keyword set handed on with each does (`label`)
+            gens = ((derived, typeName, dict(kw, label=label)) for derived, typeName, kw in shared[1])
+        else:
+            gens = self._derivedImages(image, mask, s)
         # Look-ahead: image i + 1 is cropped and its discretisation QUEUED (prebinDevice: no round trip) right behind the device
         # classes of image i, and the host collects image i - 1 after that -- the GPU works through a queue while the host does
         # its Python, and the one round trip of a binning (ROI min / max -> number of levels) has passed by the time the classes
@@ -377,6 +471,15 @@ class RadiomicsFeatureExtractor:
                 RadiomicsFeaturesBase.dropPrebinned(nxt[0])
             raise
         return out
+
+    def _derivedImages(self, image, mask, s):
+        """(derived image, name, kwargs) of every enabled image type, in their order (featureextractor.py:371-396)"""
+        gens = []
+        for imageType, custom in self.enabledImagetypes.items():
+            args = s.copy()
+            args.update(custom)
+            gens = chain(gens, _IMAGE_TYPES[imageType](image, mask, **args))
+        return gens
 
     @staticmethod
     def _abandonFeatures(started):

@@ -87,6 +87,82 @@ def roiTensor(mask, label=1):
     return mask._derived[key]
 
 
+def _censusHost(arr):
+    """labelCensus on a host array, without a pass per label: the labelled voxels are grouped by one stable sort, counts are
+    the group sizes and the box of a label is the minimum / maximum of its group's indices along each axis"""
+    if not np.issubdtype(arr.dtype, np.integer) and arr.dtype != np.bool_:
+        whole = arr.astype(np.int64)
+        if not np.array_equal(whole, arr):
+            raise ValueError("labelCensus needs an integer label map")
+        arr = whole
+    flat = np.ascontiguousarray(arr).ravel()
+    idx = np.flatnonzero(flat > 0)
+    nd = arr.ndim
+    if len(idx) == 0:
+        z = np.zeros(0, dtype=np.int64)
+        return z, z.copy(), np.zeros((0, nd), dtype=np.int64), np.zeros((0, nd), dtype=np.int64)
+    vals = flat[idx].astype(np.int64)
+    order = np.argsort(vals, kind="stable")
+    labels, starts, counts = np.unique(vals[order], return_index=True, return_counts=True)
+    coords = np.unravel_index(idx[order], arr.shape)
+    lo = np.stack([np.minimum.reduceat(c, starts) for c in coords], axis=1).astype(np.int64)
+    hi = np.stack([np.maximum.reduceat(c, starts) for c in coords], axis=1).astype(np.int64)
+    return labels.astype(np.int64), counts.astype(np.int64), lo, hi
+
+
+def labelCensus(mask, deviceResident=None):
+    """Which labels a label map holds, with the voxel count and bounding box of each: -> (labels int64 [K] ascending, counts
+    int64 [K], lo int64 [K, Nd], hi int64 [K, Nd]), inclusive bounds in array (z, y, x) order, labels >= 1.  One pass over the
+    map on the device (engine.label_census) when the mask Image lives there or the backend works on device tensors
+    (`deviceResident` overrides: False = numpy); maps the device census does not take (more than 3 dimensions, labels above
+    65535, non-integer element types) are counted on the host, by one sort of the labelled voxels.  An Image uploads uint8 maps
+    as int16 (Image.device_tensor), so this route reads 2 bytes per voxel of such a map; the 1-byte kernel is reached with a
+    uint8 tensor through engine.label_census.  The result is memoised on the mask Image, and ("bbox", label) is pre-filled for every
+    present label so that cropToTumorMask finds its box without scanning.  (No reference analogue: the reference asks
+    sitk.LabelStatisticsImageFilter about one label per execute() call, imageoperations.py:407-445.)"""
+    msk = as_image(mask)
+    memo = msk._derived.get("census")
+    if memo is not None:
+        return memo["labels"], memo["counts"], memo["lo"], memo["hi"]
+    if deviceResident is None:
+        from . import backend
+        deviceResident = bool(getattr(backend.get(), "DEVICE_TENSORS", False))
+    res = None
+    if (msk.on_device or deviceResident) and len(msk.shape) in (2, 3):
+        t = msk.device_tensor()
+        if not t.dtype.is_floating_point:
+            engine = _engine()
+            try:
+                res = engine.label_census(t)
+            except engine.LabelRangeError:  # labels above engine.MAX_CENSUS_LABEL; any other failure is an error
+                res = None
+    if res is None:
+        res = _censusHost(msk.array)
+    labels, counts, lo, hi = res
+    msk._derived["census"] = {"labels": labels, "counts": counts, "lo": lo, "hi": hi,
+                              "index": {int(l): i for i, l in enumerate(labels)}}
+    for i, l in enumerate(labels):
+        msk._derived[("bbox", int(l))] = (lo[i].astype(int), hi[i].astype(int))
+    return res
+
+
+def censusLookup(mask, label):
+    """(count, lo, hi) of `label` from the census memoised on the mask Image -- count 0 and no box for an absent label --
+    or None when no census was taken (or it cannot speak for this label: labels below 1 are not counted)"""
+    memo = mask._derived.get("census") if isinstance(mask, Image) else None
+    if memo is None:
+        return None
+    try:
+        if label != int(label) or int(label) < 1:
+            return None
+    except (TypeError, ValueError):
+        return None
+    i = memo["index"].get(int(label))
+    if i is None:
+        return 0, None, None
+    return int(memo["counts"][i]), memo["lo"][i].astype(int), memo["hi"][i].astype(int)
+
+
 def cropToTumorMask(image, mask, label=1, padDistance=0, deviceResident=False, alignRows=True):
     """Crops image and mask to the ROI bounding box padded by `padDistance` voxels, clipped to the image
     (imageoperations.py:407-445).  Accepts / returns pyradiomics_amd.image.Image.  With `deviceResident` the crop
@@ -378,10 +454,16 @@ def sameGeometry(image, mask, tolerance=None):
 def _checkROI(image, mask, **kwargs):
     """imageoperations.py:341-402: the label must be present and the physical box of its ROI (voxel edges, hence the
     half voxel) must lie inside the image's, with the reference's 1e-3 voxel tolerance"""
-    label = int(kwargs.get("label", 1))
-    roi = mask.array == label
-    if not roi.any():
-        raise ValueError("Label (%d) not present in mask" % label)
+    label = kwargs.get("label", 1)
+    if label is None:                                          # (executeLabels without a label list: every label's voxels)
+        roi = mask.array != 0
+        if not roi.any():
+            raise ValueError("No labels found in this mask (i.e. nothing is segmented)!")
+    else:
+        label = int(label)
+        roi = mask.array == label
+        if not roi.any():
+            raise ValueError("Label (%d) not present in mask" % label)
     lo, hi = boundingBox(roi)                                  # numpy (z, y, x) order, inclusive
     lo_xyz, hi_xyz = lo[::-1].astype(np.float64), hi[::-1].astype(np.float64)
     mo, mm = _index_to_physical(mask)
@@ -460,6 +542,8 @@ def getMask(mask, **kwargs):
         mask = Image(np.ascontiguousarray(mask.array[..., channel]), mask.GetSpacing(), mask.GetOrigin(),
                      mask.GetDirection())
     arr = mask.array
+    if label is None:                  # (executeLabels without a label list: the channel is picked, its labels found later)
+        return mask
     if not np.any(arr == label):
         labels = np.unique(arr)
         if len(labels) == 1 and labels[0] == 0:

@@ -50,6 +50,9 @@ def get_parser():
                    help="(Batch mode) number of worker processes, spread round-robin over the GPUs")
     g.add_argument("--gpus", metavar="LIST", default=None,
                    help="Comma separated device indices to use (default: every visible GPU)")
+    g.add_argument("--all-labels", action="store_true",
+                   help="Segment mode: extract every label the mask holds (one output row per label, its value in the "
+                        "Label column) in one pass per case; a Label column of the batch file is ignored")
     g.add_argument("--validate", action="store_true", help="Only check that the input files exist")
     o = p.add_argument_group("Output")
     o.add_argument("--out", "-o", metavar="FILE", type=argparse.FileType("a"), default=sys.stdout,
@@ -180,6 +183,28 @@ def extract_segment(case_idx, case, extractor, out_dir=None):
     return fv
 
 
+def extract_segment_labels(case_idx, case, extractor):
+    """--all-labels: one row per label of the case's mask (RadiomicsFeatureExtractor.executeLabels: the case is loaded,
+    uploaded and filtered once), the label in the `Label` column the reference's batch files use (scripts/segment.py:60-66).
+    A case that fails keeps the rows of the labels extracted before the failure, or its bare row when there is none."""
+    rows = []
+    try:
+        t = time.perf_counter()
+        channel = case.get("Label_channel") or None
+        for label, result in extractor.executeLabels(case["Image"], case["Mask"],
+                                                     label_channel=int(channel) if channel is not None else None):
+            fv = collections.OrderedDict(case)
+            fv["Label"] = int(label)
+            fv.update((k, _scalar(v)) for k, v in result.items())
+            rows.append(fv)
+        logger.info("Case %s: %d labels processed in %.3f s", case_idx, len(rows), time.perf_counter() - t)
+    except (KeyboardInterrupt, SystemExit):
+        raise
+    except Exception as e:
+        logger.error("Feature extraction failed! : %s", e, exc_info=True)
+    return rows or [collections.OrderedDict(case)]
+
+
 def extract_voxel(case_idx, case, extractor, out_dir=None, unix_path=False):
     """scripts/voxel.py:37-88: feature maps of one case written as Case-<idx>_<feature>.nrrd, paths in the row"""
     from .image import Image, write_nrrd
@@ -208,20 +233,27 @@ def extract_voxel(case_idx, case, extractor, out_dir=None, unix_path=False):
 
 
 def _run_case(job):
-    case_idx, case, mode, out_dir, unix_path = job
+    case_idx, case, mode, out_dir, unix_path, all_labels = job
     ex = _WORKER["extractor"]
+    if mode == "segment" and all_labels:
+        return case_idx, extract_segment_labels(case_idx, case, ex)       # (a list of rows)
     if mode == "segment":
         return case_idx, extract_segment(case_idx, case, ex, out_dir)
     return case_idx, extract_voxel(case_idx, case, ex, out_dir, unix_path)
 
 
 def process_cases(cases, param, overrides, mode="segment", jobs=1, gpus=None, out_dir=None, unix_path=False,
-                  log_level="WARNING"):
-    """-> [feature row per case, input order].  jobs == 1 runs in this process on the current GPU."""
+                  log_level="WARNING", all_labels=False):
+    """-> [feature row per case, input order]; with all_labels (segment mode) one row per label of every case.  jobs == 1
+    runs in this process on the current GPU."""
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
     jobs = max(1, min(jobs, len(cases)))
-    work = [(i, c, mode, out_dir, unix_path) for i, c in cases]
+    all_labels = bool(all_labels) and mode == "segment"
+    work = [(i, c, mode, out_dir, unix_path, all_labels) for i, c in cases]
+
+    def flat(rows):
+        return [r for per_case in rows for r in per_case] if all_labels else rows
     if jobs == 1:
         from .featureextractor import RadiomicsFeatureExtractor
         if gpus:                                   # --gpus with a single job: that GPU, not whichever is current
@@ -229,7 +261,7 @@ def process_cases(cases, param, overrides, mode="segment", jobs=1, gpus=None, ou
             if torch.cuda.is_available():
                 torch.cuda.set_device(int(gpus[0]))
         _WORKER["extractor"] = RadiomicsFeatureExtractor(param, **overrides) if param else RadiomicsFeatureExtractor(**overrides)
-        return [_run_case(w)[1] for w in work]
+        return flat([_run_case(w)[1] for w in work])
     import multiprocessing as mp
     import torch
     if gpus is None:
@@ -238,7 +270,7 @@ def process_cases(cases, param, overrides, mode="segment", jobs=1, gpus=None, ou
     counter = ctx.Value("i", 0)
     with ctx.Pool(jobs, initializer=_init_worker, initargs=(param, overrides, gpus, counter, log_level)) as pool:
         done = dict(pool.imap_unordered(_run_case, work, chunksize=1))
-    return [done[i] for i, _ in cases]
+    return flat([done[i] for i, _ in cases])
 
 
 def write_results(results, out, fmt="txt", skip_nans=False, format_path="absolute", unix_path=False, relative_start="."):
@@ -311,7 +343,7 @@ def main(argv=None):
     try:
         gpus = [int(g) for g in args.gpus.split(",")] if args.gpus else None
         results = process_cases(cases, args.param, parse_overrides(args.setting, args.label), args.mode, args.jobs,
-                                gpus, args.out_dir, args.unix_path, level)
+                                gpus, args.out_dir, args.unix_path, level, all_labels=args.all_labels)
         write_results(results, args.out, args.format, args.skip_nans, args.format_path, args.unix_path, start)
     except (KeyboardInterrupt, SystemExit):
         logger.info("Cancelling Extraction")
