@@ -487,6 +487,41 @@ int prad_label_census_dev(const void *mask, int dtype, const int *size, int Nd, 
 int prad_label_census(const void *mask, int dtype, const int *size, int Nd, int max_label, long long *table);
 int prad_mask_max_dev(const void *mask, int dtype, long long n, long long *max_value, void *stream);
 
+/* ---- many small ROIs, one launch (no reference analogue: the reference builds one segment per call) --------------------
+ * B independent ROIs stored back to back: ROI b is the int32 level box [size[b][0]][size[b][1]][size[b][2]] (z, y, x,
+ * C-contiguous) that starts at ELEMENT off[b] of `levels`, with its uint8 mask at the same element of `mask`.  One
+ * workgroup per (ROI, angle group) packs the box into LDS and builds its matrices there (csrc/kernels_batch.h); every
+ * matrix equals what the single segment-mode call returns for that box:
+ *   PRAD_BATCH_GLCM   prad_calculate_glcm_dev   [Ng][Ng][Na]        Na = prad_get_angle_count(size, distances, unidirectional);
+ *                                                                   not symmetrised, as there
+ *   PRAD_BATCH_GLRLM  prad_calculate_glrlm_dev  [Ng][Nr][Na1]       Nr = max(size[b]); Na1 = the distance-1 count: the
+ *                                                                   reference's GLRLM ignores `distances` (_cmatrices.c:432-581)
+ *   PRAD_BATCH_GLDM   prad_calculate_gldm_dev   [Ng][2 Nb + 1]      Nb = 2 Na, the bidirectional count that call is given
+ *   PRAD_BATCH_NGTDM  prad_calculate_ngtdm_dev  [Ng][3]             (float column: the same sum as the single call, bit for bit)
+ * Each family is ONE flat float64 buffer, ROI after ROI; the call writes every element (no pre-zeroing).
+ * prad_batch_plan (host only, needs no device): out_offsets int64 [4][B + 1], row f (0 GLCM, 1 GLRLM, 2 GLDM, 3 NGTDM) =
+ *   first double of every ROI in that family's buffer and, at [B], the buffer's length (all zero for a family that is not in
+ *   `families`); Na int [2][B] = Na, then Na1.  Returns PRAD_OK, or PRAD_E_UNSUPPORTED -- outputs filled all the same -- when
+ *   prad_calculate_batch_dev would decline the batch.
+ * prad_calculate_batch_dev: levels / mask / outputs / status are DEVICE pointers, sizes ([B][3]) / off / distances HOST.
+ *   status int [B]: PRAD_OK, or PRAD_INDEX_ERROR for a ROI with a masked level outside [1, Ng] (the reference's IndexError;
+ *   its matrices are then those of an empty mask, the other ROIs are not affected).  An empty mask and a 1 x 1 x 1 box
+ *   (Na = 0: empty GLCM / GLRLM) are legal.  Covered: 1 <= Ng <= 64, boxes of at most prad_batch_max_vox() voxels, at most
+ *   127 angles per ROI; anything else returns PRAD_E_UNSUPPORTED for the whole batch before a launch (loop the single calls).
+ *   Enqueues one copy and one launch on `stream` and synchronises it; kernel family "batch" (prad_last_kernel_ms);
+ *   prad_last_path: "batch".  GLSZM is not batched: call prad_calculate_glszm_dev per ROI. */
+#define PRAD_BATCH_GLCM 1
+#define PRAD_BATCH_GLRLM 2
+#define PRAD_BATCH_GLDM 4
+#define PRAD_BATCH_NGTDM 8
+#define PRAD_BATCH_ALL 15
+int prad_batch_max_vox(void);
+int prad_batch_plan(const int *sizes, int B, int Ng, int families, const int *distances, int Ndist, long long *out_offsets,
+                    int *Na);
+int prad_calculate_batch_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B, int Ng,
+                             int families, const int *distances, int Ndist, int alpha, double *glcm, double *glrlm,
+                             double *gldm, double *ngtdm, int *status, void *stream);
+
 /* ---- filter stack in front of the matrices (radiomics/imageoperations.py:756-970) ---------------------------
  * The arithmetic of both filters lives in third-party wheels (PyWavelets, SimpleITK/ITK) that are not part of
  * the reference tree; these entry points implement their published algorithms (see oracle/filters_oracle.py):

@@ -313,6 +313,133 @@ def calculate_glszm_compact(image, mask, Ng, Ns, force2D, force2Ddimension):
     return P.cpu().numpy()[None], sizes
 
 
+# ---- many small ROIs, one launch (prad_batch_plan / prad_calculate_batch_dev; no reference analogue) --------
+BATCH_FAMILIES = ("glcm", "glrlm", "gldm", "ngtdm")      # bit f of the C `families` argument, row f of the offsets
+_batch_route = "none"
+
+
+def last_batch_route() -> str:
+    """which route served the last *_batch call: "batch" (one native launch) or "looped" (the single calls, ROI by ROI)"""
+    return _batch_route
+
+
+def _set_batch_route(route: str) -> None:
+    global _batch_route
+    _batch_route = route
+
+
+def batch_family_bits(families) -> int:
+    unknown = [f for f in families if f not in BATCH_FAMILIES]
+    if unknown or not families:
+        raise ValueError("families must be a non-empty subset of %s" % (BATCH_FAMILIES,))
+    return sum(1 << BATCH_FAMILIES.index(f) for f in set(families))
+
+
+def batch_plan(sizes, Ng, families=BATCH_FAMILIES, distances=(1,)):
+    """Host-side layout of a batch (prad_batch_plan; needs no device).  sizes: int [B, 3].  -> (covered, offsets int64
+    [4, B + 1], Na int32 [2, B]): covered = the native call takes the batch; offsets[f] = first double of every ROI in the
+    flat buffer of family BATCH_FAMILIES[f] (last entry: its length); Na[0] = unidirectional angle count of `distances`
+    (GLCM; GLDM rows hold 2 * (2 * Na) + 1 columns), Na[1] = that of distance 1 (GLRLM)."""
+    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
+    dist = np.ascontiguousarray(np.asarray(distances, dtype=np.intc).ravel())
+    B = int(sizes.shape[0])
+    offsets = np.zeros((4, B + 1), dtype=np.int64)
+    Na = np.zeros((2, B), dtype=np.intc)
+    rc = _lib.load().prad_batch_plan(_iptr(sizes), B, int(Ng), batch_family_bits(families), _iptr(dist), int(dist.shape[0]),
+                                     offsets.ctypes.data_as(C.POINTER(C.c_longlong)), _iptr(Na))
+    if rc != _lib.PRAD_OK and rc != _lib.PRAD_E_UNSUPPORTED:
+        _lib.raise_for(rc, "batch plan")
+    return rc == _lib.PRAD_OK, offsets, Na
+
+
+def batch_shapes(sizes, Ng, Na):
+    """{family: [shape of ROI b]} for the plan's Na"""
+    sizes = np.asarray(sizes).reshape(-1, 3)
+    return {"glcm": [(Ng, Ng, int(a)) for a in Na[0]],
+            "glrlm": [(Ng, int(max(s)), int(a)) for s, a in zip(sizes, Na[1])],
+            "gldm": [(Ng, 4 * int(a) + 1) for a in Na[0]],
+            "ngtdm": [(Ng, 3) for _ in Na[0]]}
+
+
+def _one_voxel_matrices(level, masked, Ng, fam):
+    """the matrices of a 1 x 1 x 1 box (no angle exists: the single calls refuse it, cmatrices.c computes these)"""
+    if fam in ("glcm", "glrlm"):
+        return np.zeros((Ng, Ng if fam == "glcm" else 1, 0))
+    out = np.zeros((Ng, 1 if fam == "gldm" else 3))
+    if fam == "ngtdm":
+        out[:, 2] = np.arange(1, Ng + 1)
+    if masked:
+        if not 1 <= level <= Ng:
+            raise IndexError("level outside [1, Ng]")
+        out[level - 1, 0] = 1
+    return out
+
+
+def _looped_matrices(image, mask, Ng, families, dist, alpha, shapes_b):
+    """one ROI through the single calls (host arrays or device tensors) -> ({family: numpy matrix}, status)"""
+    try:
+        if int(np.prod(image.shape)) == 1:
+            lv, mk = int(image.reshape(-1)[0]), bool(mask.reshape(-1)[0])
+            return {f: _one_voxel_matrices(lv, mk, Ng, f) for f in families}, _lib.PRAD_OK
+        out = {}
+        if "glcm" in families:
+            out["glcm"] = calculate_glcm(image, mask, dist, Ng, False, 0)[0][0]
+        if "glrlm" in families:
+            out["glrlm"] = calculate_glrlm(image, mask, Ng, int(max(image.shape)), False, 0)[0][0]
+        if "gldm" in families:
+            out["gldm"] = calculate_gldm(image, mask, dist, Ng, alpha, False, 0)[0]
+        if "ngtdm" in families:
+            out["ngtdm"] = calculate_ngtdm(image, mask, dist, Ng, False, 0)[0]
+        return out, _lib.PRAD_OK
+    except IndexError:          # a masked level outside [1, Ng]: as the native route, the matrices of an empty mask
+        out = {f: np.zeros(shapes_b[f]) for f in families}
+        if "ngtdm" in out:
+            out["ngtdm"][:, 2] = np.arange(1, Ng + 1)
+        return out, _lib.PRAD_INDEX_ERROR
+
+
+def calculate_matrices_batch(images, masks, Ng, families=BATCH_FAMILIES, distances=(1,), gldm_a=0):
+    """GLCM / GLRLM / GLDM / NGTDM of B small 3-D ROIs (lists of host arrays: int levels, bool masks) with one upload, one
+    native call and one download per family.  -> ({family: [B numpy matrices in the single calls' layouts]}, status [B]:
+    1, or 0 for a ROI with a masked level outside [1, Ng] -- the single calls' IndexError; its matrices are void).
+    Where the native call does not cover the batch (Ng > 64, a box above prad_batch_max_vox() voxels, > 127 angles) or no
+    device is visible, the single calls are looped ROI by ROI (and raise as they do without a device); last_batch_route()
+    tells which.  GLSZM is not batched: calculate_glszm per ROI."""
+    families = tuple(families)
+    batch_family_bits(families)
+    if len(images) != len(masks):
+        raise ValueError("images and masks differ in number")
+    parsed = [_parse_arrays(i, m) for i, m in zip(images, masks)]
+    if any(p[0].ndim != 3 for p in parsed):
+        raise ValueError("the batched matrices take 3-D ROIs")
+    dist = [int(d) for d in np.asarray(distances).ravel()]
+    sizes = np.array([p[2] for p in parsed], dtype=np.intc).reshape(-1, 3)
+    covered, offsets, Na = batch_plan(sizes, Ng, families, dist)
+    shapes = batch_shapes(sizes, int(Ng), Na)
+    B = len(parsed)
+    if not covered or _lib.load().prad_device_count() < 1:
+        _set_batch_route("looped")
+        mats, status = {f: [] for f in families}, []
+        for b, (img, msk, _) in enumerate(parsed):
+            one, st = _looped_matrices(img, msk, int(Ng), families, dist, int(gldm_a), {f: shapes[f][b] for f in families})
+            for f in families:
+                mats[f].append(one[f])
+            status.append(st)
+        return mats, status
+    import torch
+    engine = _engine()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    flat_l = torch.from_numpy(np.concatenate([p[0].ravel() for p in parsed])).to(dev) if B else torch.empty(0, dtype=torch.int32, device=dev)
+    flat_m = torch.from_numpy(np.concatenate([p[1].ravel().view(np.uint8) for p in parsed])).to(dev) if B else torch.empty(0, dtype=torch.uint8, device=dev)
+    flat, status = engine.texture_matrices_batch_flat(flat_l, flat_m, sizes, int(Ng), families, dist, int(gldm_a))
+    mats = {}
+    for f in families:
+        host = flat[f].cpu().numpy()
+        o = offsets[BATCH_FAMILIES.index(f)]
+        mats[f] = [host[o[b]:o[b + 1]].reshape(shapes[f][b]) for b in range(B)]
+    return mats, status
+
+
 # ---- fused voxel-based features of the other four texture classes (prad_voxel_texture_features_dev) ---------
 _ZONE_LIKE = {
     "glrlm": (3, ["ShortRunEmphasis", "LongRunEmphasis", "GrayLevelNonUniformity", "GrayLevelNonUniformityNormalized",

@@ -1,0 +1,188 @@
+// prad_batch.hip -- C ABI of the batched small-ROI texture matrices (include/pyradiomics_amd.h: prad_batch_plan,
+// prad_calculate_batch_dev); translation unit of libpyradiomics_amd.so.
+#include "kernels_batch.h"
+
+#include <algorithm>
+
+using namespace prad;
+
+namespace {
+
+const int kOne = 1;
+
+struct BatchLayout {
+  std::vector<long long> offsets;   // [4][B + 1]
+  std::vector<int> na;              // [2][B]: requested distances, distance 1
+  bool in_domain = true;
+  char why[160] = {0};
+};
+
+// Shapes of the per-ROI outputs, the same arithmetic the single calls use: Na = prad_get_angle_count (unidirectional),
+// GLCM [Ng][Ng][Na], GLRLM [Ng][max(size)][Na1] (distance 1), GLDM [Ng][2 Nb + 1] with Nb = 2 Na, NGTDM [Ng][3].
+// Host only: no device is touched.
+int batch_layout(const int *sizes, int B, int Ng, int families, const int *distances, int Ndist, BatchLayout *lay) {
+  if (B < 0 || (B > 0 && !sizes)) return fail(PRAD_E_ARG, "batch: B=%d, sizes=%p", B, (const void *)sizes);
+  if (Ng < 1) return fail(PRAD_E_ARG, "batch: Ng=%d < 1", Ng);
+  if (!distances || Ndist < 1) return fail(PRAD_E_ARG, "batch: no distances");
+  if (families < 1 || families > PRAD_BATCH_ALL) return fail(PRAD_E_ARG, "batch: families=%d outside [1, %d]", families, PRAD_BATCH_ALL);
+  for (int k = 0; k < Ndist; k++)
+    if (distances[k] < 1) return fail(PRAD_E_ARG, "batch: distance %d < 1", distances[k]);
+  lay->offsets.assign((size_t)4 * (B + 1), 0);
+  lay->na.assign((size_t)2 * B, 0);
+  if (Ng > PRAD_BATCH_MAX_NG) {
+    lay->in_domain = false;
+    snprintf(lay->why, sizeof(lay->why), "Ng=%d above %d", Ng, PRAD_BATCH_MAX_NG);
+  }
+  long long *o = lay->offsets.data();
+  for (int b = 0; b < B; b++) {
+    const int *sz = sizes + 3 * b;
+    for (int d = 0; d < 3; d++)
+      if (sz[d] < 1) return fail(PRAD_E_ARG, "batch: ROI %d has size[%d]=%d < 1", b, d, sz[d]);
+    const long long nvox = (long long)sz[0] * sz[1] * sz[2];
+    const int na = prad_get_angle_count(sz, distances, 3, Ndist, 0, -1);
+    const int na1 = prad_get_angle_count(sz, &kOne, 3, 1, 0, -1);
+    lay->na[b] = na;
+    lay->na[(size_t)B + b] = na1;
+    if (lay->in_domain && nvox > PRAD_BATCH_MAX_VOX) {
+      lay->in_domain = false;
+      snprintf(lay->why, sizeof(lay->why), "ROI %d holds %lld voxels, above %d", b, nvox, PRAD_BATCH_MAX_VOX);
+    }
+    if (lay->in_domain && na > PRAD_BATCH_MAX_NA) {
+      lay->in_domain = false;
+      snprintf(lay->why, sizeof(lay->why), "ROI %d has %d angles, above %d", b, na, PRAD_BATCH_MAX_NA);
+    }
+    const long long Nr = std::max(sz[0], std::max(sz[1], sz[2]));
+    const long long per[4] = {(long long)Ng * Ng * na, (long long)Ng * Nr * na1, (long long)Ng * (4 * na + 1), (long long)Ng * 3};
+    for (int f = 0; f < 4; f++)
+      o[(size_t)f * (B + 1) + b + 1] = o[(size_t)f * (B + 1) + b] + ((families >> f) & 1 ? per[f] : 0);
+  }
+  return PRAD_OK;
+}
+
+}  // namespace
+
+extern "C" int prad_batch_max_vox(void) { return PRAD_BATCH_MAX_VOX; }
+
+extern "C" int prad_batch_plan(const int *sizes, int B, int Ng, int families, const int *distances, int Ndist,
+                               long long *out_offsets, int *Na) {
+  if (!out_offsets || !Na) return fail(PRAD_E_ARG, "batch plan: NULL output");
+  BatchLayout lay;
+  PRAD_TRY(batch_layout(sizes, B, Ng, families, distances, Ndist, &lay));
+  std::copy(lay.offsets.begin(), lay.offsets.end(), out_offsets);
+  std::copy(lay.na.begin(), lay.na.end(), Na);
+  if (!lay.in_domain) return fail(PRAD_E_UNSUPPORTED, "batch: %s (use the single calls per ROI)", lay.why);
+  return PRAD_OK;
+}
+
+extern "C" int prad_calculate_batch_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off,
+                                        int B, int Ng, int families, const int *distances, int Ndist, int alpha,
+                                        double *glcm, double *glrlm, double *gldm, double *ngtdm, int *status,
+                                        void *stream) {
+  BatchLayout lay;
+  PRAD_TRY(batch_layout(sizes, B, Ng, families, distances, Ndist, &lay));
+  if (!lay.in_domain) return fail(PRAD_E_UNSUPPORTED, "batch: %s (use the single calls per ROI)", lay.why);   // nothing launched
+  if (B == 0) return PRAD_OK;
+  double *outs[4] = {glcm, glrlm, gldm, ngtdm};
+  for (int f = 0; f < 4; f++) {
+    if (!((families >> f) & 1)) outs[f] = nullptr;
+    else if (!outs[f] && lay.offsets[(size_t)f * (B + 1) + B] > 0) return fail(PRAD_E_ARG, "batch: output %d is NULL", f);
+  }
+  if (!levels || !mask || !off || !status) return fail(PRAD_E_ARG, "batch: NULL pointer");
+  if (alpha < 0) return fail(PRAD_E_ARG, "batch: alpha=%d < 0", alpha);
+  for (int b = 0; b < B; b++)
+    if (off[b] < 0) return fail(PRAD_E_ARG, "batch: off[%d]=%lld < 0", b, off[b]);
+  Context &c = ctx();
+  PRAD_TRY(c.ensure_device());
+  hipStream_t s = (hipStream_t)stream;
+
+  // ---- per-ROI records and the concatenated angle tables (prad_build_angles), one upload -----------------------------------
+  const bool runs = (families & PRAD_BATCH_GLRLM) != 0, same = Ndist == 1 && distances[0] == 1;
+  size_t nang = 0;
+  for (int b = 0; b < B; b++) nang += (size_t)lay.na[b] + (runs && !same ? (size_t)lay.na[(size_t)B + b] : 0);
+  const size_t roi_bytes = (sizeof(BatchRoi) * (size_t)B + 15) & ~(size_t)15;
+  const size_t meta_bytes = roi_bytes + sizeof(int) * 3 * std::max<size_t>(nang, 1);
+  void *h_meta = nullptr, *d_meta = nullptr;
+  PRAD_TRY(c.get_pinned("batch_meta", meta_bytes, &h_meta));
+  PRAD_TRY(c.get("batch_meta", meta_bytes, &d_meta));
+  BatchRoi *rois = (BatchRoi *)h_meta;
+  int *angles = (int *)((char *)h_meta + roi_bytes);
+  long long max_vox = 1;
+  int max_na = 0, max_nr = 1;
+  size_t row = 0;
+  for (int b = 0; b < B; b++) {
+    const int *sz = sizes + 3 * b;
+    BatchRoi &r = rois[b];
+    r.off = off[b];
+    for (int f = 0; f < 4; f++) r.out[f] = lay.offsets[(size_t)f * (B + 1) + b];
+    r.nz = sz[0], r.ny = sz[1], r.nx = sz[2];
+    r.na = lay.na[b];
+    r.na_run = lay.na[(size_t)B + b];
+    r.pad = 0;
+    r.ang = (int)row;
+    if (r.na > 0 && prad_build_angles(sz, distances, 3, Ndist, -1, r.na, angles + 3 * row) != 0)
+      return fail(PRAD_E_ARG, "batch: angles of ROI %d", b);
+    row += (size_t)r.na;
+    r.ang_run = r.ang;
+    if (runs && !same) {
+      r.ang_run = (int)row;
+      if (r.na_run > 0 && prad_build_angles(sz, &kOne, 3, 1, -1, r.na_run, angles + 3 * row) != 0)
+        return fail(PRAD_E_ARG, "batch: distance-1 angles of ROI %d", b);
+      row += (size_t)r.na_run;
+    }
+    max_vox = std::max(max_vox, (long long)sz[0] * sz[1] * sz[2]);
+    max_na = std::max(max_na, r.na);
+    max_nr = std::max(max_nr, std::max(sz[0], std::max(sz[1], sz[2])));
+  }
+
+  // ---- launch geometry ------------------------------------------------------------------------------------------------------
+  BatchArgs A;
+  A.levels = levels;
+  A.mask = mask;
+  A.rois = (const BatchRoi *)d_meta;
+  A.angles = (const int *)((const char *)d_meta + roi_bytes);
+  A.Ng = Ng;
+  A.alpha = alpha;
+  A.glcm = outs[0], A.glrlm = outs[1], A.gldm = outs[2], A.ngtdm = outs[3];
+  A.status = status;
+  // Angle groups per ROI: every group packs the ROI again, so a large batch takes one group per family (B workgroups fill the
+  // card by themselves) and a small one splits its angles until ~2048 workgroups exist (PRAD_BATCH_GROUPS overrides).
+  static const int fixed = getenv("PRAD_BATCH_GROUPS") ? atoi(getenv("PRAD_BATCH_GROUPS")) : 0;
+  const int pair_fams = (outs[0] ? 1 : 0) + (outs[1] ? 1 : 0);
+  int groups = fixed > 0 ? fixed : (int)((2048 + (long long)B * std::max(pair_fams, 1) - 1) / ((long long)B * std::max(pair_fams, 1)));
+  groups = std::max(1, std::min(groups, 13));
+  A.groups_glcm = outs[0] ? groups : 0;
+  A.groups_glrlm = outs[1] ? groups : 0;
+  A.neigh = (outs[2] || outs[3]) ? 1 : 0;
+  if (!A.groups_glcm && !A.groups_glrlm) A.neigh = 1;   // (only empty matrices asked for: a job per ROI still gives its status)
+  // table region: up to PRAD_BATCH_ANGLES_AT_ONCE angles of GLCM / GLRLM at once, every level of GLDM + NGTDM, within the
+  // budget; never below one GLCM angle, one GLRLM column per level, one level of GLDM + NGTDM
+  const long long W = 2LL * max_na + 1;
+  long long words = 64;
+  if (outs[0]) words = std::max(words, (long long)PRAD_BATCH_ANGLES_AT_ONCE * Ng * Ng);
+  if (outs[1]) words = std::max(words, (long long)PRAD_BATCH_ANGLES_AT_ONCE * Ng * max_nr);
+  if (A.neigh) words = std::max(words, 2 * W * Ng);
+  words = std::min<long long>(words, PRAD_BATCH_TABLE_BYTES / 4);
+  words = std::max<long long>(words, std::max<long long>((long long)Ng * Ng, 2 * W));   // (both below the budget: Ng <= 64, Na <= 127)
+  A.table_words = (int)words;
+  const size_t lds = PRAD_BATCH_MISC_BYTES + 4 * (size_t)words + (((size_t)max_vox + 15) & ~(size_t)15);
+  if (lds > 160 * 1024 / 2) return fail(PRAD_E_HIP, "batch: %zu bytes of LDS per workgroup", lds);
+  const long long jobs = A.groups_glcm + A.groups_glrlm + A.neigh;
+  if ((long long)B * jobs > 0x7fffffffLL) return fail(PRAD_E_UNSUPPORTED, "batch: %d ROIs x %lld jobs", B, jobs);
+
+  PRAD_TRY(c.begin_call(s));
+  PRAD_HIP(hipMemcpyAsync(d_meta, h_meta, meta_bytes, hipMemcpyHostToDevice, s));
+  if (lds > 64 * 1024)
+    PRAD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_rois_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int rc;
+  {
+    Timed t(c, "batch", s);
+    hipLaunchKernelGGL(batch_rois_kernel, dim3((unsigned)(B * jobs)), dim3(PRAD_BATCH_THREADS), lds, s, A);
+    rc = check_launch("batch_rois_kernel");
+  }
+  PRAD_TRY(c.end_call(s));
+  if (rc != PRAD_OK) return rc;
+  PRAD_HIP(hipStreamSynchronize(s));   // (the pinned record block is reused by the next call)
+  c.last_path = "batch";
+  c.last_variant = "batch-lds";
+  return PRAD_OK;
+}

@@ -11,6 +11,7 @@ import numpy as np
 import torch  # imported before the HIP library so both share one libamdhip64 instance
 
 from . import _lib
+from . import cmatrices as _cm
 from .cmatrices import _build_angles, _iptr
 
 
@@ -642,6 +643,122 @@ def gldm_ngtdm(image: torch.Tensor, mask: torch.Tensor, Ng: int, alpha: int = 0,
     if deferred:
         _deferred_keep.append((image, mask, g, n))
     return g, n
+
+
+# ---- many small ROIs, one launch (prad_calculate_batch_dev, csrc/kernels_batch.h) ----------------------------------
+def batch_max_vox() -> int:
+    """voxels of the largest ROI box the batched call takes (PRAD_BATCH_MAX_VOX)"""
+    return int(_lib.load().prad_batch_max_vox())
+
+
+def last_batch_route() -> str:
+    """ "batch" when the last texture_matrices_batch call was served by the one native launch, "looped" when it went through
+    the single calls ROI by ROI"""
+    return _cm.last_batch_route()
+
+
+def _batch_inputs(levels, masks, sizes):
+    """-> (flat int32 levels, flat uint8 mask, sizes int32 [B, 3]) on one device"""
+    if isinstance(levels, (list, tuple)):
+        if len(levels) != len(masks):
+            raise ValueError("levels and masks differ in number")
+        if any(l.dim() != 3 or l.shape != m.shape for l, m in zip(levels, masks)):
+            raise ValueError("the batched matrices take 3-D ROIs with masks of the same shape")
+        sizes = np.array([tuple(l.shape) for l in levels], dtype=np.intc).reshape(-1, 3)
+        if not len(levels):
+            raise ValueError("empty batch")
+        levels = torch.cat([l.reshape(-1).to(torch.int32) for l in levels])
+        masks = torch.cat([(m if m.dtype in (torch.bool, torch.uint8) else m != 0).reshape(-1).view(torch.uint8) for m in masks])
+    elif sizes is None:
+        raise ValueError("flat level / mask tensors need `sizes`")
+    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
+    levels, masks = levels.reshape(-1), masks.reshape(-1)
+    lib, levels, masks, _ = _prep(levels, masks)
+    if int(sizes.astype(np.int64).prod(1).sum()) != levels.numel():
+        raise ValueError("sizes describe %d voxels, the buffers hold %d" % (int(sizes.astype(np.int64).prod(1).sum()), levels.numel()))
+    return lib, levels, masks, sizes
+
+
+def texture_matrices_batch_flat(levels, masks, sizes, Ng, families=_cm.BATCH_FAMILIES, distances=(1,), gldm_a=0):
+    """the native call alone: -> ({family: flat float64 device buffer}, status list), or None when it declines the batch"""
+    lib, levels, masks, sizes = _batch_inputs(levels, masks, sizes)
+    families = tuple(families)
+    dist = np.ascontiguousarray(np.asarray(list(distances), dtype=np.intc).ravel())
+    B = int(sizes.shape[0])
+    covered, offsets, _ = _cm.batch_plan(sizes, Ng, families, dist)
+    if not covered:
+        return None
+    off = np.zeros(B, dtype=np.int64)
+    off[1:] = np.cumsum(sizes.astype(np.int64).prod(1))[:-1]
+    dev = levels.device
+    flat = {f: torch.empty(int(offsets[_cm.BATCH_FAMILIES.index(f), B]), dtype=torch.float64, device=dev) for f in families}
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    ptr = [C.c_void_p(flat[f].data_ptr()) if f in flat else None for f in _cm.BATCH_FAMILIES]
+    rc = lib.prad_calculate_batch_dev(C.c_void_p(levels.data_ptr()), C.c_void_p(masks.data_ptr()), _iptr(sizes),
+                                      off.ctypes.data_as(C.POINTER(C.c_longlong)), B, int(Ng), _cm.batch_family_bits(families),
+                                      _iptr(dist), int(dist.shape[0]), int(gldm_a), ptr[0], ptr[1], ptr[2], ptr[3],
+                                      C.c_void_p(status.data_ptr()), _stream_ptr())
+    if rc == _lib.PRAD_E_UNSUPPORTED:
+        return None
+    _lib.raise_for(rc, "batched texture matrices")
+    _cm._set_batch_route("batch")
+    return flat, status.tolist()
+
+
+def texture_matrices_batch(levels, masks, sizes, Ng, families=_cm.BATCH_FAMILIES, distances=(1,), gldm_a=0):
+    """GLCM / GLRLM / GLDM / NGTDM of B small ROIs in ONE launch (segment mode, 3-D).  levels / masks: lists of 3-D device
+    tensors (concatenated here; `sizes` is then ignored), or flat device tensors holding the ROIs back to back plus `sizes`
+    (int [B, 3]).  -> ({family: [B float64 device tensors, views into one flat buffer, in the single calls' layouts:
+    glcm [Ng, Ng, Na], glrlm [Ng, max(size), Na1], gldm [Ng, 2 * Nb + 1] with Nb = 2 * Na, ngtdm [Ng, 3]]}, status [B]: 1,
+    or 0 for a ROI with a masked level outside [1, Ng] -- the single calls' IndexError; its matrices are void).
+    Covered: Ng <= 64, boxes of at most batch_max_vox() voxels, at most 127 angles; otherwise the single calls are looped ROI
+    by ROI (same results, separate tensors) and last_batch_route() says "looped".  GLSZM is not batched: engine.glszm per ROI."""
+    lib, levels, masks, sizes = _batch_inputs(levels, masks, sizes)
+    families = tuple(families)
+    dist = [int(d) for d in distances]
+    B = int(sizes.shape[0])
+    _, offsets, Na = _cm.batch_plan(sizes, Ng, families, dist)
+    shapes = _cm.batch_shapes(sizes, int(Ng), Na)
+    res = texture_matrices_batch_flat(levels, masks, sizes, Ng, families, dist, gldm_a)
+    if res is not None:
+        flat, status = res
+        mats = {}
+        for f in families:
+            o = offsets[_cm.BATCH_FAMILIES.index(f)]
+            mats[f] = [flat[f][int(o[b]):int(o[b + 1])].view(shapes[f][b]) for b in range(B)]
+        return mats, status
+    _cm._set_batch_route("looped")
+    mats, status = {f: [] for f in families}, []
+    dev, start = levels.device, 0
+    for b in range(B):
+        shape = tuple(int(s) for s in sizes[b])
+        n = shape[0] * shape[1] * shape[2]
+        img, msk = levels[start:start + n].view(shape), masks[start:start + n].view(shape)
+        start += n
+        try:
+            if n == 1:      # no angle exists: the single calls refuse the box
+                one = {f: torch.from_numpy(_cm._one_voxel_matrices(int(img.item()), bool(msk.item()), int(Ng), f)).to(dev)
+                       for f in families}
+            else:
+                one = {}
+                if "glcm" in families:
+                    one["glcm"] = glcm(img, msk, int(Ng), dist)[0]
+                if "glrlm" in families:
+                    one["glrlm"] = glcm_glrlm(img, msk, int(Ng), max(shape), want_glcm=False)[1]
+                if "gldm" in families:
+                    one["gldm"] = gldm(img, msk, int(Ng), int(gldm_a), dist)
+                if "ngtdm" in families:
+                    one["ngtdm"] = ngtdm(img, msk, int(Ng), dist)
+            st = _lib.PRAD_OK
+        except IndexError:          # as the native route: status 0, the matrices of an empty mask
+            one = {f: torch.zeros(shapes[f][b], dtype=torch.float64, device=dev) for f in families}
+            if "ngtdm" in one:
+                one["ngtdm"][:, 2] = torch.arange(1, int(Ng) + 1, dtype=torch.float64, device=dev)
+            st = _lib.PRAD_INDEX_ERROR
+        for f in families:
+            mats[f].append(one[f])
+        status.append(st)
+    return mats, status
 
 
 NEIGH_GLDM, NEIGH_NGTDM = 0, 1
