@@ -509,7 +509,7 @@ int prad_mask_max_dev(const void *mask, int dtype, long long n, long long *max_v
  *   (Na = 0: empty GLCM / GLRLM) are legal.  Covered: 1 <= Ng <= 64, boxes of at most prad_batch_max_vox() voxels, at most
  *   127 angles per ROI; anything else returns PRAD_E_UNSUPPORTED for the whole batch before a launch (loop the single calls).
  *   Enqueues one copy and one launch on `stream` and synchronises it; kernel family "batch" (prad_last_kernel_ms);
- *   prad_last_path: "batch".  GLSZM is not batched: call prad_calculate_glszm_dev per ROI. */
+ *   prad_last_path: "batch".  GLSZM has entry points of its own (below): the shape of its output depends on the data. */
 #define PRAD_BATCH_GLCM 1
 #define PRAD_BATCH_GLRLM 2
 #define PRAD_BATCH_GLDM 4
@@ -521,6 +521,36 @@ int prad_batch_plan(const int *sizes, int B, int Ng, int families, const int *di
 int prad_calculate_batch_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B, int Ng,
                              int families, const int *distances, int Ndist, int alpha, double *glcm, double *glrlm,
                              double *gldm, double *ngtdm, int *status, void *stream);
+
+/* ---- GLSZM of many small ROIs (csrc/kernels_batch_glszm.h) -------------------------------------------------------------
+ * The same batch layout (levels / mask DEVICE, sizes [B][3] / off HOST).  One workgroup per ROI packs the box into LDS and
+ * labels its zones there -- the full 26-neighbourhood at distance 1 inside the box, which is the angle set the single call
+ * is given for a 3-D segment (an axis of length 1 has no neighbours along it) -- then a second launch histograms the zone
+ * lists.  Between the two the caller reads `summary` back and lays the matrices out: their shapes depend on the data.
+ * prad_batch_glszm_dev: all outputs are DEVICE pointers.
+ *   zones   int32: the zone list of ROI b starts at int 2 * off[b] and may use 2 * nvox_b ints (a ROI has at most nvox
+ *           zones): (level, size) pairs in the reference's tempData order, raster order of each zone's first voxel
+ *           (cmatrices.c:255-276), without the closing -1.  The ints of the region beyond the 2 * summary[b][0] of the pairs
+ *           hold scratch values.
+ *   summary int32 [B][3]: number of zones, largest zone size (0 if none), number of distinct zone sizes
+ *   status  int32 [B]: PRAD_OK, or PRAD_INDEX_ERROR for a ROI with a masked level outside [1, Ng]; that ROI is void (no
+ *           zones, summary 0, 0, 0), the others are not affected.  An empty mask gives no zones and PRAD_OK (the single
+ *           call's answer for Ns >= 1).
+ *   Covered: 1 <= Ng <= 64 and boxes of at most prad_batch_glszm_max_vox() = 54528 voxels (37^3 fits); anything else returns
+ *   PRAD_E_UNSUPPORTED for the whole batch after the arguments are checked and before anything is launched or written.
+ * prad_batch_glszm_fill_dev: zones / out / sizes_out DEVICE, summary_host (the summary read back) / off / the offsets HOST.
+ *   compact == 0: out + out_offsets[b] is float64 [Ng][max(summary[b][1], 1)], the layout of prad_fill_glszm_dev;
+ *   compact != 0: float64 [Ng][max(summary[b][2], 1)], column c counting the zones of the c-th distinct size, and
+ *   sizes_out + sizes_offsets[b] int32 [summary[b][2]] ascending: prad_glszm_sizes + prad_fill_glszm_compact_dev.
+ *   Every element of a ROI's slice is written, zeros included.  A pair that does not fit the summary is skipped.
+ * Both enqueue one copy and one launch on `stream` and synchronise it; kernel family "batch_glszm"; prad_last_path "batch",
+ * prad_last_variant "batch-glszm-lds". */
+int prad_batch_glszm_max_vox(void);
+int prad_batch_glszm_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B, int Ng,
+                         int *zones, int *summary, int *status, void *stream);
+int prad_batch_glszm_fill_dev(const int *zones, const int *summary_host, const long long *off, int B, int Ng, int compact,
+                              double *out, const long long *out_offsets, int *sizes_out, const long long *sizes_offsets,
+                              void *stream);
 
 /* ---- filter stack in front of the matrices (radiomics/imageoperations.py:756-970) ---------------------------
  * The arithmetic of both filters lives in third-party wheels (PyWavelets, SimpleITK/ITK) that are not part of

@@ -112,6 +112,10 @@ SYMBOLS = {
     "prad_batch_plan": (C.c_int, [_ip, C.c_int, C.c_int, C.c_int, _ip, C.c_int, C.POINTER(C.c_longlong), _ip]),
     "prad_calculate_batch_dev": (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_longlong), C.c_int, C.c_int, C.c_int, _ip, C.c_int,
                                            C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "prad_batch_glszm_max_vox": (C.c_int, []),
+    "prad_batch_glszm_dev": (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_longlong), C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "prad_batch_glszm_fill_dev": (C.c_int, [_vp, _ip, C.POINTER(C.c_longlong), C.c_int, C.c_int, C.c_int, _vp,
+                                            C.POINTER(C.c_longlong), _vp, C.POINTER(C.c_longlong), _vp]),
     "prad_swt_level1": (C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp]),
     "prad_swt_level1_dev": (C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp, _vp]),
     "prad_swt_level1_any_dev": (C.c_int, [_vp, C.c_int, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp, _vp]),

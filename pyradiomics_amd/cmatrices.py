@@ -319,7 +319,8 @@ _batch_route = "none"
 
 
 def last_batch_route() -> str:
-    """which route served the last *_batch call: "batch" (one native launch) or "looped" (the single calls, ROI by ROI)"""
+    """which route served the last *_batch call: "batch" (the native launch), "looped" (the single calls, ROI by ROI) or, for
+    the GLSZM batch, "mixed" (ROIs outside the native domain looped, the others batched)"""
     return _batch_route
 
 
@@ -404,7 +405,7 @@ def calculate_matrices_batch(images, masks, Ng, families=BATCH_FAMILIES, distanc
     1, or 0 for a ROI with a masked level outside [1, Ng] -- the single calls' IndexError; its matrices are void).
     Where the native call does not cover the batch (Ng > 64, a box above prad_batch_max_vox() voxels, > 127 angles) or no
     device is visible, the single calls are looped ROI by ROI (and raise as they do without a device); last_batch_route()
-    tells which.  GLSZM is not batched: calculate_glszm per ROI."""
+    tells which.  GLSZM: calculate_glszm_batch."""
     families = tuple(families)
     batch_family_bits(families)
     if len(images) != len(masks):
@@ -438,6 +439,55 @@ def calculate_matrices_batch(images, masks, Ng, families=BATCH_FAMILIES, distanc
         o = offsets[BATCH_FAMILIES.index(f)]
         mats[f] = [host[o[b]:o[b + 1]].reshape(shapes[f][b]) for b in range(B)]
     return mats, status
+
+
+def calculate_glszm_batch(images, masks, Ng, compact=False):
+    """GLSZM of B small 3-D ROIs (lists of host arrays: int levels, bool masks) with one upload and the two launches of
+    engine.glszm_batch.  -> (list of B results, status [B]: 1, or 0 for a ROI with a masked level outside [1, Ng] -- the
+    single call's IndexError; its result is that of an empty mask).  compact=False: a result is the float64 matrix [Ng,
+    max(maxRegion, 1)] of calculate_glszm (without its leading axis); compact=True: (P [Ng, k], sizes int32 [k]) as
+    calculate_glszm_compact.  With no device visible the single calls are looped ROI by ROI (and raise as they do without a
+    device); last_batch_route() tells which route ran."""
+    if len(images) != len(masks):
+        raise ValueError("images and masks differ in number")
+    parsed = [_parse_arrays(i, m) for i, m in zip(images, masks)]
+    if any(p[0].ndim != 3 for p in parsed):
+        raise ValueError("the batched GLSZM takes 3-D ROIs")
+    Ng = int(Ng)
+    B = len(parsed)
+    if _lib.load().prad_device_count() < 1:
+        _set_batch_route("looped")
+        results, status = [], []
+        for img, msk, _ in parsed:
+            try:
+                if img.size == 1:       # no angle exists: the single call refuses the box
+                    lv, mk = int(img.reshape(-1)[0]), bool(msk.reshape(-1)[0])
+                    if mk and not 1 <= lv <= Ng:
+                        raise IndexError("level outside [1, Ng]")
+                    P = np.zeros((Ng, 1))
+                    if mk:
+                        P[lv - 1, 0] = 1
+                else:
+                    P = calculate_glszm(img, msk, Ng, max(1, int(msk.sum())), False, 0)[0]
+                st = _lib.PRAD_OK
+            except IndexError:
+                P, st = np.zeros((Ng, 1)), _lib.PRAD_INDEX_ERROR
+            if compact:
+                cols = np.flatnonzero(P.any(0))
+                P = (np.ascontiguousarray(P[:, cols]), (cols + 1).astype(np.intc))
+            results.append(P)
+            status.append(st)
+        return results, status
+    import torch
+    engine = _engine()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    sizes = np.array([p[2] for p in parsed], dtype=np.intc).reshape(-1, 3)
+    flat_l = torch.from_numpy(np.concatenate([p[0].ravel() for p in parsed])).to(dev) if B else torch.empty(0, dtype=torch.int32, device=dev)
+    flat_m = torch.from_numpy(np.concatenate([p[1].ravel().view(np.uint8) for p in parsed])).to(dev) if B else torch.empty(0, dtype=torch.uint8, device=dev)
+    results, status = engine.glszm_batch(flat_l, flat_m, sizes, Ng, compact=compact)
+    if compact:
+        return [(P.cpu().numpy(), s) for P, s in results], status
+    return [P.cpu().numpy() for P in results], status
 
 
 # ---- fused voxel-based features of the other four texture classes (prad_voxel_texture_features_dev) ---------

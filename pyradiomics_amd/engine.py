@@ -652,8 +652,8 @@ def batch_max_vox() -> int:
 
 
 def last_batch_route() -> str:
-    """ "batch" when the last texture_matrices_batch call was served by the one native launch, "looped" when it went through
-    the single calls ROI by ROI"""
+    """ "batch" when the last texture_matrices_batch / glszm_batch call was served by the native launch, "looped" when it went
+    through the single calls ROI by ROI, "mixed" (glszm_batch only) when some ROIs of the batch took each route"""
     return _cm.last_batch_route()
 
 
@@ -712,7 +712,7 @@ def texture_matrices_batch(levels, masks, sizes, Ng, families=_cm.BATCH_FAMILIES
     glcm [Ng, Ng, Na], glrlm [Ng, max(size), Na1], gldm [Ng, 2 * Nb + 1] with Nb = 2 * Na, ngtdm [Ng, 3]]}, status [B]: 1,
     or 0 for a ROI with a masked level outside [1, Ng] -- the single calls' IndexError; its matrices are void).
     Covered: Ng <= 64, boxes of at most batch_max_vox() voxels, at most 127 angles; otherwise the single calls are looped ROI
-    by ROI (same results, separate tensors) and last_batch_route() says "looped".  GLSZM is not batched: engine.glszm per ROI."""
+    by ROI (same results, separate tensors) and last_batch_route() says "looped".  GLSZM: glszm_batch."""
     lib, levels, masks, sizes = _batch_inputs(levels, masks, sizes)
     families = tuple(families)
     dist = [int(d) for d in distances]
@@ -759,6 +759,116 @@ def texture_matrices_batch(levels, masks, sizes, Ng, families=_cm.BATCH_FAMILIES
             mats[f].append(one[f])
         status.append(st)
     return mats, status
+
+
+# ---- GLSZM of many small ROIs (prad_batch_glszm_dev / prad_batch_glszm_fill_dev, csrc/kernels_batch_glszm.h) -------------------
+def batch_glszm_max_vox() -> int:
+    """voxels of the largest ROI box the batched GLSZM takes (PRAD_BATCH_GLSZM_MAX_VOX)"""
+    return int(_lib.load().prad_batch_glszm_max_vox())
+
+
+def _lp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_longlong))
+
+
+def _glszm_batch_label(lib, levels, masks, sizes, off, Ng):
+    """the labelling launch on the ROIs (sizes[b], off[b]) of the flat buffers -> (zones int32 device buffer indexed by
+    2 * off[b], summary int32 numpy [B, 3], status int32 numpy [B]); summary and status come back in ONE copy"""
+    B = int(sizes.shape[0])
+    dev = levels.device
+    zones = torch.empty(2 * levels.numel(), dtype=torch.int32, device=dev)
+    meta = torch.empty(4 * B, dtype=torch.int32, device=dev)
+    rc = lib.prad_batch_glszm_dev(C.c_void_p(levels.data_ptr()), C.c_void_p(masks.data_ptr()), _iptr(sizes), _lp(off), B, int(Ng),
+                                  C.c_void_p(zones.data_ptr()), C.c_void_p(meta.data_ptr()),
+                                  C.c_void_p(meta.data_ptr() + 12 * B), _stream_ptr())
+    _lib.raise_for(rc, "batched GLSZM")
+    host = meta.cpu().numpy()
+    return zones, np.ascontiguousarray(host[:3 * B].reshape(B, 3)), host[3 * B:].copy()
+
+
+def _glszm_batch_split(sizes, Ng):
+    """-> (element offset of every ROI, indices of the ROIs the native launch covers)"""
+    nvox = sizes.astype(np.int64).prod(1)
+    off = np.zeros(len(nvox), dtype=np.int64)
+    off[1:] = np.cumsum(nvox)[:-1]
+    covered = np.flatnonzero(nvox <= batch_glszm_max_vox()) if int(Ng) <= 64 else np.zeros(0, dtype=np.int64)
+    return off, covered
+
+
+def _one_voxel_glszm(level, masked, Ng, compact, dev):
+    """the GLSZM of a 1 x 1 x 1 box (no angle exists: the single call refuses it)"""
+    if masked and not 1 <= level <= Ng:
+        raise IndexError("level outside [1, Ng]")
+    P = torch.zeros((Ng, 1), dtype=torch.float64, device=dev)
+    if masked:
+        P[level - 1, 0] = 1
+    if not compact:
+        return P
+    return (P, np.ones(1, dtype=np.intc)) if masked else (P[:, :0], np.zeros(0, dtype=np.intc))
+
+
+def glszm_batch_zones(levels, masks, sizes, Ng):
+    """the zone lists of B small ROIs from the labelling launch alone -> (list of B int32 device tensors [nzones, 2] of
+    (level, size) in raster order of each zone's first voxel -- views into one buffer --, summary int32 numpy [B, 3]: zones,
+    largest zone, distinct sizes; status int32 numpy [B]).  Raises NotImplementedError outside the native domain (Ng > 64, a box
+    above batch_glszm_max_vox() voxels)."""
+    lib, levels, masks, sizes = _batch_inputs(levels, masks, sizes)
+    off, _ = _glszm_batch_split(sizes, Ng)
+    zones, summary, status = _glszm_batch_label(lib, levels, masks, sizes, off, Ng)
+    _cm._set_batch_route("batch")
+    return [zones[2 * int(o):2 * int(o) + 2 * int(n)].view(-1, 2) for o, n in zip(off, summary[:, 0])], summary, status
+
+
+def glszm_batch(levels, masks, sizes, Ng, compact=True):
+    """GLSZM of B small ROIs in two launches (segment mode, 3-D, the full neighbourhood): zones labelled in LDS by one workgroup
+    per ROI, one read-back of the per-ROI summary, one fill.  Inputs as texture_matrices_batch.  -> (list of B results, status
+    [B]: 1, or 0 for a ROI with a masked level outside [1, Ng] -- the single call's IndexError; its result is that of an empty
+    mask).  compact=True: a result is (P float64 [Ng, k] device tensor, sizes int32 numpy [k] ascending) as glszm_compact
+    returns; compact=False: the dense [Ng, max(maxRegion, 1)] tensor as glszm returns.  The results of the native route are
+    views into one flat buffer.  ROIs above batch_glszm_max_vox() voxels, or every ROI when Ng > 64, go through glszm_compact /
+    glszm one by one (Ns = max(1, masked voxels)); last_batch_route() says "batch", "mixed" or "looped"."""
+    lib, levels, masks, sizes = _batch_inputs(levels, masks, sizes)
+    Ng = int(Ng)
+    B = int(sizes.shape[0])
+    dev = levels.device
+    off, covered = _glszm_batch_split(sizes, Ng)
+    results, status = [None] * B, [_lib.PRAD_OK] * B
+    if len(covered):
+        csz, coff = np.ascontiguousarray(sizes[covered]), np.ascontiguousarray(off[covered])
+        zones, summary, st = _glszm_batch_label(lib, levels, masks, csz, coff, Ng)
+        cols = np.maximum(summary[:, 2 if compact else 1], 1).astype(np.int64)
+        out_off = np.zeros(len(covered) + 1, dtype=np.int64)
+        out_off[1:] = np.cumsum(Ng * cols)
+        k = summary[:, 2].astype(np.int64)
+        s_off = np.zeros(len(covered) + 1, dtype=np.int64)
+        s_off[1:] = np.cumsum(k)
+        flat = torch.empty(int(out_off[-1]), dtype=torch.float64, device=dev)
+        sizes_dev = torch.empty(max(int(s_off[-1]), 1), dtype=torch.int32, device=dev)
+        rc = lib.prad_batch_glszm_fill_dev(C.c_void_p(zones.data_ptr()), _iptr(summary), _lp(coff), len(covered), Ng,
+                                           1 if compact else 0, C.c_void_p(flat.data_ptr()), _lp(out_off),
+                                           C.c_void_p(sizes_dev.data_ptr()), _lp(s_off), _stream_ptr())
+        _lib.raise_for(rc, "batched GLSZM fill")
+        sizes_host = sizes_dev.cpu().numpy() if compact else None
+        for i, b in enumerate(covered):
+            P = flat[int(out_off[i]):int(out_off[i + 1])].view(Ng, int(cols[i]))
+            results[b] = (P[:, :int(k[i])], sizes_host[s_off[i]:s_off[i + 1]].copy()) if compact else P
+            status[b] = int(st[i])
+    rest = sorted(set(range(B)) - set(int(b) for b in covered))
+    for b in rest:
+        shape = tuple(int(s) for s in sizes[b])
+        n = shape[0] * shape[1] * shape[2]
+        img, msk = levels[int(off[b]):int(off[b]) + n].view(shape), masks[int(off[b]):int(off[b]) + n].view(shape)
+        try:
+            if n == 1:
+                results[b] = _one_voxel_glszm(int(img.item()), bool(msk.item()), Ng, compact, dev)
+            else:
+                Ns = max(1, int(msk.sum().item()))
+                results[b] = glszm_compact(img, msk, Ng, Ns) if compact else glszm(img, msk, Ng, Ns)
+        except IndexError:          # as the native route: status 0, the result of an empty mask
+            results[b] = _one_voxel_glszm(0, False, Ng, compact, dev)
+            status[b] = _lib.PRAD_INDEX_ERROR
+    _cm._set_batch_route("looped" if not len(covered) else ("mixed" if rest else "batch"))
+    return results, status
 
 
 NEIGH_GLDM, NEIGH_NGTDM = 0, 1
