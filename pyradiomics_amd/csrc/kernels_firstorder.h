@@ -61,13 +61,14 @@ __device__ __forceinline__ double fo_block_sum(double v, double *sh) {
 // ROI scan shared by every pass: threads t, t + nthreads, ... take 16-byte pieces (8 int16 / 4 float32 / 2 float64 voxels
 // with their 8 / 4 / 2 mask bytes) of [first, last) in a fixed assignment, so a pass issues one wide load per 2..8
 // voxels instead of two narrow ones per voxel (the scalar form ran at a fifth of HBM speed: load-issue bound).
-// f(x) is called for every ROI voxel of the thread, in index order.  Unaligned views take the scalar form.
+// f(x) is called for every ROI voxel of the thread, in index order.  Unaligned views load the same pieces voxel by
+// voxel: the assignment of voxels to threads, and with it every partial sum, does not depend on where the arrays lie.
 template <typename T, typename F>
 __device__ __forceinline__ void fo_scan(const T *__restrict__ img, const uint8_t *__restrict__ mask, long long first,
                                         long long last, long long t, long long nthreads, F f) {
   constexpr int E = 16 / (int)sizeof(T);
+  const long long nvec = (last - first) / E;
   if ((((uintptr_t)(img + first)) & 15) == 0 && (((uintptr_t)(mask + first)) & (E - 1)) == 0) {
-    const long long nvec = (last - first) / E;
     for (long long v = t; v < nvec; v += nthreads) {
       const long long i = first + v * E;
       const uint4 q = *reinterpret_cast<const uint4 *>(img + i);
@@ -81,12 +82,16 @@ __device__ __forceinline__ void fo_scan(const T *__restrict__ img, const uint8_t
       for (int e = 0; e < E; e++)
         if (mk[e]) f((double)vals[e]);
     }
-    for (long long i = first + nvec * E + t; i < last; i += nthreads)
-      if (mask[i]) f((double)img[i]);
   } else {
-    for (long long i = first + t; i < last; i += nthreads)
-      if (mask[i]) f((double)img[i]);
+    for (long long v = t; v < nvec; v += nthreads) {
+      const long long i = first + v * E;
+#pragma unroll
+      for (int e = 0; e < E; e++)
+        if (mask[i + e]) f((double)img[i + e]);
+    }
   }
+  for (long long i = first + nvec * E + t; i < last; i += nthreads)
+    if (mask[i]) f((double)img[i]);
 }
 
 // The reductions read the image and the mask directly, in raster order with a fixed block layout, so their partial
