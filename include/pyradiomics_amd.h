@@ -552,6 +552,45 @@ int prad_batch_glszm_fill_dev(const int *zones, const int *summary_host, const l
                               double *out, const long long *out_offsets, int *sizes_out, const long long *sizes_offsets,
                               void *stream);
 
+/* ---- feature formulas of many small ROIs (csrc/kernels_batch_features.h) -------------------------------------------------
+ * The formulas of prad_glcm_features_dev, prad_glcm_mcc_dev, prad_zone_matrix_features_dev and prad_ngtdm_features_dev on the
+ * flat buffers of the two batched matrix calls above: one launch for every matrix of the batch, a second one for MCC.  A
+ * workgroup evaluates one matrix with the device function, the thread count and the order of additions of the single call, so
+ * every value equals the single call's bit for bit.  ROI b produces, in one flat float64 output,
+ *   PRAD_BATCH_GLCM   Na_b rows of 24: the 23 sum features in the order of prad_glcm_features_dev, then MCC (NaN for an angle
+ *                     without pairs, and everywhere when want_mcc == 0)
+ *   PRAD_BATCH_GLRLM  Na1_b rows of 16 (size values 1 .. max(size[b]))
+ *   PRAD_BATCH_GLDM   one row of 16 (size values 1 .. 2 Nb + 1)
+ *   PRAD_BATCH_NGTDM  one row of 5
+ *   PRAD_BATCH_GLSZM  one row of 16; glszm_cols[b] = columns of the ROI's matrix [Ng][glszm_cols[b]], i.e. max(summary[b][2], 1)
+ *                     compact and max(summary[b][1], 1) dense.  glszm_cols[b] <= 0: the ROI's GLSZM is not in the buffer (it
+ *                     was outside the domain of prad_batch_glszm_dev); its row is laid out but not written.
+ * and one int32 `empty` flag per row (1: the matrix is all zero and the row is NaN; NGTDM: no level occurs, the row is what
+ * prad_ngtdm_features_dev gives).  Na is the int [2][B] of prad_batch_plan.
+ * prad_batch_features_plan (host only, needs no device).  Deviations from a plain row table, because rows differ in width:
+ *   out_offsets int64 [2][5][B + 1]: [0][f][b] = first DOUBLE of ROI b's rows of family f (0 GLCM .. 3 NGTDM, 4 GLSZM) in `out`,
+ *   [1][f][b] = its first ROW, i.e. index into `empty`; families follow one another, [.][f][B] = end of family f (a family
+ *   that is not asked for takes no space); nrec int64 [3] = records (workgroups) of the first launch, GLCM angles (workgroups
+ *   of the MCC launch), doubles of scratch.  Returns PRAD_OK, or PRAD_E_UNSUPPORTED -- outputs filled all the same -- when
+ *   prad_batch_features_dev would decline: covered is 1 <= Ng <= 64.
+ * prad_batch_features_dev: sizes / Na / glszm_cols / offsets / glszm_offsets / glszm_sizes_offsets HOST; the matrices,
+ *   glszm_sizes, out and empty DEVICE.  offsets int64 [4][B + 1] as prad_batch_plan writes them (only [f][b], b < B, is read:
+ *   the first double of ROI b's matrix, which has the shape prad_calculate_batch_dev gives it); glszm_offsets int64 [B] likewise
+ *   for the GLSZM buffer.  glszm_sizes: the int32 sizes_out of prad_batch_glszm_fill_dev with glszm_sizes_offsets [B] (an entry
+ *   < 0: size value j + 1 for that ROI); NULL: dense matrices, size value j + 1.  The size values are widened to double in the
+ *   kernel (exact).  Buffers of families that are not asked for may be NULL.  Anything outside the domain returns
+ *   PRAD_E_UNSUPPORTED before a launch and writes nothing.  Enqueues one copy and one launch (two with want_mcc) on `stream`
+ *   and synchronises it; kernel family "batch_features"; prad_last_path "batch", prad_last_variant "batch-features". */
+#define PRAD_BATCH_GLSZM 16
+#define PRAD_BATCH_FEATURES_ALL 31
+int prad_batch_features_plan(const int *sizes, int B, int Ng, int families, const int *Na, const int *glszm_cols,
+                             long long *out_offsets, long long *nrec);
+int prad_batch_features_dev(const int *sizes, int B, int Ng, int families, const int *Na, const int *glszm_cols,
+                            const double *glcm, const double *glrlm, const double *gldm, const double *ngtdm,
+                            const long long *offsets, const double *glszm, const long long *glszm_offsets,
+                            const int *glszm_sizes, const long long *glszm_sizes_offsets, int symmetric, int want_mcc,
+                            double *out, int *empty, void *stream);
+
 /* ---- filter stack in front of the matrices (radiomics/imageoperations.py:756-970) ---------------------------
  * The arithmetic of both filters lives in third-party wheels (PyWavelets, SimpleITK/ITK) that are not part of
  * the reference tree; these entry points implement their published algorithms (see oracle/filters_oracle.py):

@@ -116,6 +116,11 @@ SYMBOLS = {
     "prad_batch_glszm_dev": (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_longlong), C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "prad_batch_glszm_fill_dev": (C.c_int, [_vp, _ip, C.POINTER(C.c_longlong), C.c_int, C.c_int, C.c_int, _vp,
                                             C.POINTER(C.c_longlong), _vp, C.POINTER(C.c_longlong), _vp]),
+    "prad_batch_features_plan": (C.c_int, [_ip, C.c_int, C.c_int, C.c_int, _ip, _ip, C.POINTER(C.c_longlong),
+                                           C.POINTER(C.c_longlong)]),
+    "prad_batch_features_dev": (C.c_int, [_ip, C.c_int, C.c_int, C.c_int, _ip, _ip, _vp, _vp, _vp, _vp, C.POINTER(C.c_longlong),
+                                          _vp, C.POINTER(C.c_longlong), _vp, C.POINTER(C.c_longlong), C.c_int, C.c_int, _vp,
+                                          _vp, _vp]),
     "prad_swt_level1": (C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp]),
     "prad_swt_level1_dev": (C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp, _vp]),
     "prad_swt_level1_any_dev": (C.c_int, [_vp, C.c_int, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp, _vp]),

@@ -490,6 +490,37 @@ def calculate_glszm_batch(images, masks, Ng, compact=False):
     return [P.cpu().numpy() for P in results], status
 
 
+def batch_feature_names(cls):
+    """the columns of engine.texture_features_batch for class `cls` (None: a slot that is no feature of the class)"""
+    return VOXEL_GLCM_FEATURES + ["MCC"] if cls == "glcm" else list(_ZONE_LIKE[cls][1])
+
+
+def calculate_features_batch(images, masks, Ng, classes=("glcm", "glrlm", "glszm", "gldm", "ngtdm"), distances=(1,), gldm_a=0,
+                             symmetricalGLCM=True, mcc=True):
+    """The texture features of B small 3-D ROIs (lists of host arrays: int levels, bool masks): one upload, the batched matrix
+    calls and the batched formulas of engine.texture_features_batch.  -> {class: {feature name: float64 [B]}}; a ROI with a masked level
+    outside [1, Ng] (the single calls' IndexError) has NaN everywhere, the others are not affected.  The names are those of the feature classes
+    (VOXEL_*_FEATURES, plus "MCC").  Needs a device (RuntimeError without one); last_batch_route() tells which route ran."""
+    if len(images) != len(masks):
+        raise ValueError("images and masks differ in number")
+    parsed = [_parse_arrays(i, m) for i, m in zip(images, masks)]
+    if not parsed or any(p[0].ndim != 3 for p in parsed):
+        raise ValueError("the batched features take a non-empty list of 3-D ROIs")
+    if _lib.load().prad_device_count() < 1:
+        raise RuntimeError("no HIP device: the batched features are evaluated on the device")
+    import torch
+    engine = _engine()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    sizes = np.array([p[2] for p in parsed], dtype=np.intc).reshape(-1, 3)
+    flat_l = torch.from_numpy(np.concatenate([p[0].ravel() for p in parsed])).to(dev)
+    flat_m = torch.from_numpy(np.concatenate([p[1].ravel().view(np.uint8) for p in parsed])).to(dev)
+    table, _ = engine.texture_features_batch(flat_l, flat_m, sizes, int(Ng), tuple(classes),
+                                             [int(d) for d in np.asarray(distances).ravel()], int(gldm_a),
+                                             bool(symmetricalGLCM), bool(mcc))
+    return {cls: {name: table[cls][:, i].copy() for i, name in enumerate(batch_feature_names(cls)) if name}
+            for cls in table}
+
+
 # ---- fused voxel-based features of the other four texture classes (prad_voxel_texture_features_dev) ---------
 _ZONE_LIKE = {
     "glrlm": (3, ["ShortRunEmphasis", "LongRunEmphasis", "GrayLevelNonUniformity", "GrayLevelNonUniformityNormalized",

@@ -78,15 +78,17 @@ __device__ __forceinline__ double feat_block_max(double v, double *shw) {
   return r;
 }
 
-// counts: [Ng][Ng][Na] float64 (reference layout).  out: [Na][GF_COUNT]; empty[a] = 1 when the angle has no pair.
-__global__ void __launch_bounds__(PRAD_FEAT_THREADS) glcm_matrix_features_kernel(const double *__restrict__ counts,
-                                                                                 int Ng, int Na, int symmetric,
-                                                                                 double *__restrict__ out,
-                                                                                 int *__restrict__ empty) {
+// The formulas are __device__ functions of one workgroup of PRAD_FEAT_THREADS threads: the single-call kernels below and the
+// batched kernel (kernels_batch_features.h) call the same code on a matrix, so both give the same bits.  Every function takes
+// the matrix, the angle `a` it evaluates, its output row `o`, the slot of its "empty" flag and its LDS.
+//
+// counts: [Ng][Ng][Na] float64 (reference layout).  o: [GF_COUNT] of angle a; *empty = 1 when the angle has no pair.
+// fs: 5 Ng + PRAD_FEAT_WAVES doubles of LDS.
+__device__ __forceinline__ void glcm_features_block(const double *__restrict__ counts, int Ng, int Na, int a, int symmetric,
+                                                    double *__restrict__ o, int *__restrict__ empty, double *fs) {
 #pragma clang fp contract(off)
-  extern __shared__ double fs[];
   double *px = fs, *py = px + Ng, *psum = py + Ng, *pdif = psum + 2 * Ng, *sh4 = pdif + Ng;   // sizes Ng, Ng, 2Ng, Ng, 4
-  const int a = blockIdx.x, t = threadIdx.x;
+  const int t = threadIdx.x;
   const double eps = PRAD_FEAT_EPS;
   auto C = [&](int i, int j) -> double {
     const double v = counts[((size_t)i * Ng + j) * Na + a];
@@ -97,11 +99,11 @@ __global__ void __launch_bounds__(PRAD_FEAT_THREADS) glcm_matrix_features_kernel
   for (int e = t; e < n2; e += PRAD_FEAT_THREADS) tot += C(e / Ng, e % Ng);
   tot = feat_block_sum(tot, sh4);
   if (tot == 0) {
-    if (t == 0) empty[a] = 1;
-    for (int f = t; f < GF_COUNT; f += PRAD_FEAT_THREADS) out[(size_t)a * GF_COUNT + f] = __builtin_nan("");
+    if (t == 0) *empty = 1;
+    for (int f = t; f < GF_COUNT; f += PRAD_FEAT_THREADS) o[f] = __builtin_nan("");
     return;
   }
-  if (t == 0) empty[a] = 0;
+  if (t == 0) *empty = 0;
   // marginals: one row / column / (anti-)diagonal per thread, in index order
   for (int i = t; i < Ng; i += PRAD_FEAT_THREADS) {
     double r = 0, c = 0;
@@ -211,7 +213,6 @@ __global__ void __launch_bounds__(PRAD_FEAT_THREADS) glcm_matrix_features_kernel
   sa = feat_block_sum(sa, sh4);
   se = -feat_block_sum(se, sh4);
   if (t == 0) {
-    double *o = out + (size_t)a * GF_COUNT;
     const double sigx = sqrt(vx), sigy = sqrt(vy);
     o[GF_Autocorrelation] = autoc;
     o[GF_JointAverage] = ux;
@@ -239,6 +240,17 @@ __global__ void __launch_bounds__(PRAD_FEAT_THREADS) glcm_matrix_features_kernel
     o[GF_SumSquares] = vx;
   }
 }
+#ifndef PRAD_DEVICE_FUNCTIONS_ONLY
+// out: [Na][GF_COUNT]; empty: [Na]; one workgroup per angle
+__global__ void __launch_bounds__(PRAD_FEAT_THREADS) glcm_matrix_features_kernel(const double *__restrict__ counts,
+                                                                                 int Ng, int Na, int symmetric,
+                                                                                 double *__restrict__ out,
+                                                                                 int *__restrict__ empty) {
+  extern __shared__ double fs[];
+  const int a = blockIdx.x;
+  glcm_features_block(counts, Ng, Na, a, symmetric, out + (size_t)a * GF_COUNT, empty + a, fs);
+}
+#endif
 
 // ---- GLRLM / GLSZM / GLDM ------------------------------------------------------------------------------------
 enum { ZM_SmallEmphasis = 0, ZM_LargeEmphasis, ZM_GrayLevelNonUniformity, ZM_GrayLevelNonUniformityNormalized,
@@ -247,19 +259,17 @@ enum { ZM_SmallEmphasis = 0, ZM_LargeEmphasis, ZM_GrayLevelNonUniformity, ZM_Gra
        ZM_SmallHighGrayLevelEmphasis, ZM_LargeLowGrayLevelEmphasis, ZM_LargeHighGrayLevelEmphasis, ZM_COUNT };
 
 static_assert(ZM_COUNT == 16, "prad_api.hip (ZM_FEATURES) and include/pyradiomics_amd.h say 16 zone-matrix features");
-// P(i, j, a) = counts[i * si + j * sj + a * sa]; level value = i + 1; size value = jvals[j] (jvals == NULL: j + 1).
-// scratch: [Na][Ni + Nj] float64 (marginals).  out: [Na][ZM_COUNT]; empty[a] = 1 when the matrix of angle a is all zero.
-__global__ void __launch_bounds__(PRAD_FEAT_THREADS) zone_matrix_features_kernel(
-    const double *__restrict__ counts, int Ni, int Nj, int Na, long long si, long long sj, long long sa,
-    const double *__restrict__ jvals, double *__restrict__ scratch, double *__restrict__ out, int *__restrict__ empty,
-    const int *__restrict__ nj_dev = nullptr) {
+// P(i, j, a) = counts[i * si + j * sj + a * sa]; level value = i + 1; size value = jval(j), a double.
+// pg: [Ni + Nj] float64 of global scratch (marginals).  o: [ZM_COUNT] of angle a; *empty = 1 when the matrix of angle a is all
+// zero.  sh4: PRAD_FEAT_WAVES doubles of LDS, shn: 13 * PRAD_FEAT_WAVES.
+template <class JV>
+__device__ __forceinline__ void zone_features_block(const double *__restrict__ counts, int Ni, int Nj, int a, long long si,
+                                                    long long sj, long long sa, JV jval, double *__restrict__ pg,
+                                                    double *__restrict__ o, int *__restrict__ empty, double *sh4, double *shn) {
 #pragma clang fp contract(off)
-  __shared__ double sh4[PRAD_FEAT_WAVES];
-  __shared__ double shn[13 * PRAD_FEAT_WAVES];
-  const int a = blockIdx.x, t = threadIdx.x;
-  if (nj_dev) Nj = min(Nj, nj_dev[0]);      // (the column count was found on the device: glszm_rank_kernel; Nj = capacity)
+  const int t = threadIdx.x;
   const double eps = PRAD_FEAT_EPS;
-  double *pg = scratch + (size_t)a * (Ni + Nj), *pj = pg + Ni;
+  double *pj = pg + Ni;
   auto P = [&](int i, int j) -> double { return counts[i * si + j * sj + a * sa]; };
   // row sums: one wave per level row, lanes stride over the sizes, shuffle tree (a GLSZM row has thousands of columns:
   // one thread per row was 100+ us of dependent loads); the order of the additions is fixed, so runs reproduce
@@ -287,11 +297,11 @@ __global__ void __launch_bounds__(PRAD_FEAT_THREADS) zone_matrix_features_kernel
   for (int i = t; i < Ni; i += PRAD_FEAT_THREADS) n += pg[i];
   n = feat_block_sum(n, sh4);
   if (n == 0) {
-    if (t == 0) empty[a] = 1;
-    for (int f = t; f < ZM_COUNT; f += PRAD_FEAT_THREADS) out[(size_t)a * ZM_COUNT + f] = __builtin_nan("");
+    if (t == 0) *empty = 1;
+    for (int f = t; f < ZM_COUNT; f += PRAD_FEAT_THREADS) o[f] = __builtin_nan("");
     return;
   }
-  if (t == 0) empty[a] = 0;
+  if (t == 0) *empty = 0;
   double i1 = 0, i2 = 0, inv_i2 = 0, mg = 0;
   for (int i = t; i < Ni; i += PRAD_FEAT_THREADS) {
     const double g = pg[i], iv = i + 1;
@@ -302,7 +312,7 @@ __global__ void __launch_bounds__(PRAD_FEAT_THREADS) zone_matrix_features_kernel
   }
   double j1 = 0, j2 = 0, inv_j2 = 0, mj = 0;
   for (int j = t; j < Nj; j += PRAD_FEAT_THREADS) {
-    const double s = pj[j], jv = jvals ? jvals[j] : (double)(j + 1);
+    const double s = pj[j], jv = jval(j);
     j1 += s * jv;
     j2 += s * (jv * jv);
     inv_j2 += s / (jv * jv);
@@ -317,7 +327,7 @@ __global__ void __launch_bounds__(PRAD_FEAT_THREADS) zone_matrix_features_kernel
     const int i = (int)(e / Nj), j = (int)(e - (long long)i * Nj);
     const double v = P(i, j);
     if (v == 0) continue;
-    const double iv = i + 1, jv = jvals ? jvals[j] : (double)(j + 1), i2v = iv * iv, j2v = jv * jv, ri2 = 1.0 / i2v, rj2 = 1.0 / j2v, p = v * rn;
+    const double iv = i + 1, jv = jval(j), i2v = iv * iv, j2v = jv * jv, ri2 = 1.0 / i2v, rj2 = 1.0 / j2v, p = v * rn;
     ent += p * log2(p + eps);
     c1 += v * (ri2 * rj2);
     c2 += v * (i2v * rj2);
@@ -337,7 +347,7 @@ __global__ void __launch_bounds__(PRAD_FEAT_THREADS) zone_matrix_features_kernel
     vi += (pg[i] / n) * (d * d);
   }
   for (int j = t; j < Nj; j += PRAD_FEAT_THREADS) {
-    const double d = (jvals ? jvals[j] : (double)(j + 1)) - uj;
+    const double d = jval(j) - uj;
     vj += (pj[j] / n) * (d * d);
   }
   {
@@ -346,7 +356,6 @@ __global__ void __launch_bounds__(PRAD_FEAT_THREADS) zone_matrix_features_kernel
     vi = r[0]; vj = r[1];
   }
   if (t == 0) {
-    double *o = out + (size_t)a * ZM_COUNT;
     o[ZM_SmallEmphasis] = inv_j2 / n;
     o[ZM_LargeEmphasis] = j2 / n;
     o[ZM_GrayLevelNonUniformity] = mg / n;
@@ -365,14 +374,28 @@ __global__ void __launch_bounds__(PRAD_FEAT_THREADS) zone_matrix_features_kernel
     o[ZM_LargeHighGrayLevelEmphasis] = c4 / n;
   }
 }
+#ifndef PRAD_DEVICE_FUNCTIONS_ONLY
+// size value = jvals[j] (jvals == NULL: j + 1).  scratch: [Na][Ni + Nj] float64.  out: [Na][ZM_COUNT]; empty: [Na]
+__global__ void __launch_bounds__(PRAD_FEAT_THREADS) zone_matrix_features_kernel(
+    const double *__restrict__ counts, int Ni, int Nj, int Na, long long si, long long sj, long long sa,
+    const double *__restrict__ jvals, double *__restrict__ scratch, double *__restrict__ out, int *__restrict__ empty,
+    const int *__restrict__ nj_dev = nullptr) {
+  __shared__ double sh4[PRAD_FEAT_WAVES];
+  __shared__ double shn[13 * PRAD_FEAT_WAVES];
+  const int a = blockIdx.x;
+  if (nj_dev) Nj = min(Nj, nj_dev[0]);      // (the column count was found on the device: glszm_rank_kernel; Nj = capacity)
+  auto jval = [&](int j) -> double { return jvals ? jvals[j] : (double)(j + 1); };
+  zone_features_block(counts, Ni, Nj, a, si, sj, sa, jval, scratch + (size_t)a * (Ni + Nj), out + (size_t)a * ZM_COUNT,
+                      empty + a, sh4, shn);
+}
+#endif
 
 // ---- NGTDM (ngtdm.py:133-287): P[Ng][3] = (n_i, s_i, level) -> Coarseness, Contrast, Busyness, Complexity, Strength ----
-__global__ void __launch_bounds__(PRAD_FEAT_THREADS) ngtdm_matrix_features_kernel(const double *__restrict__ P, int Ng,
-                                                                                  double *__restrict__ out) {
+// ns: 3 Ng + PRAD_FEAT_WAVES doubles of LDS, ngp_sh: one int of LDS
+__device__ __forceinline__ void ngtdm_features_block(const double *__restrict__ P, int Ng, double *__restrict__ out, double *ns,
+                                                     int *ngp_sh) {
 #pragma clang fp contract(off)
-  extern __shared__ double ns[];
   double *pi = ns, *si = pi + Ng, *lv = si + Ng, *sh4 = lv + Ng;     // present levels, compacted in level order
-  __shared__ int ngp_s;
   const int t = threadIdx.x;
   if (t == 0) {                       // compaction in level order (Ng <= a few hundred: serial is fine)
     int k = 0;
@@ -383,10 +406,10 @@ __global__ void __launch_bounds__(PRAD_FEAT_THREADS) ngtdm_matrix_features_kerne
         lv[k] = P[g * 3 + 2];
         k++;
       }
-    ngp_s = k;
+    *ngp_sh = k;
   }
   __syncthreads();
-  const int ngp = ngp_s;
+  const int ngp = *ngp_sh;
   double nvp = 0, stot = 0;
   for (int k = t; k < ngp; k += PRAD_FEAT_THREADS) {
     nvp += pi[k];
@@ -421,5 +444,13 @@ __global__ void __launch_bounds__(PRAD_FEAT_THREADS) ngtdm_matrix_features_kerne
     out[4] = stot != 0 ? strength / stot : 0.0;                                   // :284-285
   }
 }
+#ifndef PRAD_DEVICE_FUNCTIONS_ONLY
+__global__ void __launch_bounds__(PRAD_FEAT_THREADS) ngtdm_matrix_features_kernel(const double *__restrict__ P, int Ng,
+                                                                                  double *__restrict__ out) {
+  extern __shared__ double ns[];
+  __shared__ int ngp_s;
+  ngtdm_features_block(P, Ng, out, ns, &ngp_s);
+}
+#endif
 
 }  // namespace prad

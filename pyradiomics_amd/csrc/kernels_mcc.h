@@ -12,7 +12,10 @@
 // builds the window's counts per angle in LDS (as kernels_voxel.h pass A) and runs the same routine.
 #pragma once
 #include "prad_runtime.h"
+#include "wave_reduce.h"
+#ifndef PRAD_DEVICE_FUNCTIONS_ONLY      // (kernels_batch_features.h takes the segment-mode device functions alone)
 #include "kernels_voxel.h"
+#endif
 
 namespace prad {
 
@@ -331,14 +334,14 @@ __device__ double block_mcc(Acc C, int Ng, double tot, MccScratch S, int nmax, i
   return sqrt(fmax(second, 0.0));
 }
 
-// segment mode: counts [Ng][Ng][Na] float64 (raw, reference layout) -> out[a] = MCC of angle a (NaN: no pair)
-__global__ void __launch_bounds__(PRAD_MCC_BT) glcm_matrix_mcc_kernel(const double *__restrict__ counts, int Ng, int Na,
-                                                                      int symmetric, int nmax, int staged,
-                                                                      double *__restrict__ out, int *__restrict__ too_many) {
-  extern __shared__ double mcc_lds[];
-  __shared__ double red[PRAD_MCC_BT / 64];
-  __shared__ int shn;
-  const int a = blockIdx.x, tid = threadIdx.x;
+// segment mode: counts [Ng][Ng][Na] float64 (raw, reference layout) -> *out = MCC of angle a (NaN: no pair).  One workgroup of
+// PRAD_MCC_BT threads; mcc_lds: mcc_scratch_bytes(Ng, nmax), rounded up to 16, plus Ng * Ng doubles when staged; red:
+// PRAD_MCC_BT / 64 doubles of LDS, shn: one int.  The single-call kernel below and batch_mcc_kernel
+// (kernels_batch_features.h) call the same code on a matrix: same bits.
+__device__ __forceinline__ void glcm_mcc_block(const double *__restrict__ counts, int Ng, int Na, int a, int symmetric, int nmax,
+                                               int staged, double *__restrict__ out, int *__restrict__ too_many,
+                                               double *mcc_lds, double *red, int *shn) {
+  const int tid = threadIdx.x;
   auto G = [&](int i, int j) -> double {
     const double v = counts[((size_t)i * Ng + j) * Na + a];
     return symmetric ? v + counts[((size_t)j * Ng + i) * Na + a] : v;
@@ -356,14 +359,26 @@ __global__ void __launch_bounds__(PRAD_MCC_BT) glcm_matrix_mcc_kernel(const doub
     }
     tot = block_sum_f64(tot, red);
     auto C = [&](int i, int j) -> double { return Cs[i * Ng + j]; };
-    if (tot > 0) v = block_mcc(C, Ng, tot, mcc_scratch(mcc_lds, Ng, nmax), nmax, too_many, red, &shn);
+    if (tot > 0) v = block_mcc(C, Ng, tot, mcc_scratch(mcc_lds, Ng, nmax), nmax, too_many, red, shn);
   } else {
     double tot = 0;
     for (int e = tid; e < Ng * Ng; e += PRAD_MCC_BT) tot += G(e / Ng, e % Ng);
     tot = block_sum_f64(tot, red);
-    if (tot > 0) v = block_mcc(G, Ng, tot, mcc_scratch(mcc_lds, Ng, nmax), nmax, too_many, red, &shn);
+    if (tot > 0) v = block_mcc(G, Ng, tot, mcc_scratch(mcc_lds, Ng, nmax), nmax, too_many, red, shn);
   }
-  if (tid == 0) out[a] = v;
+  if (tid == 0) *out = v;
+}
+
+#ifndef PRAD_DEVICE_FUNCTIONS_ONLY
+// out: [Na]; one workgroup per angle
+__global__ void __launch_bounds__(PRAD_MCC_BT) glcm_matrix_mcc_kernel(const double *__restrict__ counts, int Ng, int Na,
+                                                                      int symmetric, int nmax, int staged,
+                                                                      double *__restrict__ out, int *__restrict__ too_many) {
+  extern __shared__ double mcc_lds[];
+  __shared__ double red[PRAD_MCC_BT / 64];
+  __shared__ int shn;
+  const int a = blockIdx.x;
+  glcm_mcc_block(counts, Ng, Na, a, symmetric, nmax, staged, out + a, too_many, mcc_lds, red, &shn);
 }
 
 #define PRAD_MCC_WAVES 2
@@ -438,5 +453,7 @@ __global__ void __launch_bounds__(64 * PRAD_MCC_WAVES) voxel_glcm_mcc_kernel(
     if (lane == 0) out[v] = n_angles ? acc / (double)n_angles : __builtin_nan("");
   }
 }
+
+#endif   // PRAD_DEVICE_FUNCTIONS_ONLY
 
 }  // namespace prad

@@ -17,6 +17,7 @@
 // angle, glcm.py:665-707) is not evaluated here; callers fall back to the matrix path for it.
 #pragma once
 #include "prad_runtime.h"
+#include "wave_reduce.h"
 #include "kernels_sweep.h"
 
 namespace prad {
@@ -33,22 +34,6 @@ struct VoxAngles {
   int na;
   signed char o[PRAD_VOX_MAX_ANGLES][4];
 };
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 #define PRAD_VOX_WAVES 4  // waves (= centre voxels in flight) per workgroup
 

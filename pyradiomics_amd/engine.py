@@ -807,6 +807,11 @@ def _one_voxel_glszm(level, masked, Ng, compact, dev):
     return (P, np.ones(1, dtype=np.intc)) if masked else (P[:, :0], np.zeros(0, dtype=np.intc))
 
 
+class _GlszmBatch(list):
+    """the result list of glszm_batch; `flat` describes the device buffers the native route's results are views of"""
+    flat = None
+
+
 def glszm_batch_zones(levels, masks, sizes, Ng):
     """the zone lists of B small ROIs from the labelling launch alone -> (list of B int32 device tensors [nzones, 2] of
     (level, size) in raster order of each zone's first voxel -- views into one buffer --, summary int32 numpy [B, 3]: zones,
@@ -853,6 +858,10 @@ def glszm_batch(levels, masks, sizes, Ng, compact=True):
             P = flat[int(out_off[i]):int(out_off[i + 1])].view(Ng, int(cols[i]))
             results[b] = (P[:, :int(k[i])], sizes_host[s_off[i]:s_off[i + 1]].copy()) if compact else P
             status[b] = int(st[i])
+    results = _GlszmBatch(results)
+    if len(covered):      # (batch_features_per_angle evaluates the formulas on these buffers, in place)
+        results.flat = {"P": flat, "covered": covered, "out_off": out_off, "cols": cols, "compact": bool(compact),
+                        "sizes": sizes_dev if compact else None, "s_off": s_off, "k": k}
     rest = sorted(set(range(B)) - set(int(b) for b in covered))
     for b in rest:
         shape = tuple(int(s) for s in sizes[b])
@@ -869,6 +878,162 @@ def glszm_batch(levels, masks, sizes, Ng, compact=True):
             status[b] = _lib.PRAD_INDEX_ERROR
     _cm._set_batch_route("looped" if not len(covered) else ("mixed" if rest else "batch"))
     return results, status
+
+
+# ---- feature formulas of many small ROIs (prad_batch_features_dev, csrc/kernels_batch_features.h) ----------------------------
+FEATURE_FAMILIES = ("glcm", "glrlm", "gldm", "ngtdm", "glszm")       # bit f of the C `families` argument, row f of its offsets
+_FEATURE_ROW = {"glcm": 24, "glrlm": 16, "gldm": 16, "ngtdm": 5, "glszm": 16}
+
+
+def _flat_offsets(tensors):
+    """element offsets of the tensors in the ONE storage they all are contiguous views of (-> base pointer, int64 offsets),
+    or None when they are separate tensors (the looped routes' results)"""
+    if not tensors:
+        return None
+    base = tensors[0].untyped_storage().data_ptr()
+    if any((not t.is_cuda) or t.dtype != torch.float64 or not t.is_contiguous() or t.untyped_storage().data_ptr() != base
+           for t in tensors):
+        return None
+    return base, np.array([t.storage_offset() for t in tensors], dtype=np.int64)
+
+
+def _single_glszm_features(item, Ng):
+    """the single call on one glszm_batch result (compact pair or dense tensor); a ROI without zones is an empty matrix"""
+    P, jv = item if isinstance(item, tuple) else (item, np.arange(1, item.shape[1] + 1))
+    if P.shape[1] == 0:
+        return np.full((1, 16), np.nan), np.ones(1, dtype=bool)
+    return zone_matrix_features(P, jv)
+
+
+def _single_features(f, M, symmetric, mcc):
+    """family f of one ROI through the single calls -> (float64 [rows, nfeat], bool [rows])"""
+    if f == "ngtdm":
+        return ngtdm_features(M).reshape(1, 5).copy(), np.array([not bool((M[:, 0] > 0).any().item())])
+    if f == "glcm":
+        Na = int(M.shape[2])
+        vals, empty = (glcm_features(M, symmetric) if Na else (np.empty((0, 23)), np.zeros(0, dtype=bool)))
+        last = glcm_mcc(M, symmetric) if (mcc and Na) else np.full(Na, np.nan)
+        return np.concatenate([vals, last.reshape(Na, 1)], axis=1), empty
+    if M.dim() == 3 and M.shape[2] == 0:
+        return np.empty((0, 16)), np.zeros(0, dtype=bool)
+    return zone_matrix_features(M, np.arange(1, M.shape[1] + 1))
+
+
+def batch_features_per_angle(mats, Ng, glszm=None, symmetric=True, mcc=True):
+    """The feature formulas on the matrices of a batch: `mats` is the dict of texture_matrices_batch, `glszm` the result list of
+    glszm_batch (compact or dense) or None.  -> {family: [B pairs (float64 numpy [rows, nfeat], bool numpy [rows] = matrix
+    empty)]}, rows = angles for glcm (24 columns: the 23 of glcm_features, then glcm_mcc; NaN without `mcc`) and glrlm (16),
+    one row for gldm (16), ngtdm (5; its flag says that no level occurs) and glszm (16): the arrays the single calls return,
+    bit for bit.  Matrices that are views of the flat buffers of the batched calls are evaluated in two launches
+    (prad_batch_features_dev: Ng <= 64); anything else goes through the single calls, one by one."""
+    lib = _lib.load()
+    Ng = int(Ng)
+    fams = [f for f in FEATURE_FAMILIES[:4] if f in mats]
+    B = len(mats[fams[0]]) if fams else len(glszm or [])
+    if any(len(mats[f]) != B for f in fams) or (glszm is not None and len(glszm) != B):
+        raise ValueError("the families differ in their number of ROIs")
+    out = {f: [None] * B for f in fams}
+    if glszm is not None:
+        out["glszm"] = [None] * B
+    views = {f: _flat_offsets(list(mats[f])) for f in fams} if Ng <= 64 else {f: None for f in fams}
+    zflat = getattr(glszm, "flat", None) if (glszm is not None and Ng <= 64) else None
+    native = [f for f in fams if views[f] is not None]
+    if (native or zflat is not None) and B:
+        dev = (mats[native[0]][0] if native else zflat["P"]).device
+        lib.prad_set_device(dev.index or 0)
+        # the angle counts and the longest axis as the matrices' shapes give them (the C call takes them as prad_batch_plan does)
+        Na = np.zeros((2, B), dtype=np.intc)
+        sizes = np.ones((B, 3), dtype=np.intc)
+        for b in range(B):
+            if "glcm" in native:
+                Na[0, b] = mats["glcm"][b].shape[2]
+            elif "gldm" in native:
+                Na[0, b] = (mats["gldm"][b].shape[1] - 1) // 4
+            if "glrlm" in native:
+                sizes[b, 0], Na[1, b] = mats["glrlm"][b].shape[1], mats["glrlm"][b].shape[2]
+        offsets = np.zeros((4, B + 1), dtype=np.int64)
+        ptrs = [None] * 4
+        bits = 0
+        for f in native:
+            i = FEATURE_FAMILIES.index(f)
+            ptrs[i], offsets[i, :B] = C.c_void_p(views[f][0]), views[f][1]
+            bits |= 1 << i
+        cols = np.zeros(B, dtype=np.intc)
+        zoff, soff = np.zeros(B, dtype=np.int64), np.full(B, -1, dtype=np.int64)
+        zptr = sptr = None
+        if zflat is not None:
+            bits |= 16
+            cov = zflat["covered"]
+            cols[cov] = zflat["cols"]
+            zoff[cov] = zflat["out_off"][:-1]
+            zptr = C.c_void_p(zflat["P"].data_ptr())
+            if zflat["compact"]:
+                soff[cov] = np.where(zflat["k"] > 0, zflat["s_off"][:-1], -1)      # (no zone: one zero column, no size list)
+                sptr = C.c_void_p(zflat["sizes"].data_ptr())
+        lay = np.zeros((2, 5, B + 1), dtype=np.int64)
+        nrec = np.zeros(3, dtype=np.int64)
+        rc = lib.prad_batch_features_plan(_iptr(sizes), B, Ng, bits, _iptr(Na), _iptr(cols), _lp(lay), _lp(nrec))
+        _lib.raise_for(rc, "batched features plan")
+        nout, nrows = int(lay[0, 4, B]), int(lay[1, 4, B])
+        # values and flags in one device block: one read-back
+        block = torch.empty(nout + (nrows + 1) // 2 + 1, dtype=torch.float64, device=dev)
+        flags = block[nout:].view(torch.int32)
+        rc = lib.prad_batch_features_dev(_iptr(sizes), B, Ng, bits, _iptr(Na), _iptr(cols), ptrs[0], ptrs[1], ptrs[2], ptrs[3],
+                                         _lp(offsets), zptr, _lp(zoff), sptr, _lp(soff), 1 if symmetric else 0, 1 if mcc else 0,
+                                         C.c_void_p(block.data_ptr()), C.c_void_p(flags.data_ptr()), _stream_ptr())
+        _lib.raise_for(rc, "batched features")
+        host = block.cpu().numpy()
+        vals, empty = host[:nout], host[nout:].view(np.int32)[:nrows] != 0
+        for f in native + (["glszm"] if zflat is not None else []):
+            i, w = FEATURE_FAMILIES.index(f), _FEATURE_ROW[f]
+            for b in (range(B) if f != "glszm" else zflat["covered"]):
+                e0, e1, r0, r1 = int(lay[0, i, b]), int(lay[0, i, b + 1]), int(lay[1, i, b]), int(lay[1, i, b + 1])
+                out[f][b] = (vals[e0:e1].reshape(r1 - r0, w).copy(), empty[r0:r1].copy())
+    for f in out:      # whatever the native call did not take
+        for b in range(B):
+            if out[f][b] is None:
+                out[f][b] = _single_glszm_features(glszm[b], Ng) if f == "glszm" else _single_features(f, mats[f][b], symmetric, mcc)
+    return out
+
+
+def texture_features_batch(levels, masks, sizes, Ng, classes=("glcm", "glrlm", "glszm", "gldm", "ngtdm"),
+                           distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True):
+    """The texture FEATURES of B small ROIs (segment mode, 3-D; inputs as texture_matrices_batch): texture_matrices_batch,
+    glszm_batch(compact=True), the formulas of all matrices in two launches (batch_features_per_angle) and, per ROI, the mean
+    over the angles the reference keeps (cmatrices._angle_mean).  -> ({class: float64 numpy [B, nfeat]}, status [B]): glcm 24
+    columns (cmatrices.VOXEL_GLCM_FEATURES, then MCC -- NaN without `mcc`), glrlm / gldm / glszm 16 (the shared zone numbering),
+    ngtdm 5.  status 0: a masked level outside [1, Ng]; that ROI's rows are NaN, the others are not affected.  weightingNorm is
+    not offered.  Outside the native domain (Ng > 64, boxes above the batch caps) the single calls are looped and give the same
+    values; last_batch_route() says "batch", "mixed" or "looped"."""
+    lib, levels, masks, sizes = _batch_inputs(levels, masks, sizes)
+    classes = tuple(classes)
+    unknown = [c for c in classes if c not in FEATURE_FAMILIES]
+    if unknown or not classes:
+        raise ValueError("classes must be a non-empty subset of %s" % (FEATURE_FAMILIES,))
+    B = int(sizes.shape[0])
+    fams = tuple(f for f in FEATURE_FAMILIES[:4] if f in classes)
+    status = np.ones(B, dtype=np.int64)
+    routes = []
+    mats, zones = {}, None
+    if fams:
+        mats, st = texture_matrices_batch(levels, masks, sizes, Ng, fams, distances, gldm_a)
+        routes.append(last_batch_route())
+        status &= np.asarray(st, dtype=np.int64) == _lib.PRAD_OK
+    if "glszm" in classes:
+        zones, st = glszm_batch(levels, masks, sizes, Ng, compact=True)
+        routes.append(last_batch_route())
+        status &= np.asarray(st, dtype=np.int64) == _lib.PRAD_OK
+    per = batch_features_per_angle(mats, Ng, zones, symmetricalGLCM, mcc)
+    table = {}
+    for f in classes:
+        rows = np.full((B, _FEATURE_ROW[f]), np.nan)
+        for b in range(B):
+            if status[b]:
+                vals, empty = per[f][b]
+                rows[b] = vals[0] if f == "ngtdm" else _cm._angle_mean(vals, empty)
+        table[f] = rows
+    _cm._set_batch_route(routes[0] if all(r == routes[0] for r in routes) else "mixed")
+    return table, status.tolist()
 
 
 NEIGH_GLDM, NEIGH_NGTDM = 0, 1
