@@ -591,6 +591,45 @@ int prad_batch_features_dev(const int *sizes, int B, int Ng, int families, const
                             const int *glszm_sizes, const long long *glszm_sizes_offsets, int symmetric, int want_mcc,
                             double *out, int *empty, void *stream);
 
+/* ---- first-order statistics and discretisation of many small ROIs (csrc/kernels_batch_firstorder.h) --------------------
+ * The front end of the batched route: raw intensity boxes in, the statistics of prad_firstorder_dev and the levels and level
+ * counts of prad_digitize_counts_dev out, one launch each for the whole batch, one workgroup per ROI.  The batch layout is that
+ * of the calls above, in the image's own dtype (codes of prad_digitize_dev: 0 float32, 1 float64, 2 int32, 3 int16): ROI b is
+ * the box [size[b][0]][size[b][1]][size[b][2]] at ELEMENT off[b] of `image` (DEVICE), its uint8 mask at the same element of
+ * `mask` (DEVICE); sizes ([B][3]) and off are HOST arrays.
+ * prad_batch_firstorder_max_roi(dtype): the key capacity, i.e. the most ROI voxels (mask != 0) a workgroup sorts in LDS: 32768
+ *   for the 4-byte keys of float32 / int32 / int16, 16384 for float64 (128 KiB of keys); PRAD_E_ARG for another dtype.
+ * prad_batch_firstorder_plan (host only, needs no device): *lds_bytes = the dynamic LDS the launch asks for -- 64 bytes + one
+ *   key per slot, slots = the next power of two >= min(largest box, capacity), so a batch of 16^3 boxes runs many workgroups
+ *   per CU; inside int [B] = 1 where the box itself holds no more voxels than the capacity (the ROI is then certainly served),
+ *   0 where that depends on the mask.  PRAD_E_ARG for a bad dtype, B < 1 or a size < 1; PRAD_E_UNSUPPORTED -- outputs filled all
+ *   the same -- when prad_batch_firstorder_dev would decline: a box above 2^31 - 1 voxels.
+ * prad_batch_firstorder_dev: table DEVICE float64 [B][16]: the PRAD_FO_COUNT statistics in the enum's order, then a verdict:
+ *   0 fine; 1 empty ROI (prad_firstorder_dev's PRAD_E_ARG); 2 a non-finite ROI value; 8 more ROI voxels than the capacity.
+ *   The 15 statistics are NaN unless the verdict is 0; verdicts 2 and 8: give that ROI to prad_firstorder_dev.  Minimum, Maximum,
+ *   the percentiles and Median are those of prad_firstorder_dev bit for bit; the sums run over the ROI's SORTED values (thread t
+ *   of 256 adds elements t, t + 256, ..., then 6 shuffle steps and 3 additions), Mean is one float64 division, MAD / m2 / m3 / m4
+ *   are taken about that Mean and rMAD about the float64 mean of the band P10 <= x <= P90, so a ROI's row depends on its values
+ *   alone -- not on the other ROIs, its place in the batch or the timing of the launch.  Boxes of up to 2^31 - 1 voxels are legal.
+ * prad_batch_digitize_dev: edges DEVICE float64, the ascending edges of ROI b (np.digitize's `bins`, built on the host by
+ *   getBinEdges from the ROI's Minimum / Maximum) at edge_off[b] .. edge_off[b + 1] - 1 (edge_off HOST int64 [B + 1]).  levels
+ *   DEVICE int32, the batch layout: levels[i] = number of edges <= (double)image[i] where mask != 0 (the comparisons of
+ *   prad_digitize_dev), 0 elsewhere; every element of every served box is written.  counts DEVICE int64: the ROI voxels per level
+ *   0 .. nedges of ROI b at count_off[b] (HOST int64 [B]); top DEVICE int [B]: the largest level.  count_off[b] < 0: the ROI is not
+ *   served (nothing of it is written: the caller bins it with prad_digitize_counts_dev).  A ROI without edges gets level 0
+ *   throughout.  Covered: at most prad_batch_digitize_max_edges() = 8192 edges per served ROI (edges and counters share the LDS:
+ *   12 bytes per edge, 96 KiB at the cap); beyond it PRAD_E_UNSUPPORTED before anything is launched or written.
+ * Both enqueue one copy and one launch on `stream` and synchronise it; kernel family "batch_firstorder" (prad_last_kernel_ms);
+ * prad_last_path "batch", prad_last_variant "batch-firstorder-lds" / "batch-digitize-lds". */
+int prad_batch_firstorder_max_roi(int dtype);
+int prad_batch_firstorder_plan(const int *sizes, int B, int dtype, long long *lds_bytes, int *inside);
+int prad_batch_firstorder_dev(const void *image, int dtype, const uint8_t *mask, const int *sizes, const long long *off, int B,
+                              double voxelArrayShift, double *table, void *stream);
+int prad_batch_digitize_max_edges(void);
+int prad_batch_digitize_dev(const void *image, int dtype, const uint8_t *mask, const int *sizes, const long long *off, int B,
+                            const double *edges, const long long *edge_off, int32_t *levels, long long *counts,
+                            const long long *count_off, int *top, void *stream);
+
 /* ---- filter stack in front of the matrices (radiomics/imageoperations.py:756-970) ---------------------------
  * The arithmetic of both filters lives in third-party wheels (PyWavelets, SimpleITK/ITK) that are not part of
  * the reference tree; these entry points implement their published algorithms (see oracle/filters_oracle.py):

@@ -521,6 +521,65 @@ def calculate_features_batch(images, masks, Ng, classes=("glcm", "glrlm", "glszm
             for cls in table}
 
 
+def batch_firstorder_plan(sizes, dtype):
+    """Host-side plan of the batched first-order launch (prad_batch_firstorder_plan; needs no device).  sizes: int [B, 3]; dtype:
+    the image dtype code (0 float32, 1 float64, 2 int32, 3 int16).  -> (covered, lds_bytes, inside bool [B]): the launch takes the
+    batch; the dynamic LDS it asks for; per ROI whether the box is certainly within the key capacity."""
+    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
+    B = int(sizes.shape[0])
+    lds = C.c_longlong(0)
+    inside = np.zeros(max(B, 1), dtype=np.intc)
+    rc = _lib.load().prad_batch_firstorder_plan(_iptr(sizes), B, int(dtype), C.byref(lds), _iptr(inside))
+    if rc != _lib.PRAD_E_UNSUPPORTED:
+        _lib.raise_for(rc, "batch firstorder plan")
+    return rc == _lib.PRAD_OK, int(lds.value), inside[:B].astype(bool)
+
+
+def _upload_roi_batch(images, masks, what):
+    """lists of host arrays (raw intensity boxes, masks) -> (flat image tensor, flat uint8 mask tensor, sizes) in ONE upload each"""
+    if len(images) != len(masks):
+        raise ValueError("images and masks differ in number")
+    imgs = [np.ascontiguousarray(np.asarray(i)) for i in images]
+    msks = [np.ascontiguousarray(np.asarray(m)) for m in masks]
+    if not imgs or any(i.ndim != 3 or i.shape != m.shape for i, m in zip(imgs, msks)):
+        raise ValueError("the batched %s take a non-empty list of 3-D ROIs with masks of the same shape" % what)
+    if _lib.load().prad_device_count() < 1:
+        raise RuntimeError("no HIP device: the batched %s are evaluated on the device" % what)
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    dt = imgs[0].dtype if (imgs[0].dtype in (np.float32, np.float64, np.int32, np.int16)
+                           and all(i.dtype == imgs[0].dtype for i in imgs)) else np.dtype(np.float64)
+    sizes = np.array([i.shape for i in imgs], dtype=np.intc).reshape(-1, 3)
+    flat_i = torch.from_numpy(np.concatenate([i.ravel().astype(dt, copy=False) for i in imgs])).to(dev)
+    flat_m = torch.from_numpy(np.concatenate([(m.ravel() != 0).view(np.uint8) for m in msks])).to(dev)
+    return flat_i, flat_m, sizes
+
+
+def calculate_firstorder_batch(images, masks, voxelArrayShift=0.0, voxelVolume=1.0, **binning):
+    """The first-order features of B small 3-D ROIs (lists of host arrays: raw intensities, masks): one upload, then
+    engine.roi_features_batch with the first-order class alone -- two launches and two read-backs for the whole batch.  binning:
+    binWidth (default 25) or binCount, for Entropy and Uniformity.  -> {"firstorder": {feature name: float64 [B]}}; an empty ROI
+    has NaN everywhere.  Needs a device (RuntimeError without one); last_batch_route() tells which route ran."""
+    return calculate_roi_features_batch(images, masks, classes=("firstorder",), voxelArrayShift=voxelArrayShift,
+                                        voxelVolume=voxelVolume, **binning)
+
+
+def calculate_roi_features_batch(images, masks, classes=("firstorder", "glcm", "glrlm", "glszm", "gldm", "ngtdm"), binWidth=None,
+                                 binCount=None, voxelArrayShift=0.0, voxelVolume=1.0, distances=(1,), gldm_a=0,
+                                 symmetricalGLCM=True, mcc=True):
+    """The features of all six classes of B small 3-D ROIs from raw intensity boxes and masks (lists of host arrays): one upload,
+    then engine.roi_features_batch.  -> {class: {feature name: float64 [B]}} (FIRSTORDER_FEATURES / batch_feature_names); an
+    empty ROI has NaN everywhere, the others are not affected.  Needs a device (RuntimeError without one); last_batch_route()
+    tells which route ran."""
+    flat_i, flat_m, sizes = _upload_roi_batch(images, masks, "ROI features")
+    engine = _engine()
+    table, _ = engine.roi_features_batch(flat_i, flat_m, sizes, tuple(classes), binWidth, binCount, float(voxelArrayShift), voxelVolume,
+                                         [int(d) for d in np.asarray(distances).ravel()], int(gldm_a), bool(symmetricalGLCM),
+                                         bool(mcc))
+    names = {cls: (FIRSTORDER_FEATURES if cls == "firstorder" else batch_feature_names(cls)) for cls in table}
+    return {cls: {name: table[cls][:, i].copy() for i, name in enumerate(names[cls]) if name} for cls in table}
+
+
 # ---- fused voxel-based features of the other four texture classes (prad_voxel_texture_features_dev) ---------
 _ZONE_LIKE = {
     "glrlm": (3, ["ShortRunEmphasis", "LongRunEmphasis", "GrayLevelNonUniformity", "GrayLevelNonUniformityNormalized",

@@ -369,6 +369,7 @@ __device__ __forceinline__ double fo_lerp_np(double a, double b, double t) {
   return t >= 0.5 ? b - d * (1 - t) : a + d * t;
 }
 
+#ifndef PRAD_DEVICE_FUNCTIONS_ONLY      // (kernels_batch_firstorder.h takes the device functions alone: the glue kernels are no templates)
 // after fo_sums_kernel: block partials -> sums, extremes, count, mean, quantile ranks, histogram scale
 __global__ void fo_glue_sums_kernel(const double *__restrict__ partial, int blocks, long long expect_m, FoDev *st) {
 #pragma clang fp contract(off)
@@ -645,6 +646,7 @@ __global__ void fo_glue_final_kernel(const double *__restrict__ partial, int blo
   out[13] = st->cen[2] / dm;           // M3
   out[14] = st->cen[3] / dm;           // M4
 }
+#endif  // PRAD_DEVICE_FUNCTIONS_ONLY
 
 // ---- voxel mode (firstorder.py:37-118): one wave per centre voxel ------------------------------------------------
 // The reference gathers, for every centre, the intensities at centre + kernelOffsets from a NaN-padded copy of the

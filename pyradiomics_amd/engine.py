@@ -657,8 +657,14 @@ def last_batch_route() -> str:
     return _cm.last_batch_route()
 
 
-def _batch_inputs(levels, masks, sizes):
-    """-> (flat int32 levels, flat uint8 mask, sizes int32 [B, 3]) on one device"""
+def _batch_inputs(levels, masks, sizes, raw=False):
+    """-> (flat int32 levels, flat uint8 mask, sizes int32 [B, 3]) on one device.  raw: intensity images instead of levels; they
+    keep their dtype where it is one of the four the kernels read (float32, float64, int32, int16; anything else, or a list of
+    mixed dtypes, becomes float64)"""
+    def image_dtype(dts):
+        if not raw:
+            return torch.int32
+        return dts[0] if dts[0] in _DTYPE_CODES and all(d == dts[0] for d in dts) else torch.float64
     if isinstance(levels, (list, tuple)):
         if len(levels) != len(masks):
             raise ValueError("levels and masks differ in number")
@@ -667,13 +673,24 @@ def _batch_inputs(levels, masks, sizes):
         sizes = np.array([tuple(l.shape) for l in levels], dtype=np.intc).reshape(-1, 3)
         if not len(levels):
             raise ValueError("empty batch")
-        levels = torch.cat([l.reshape(-1).to(torch.int32) for l in levels])
+        dt = image_dtype([l.dtype for l in levels])
+        levels = torch.cat([l.reshape(-1).to(dt) for l in levels])
         masks = torch.cat([(m if m.dtype in (torch.bool, torch.uint8) else m != 0).reshape(-1).view(torch.uint8) for m in masks])
     elif sizes is None:
         raise ValueError("flat level / mask tensors need `sizes`")
     sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
     levels, masks = levels.reshape(-1), masks.reshape(-1)
-    lib, levels, masks, _ = _prep(levels, masks)
+    if raw:
+        if not levels.is_cuda or not masks.is_cuda:
+            raise ValueError("engine.* expects CUDA/HIP tensors; use pyradiomics_amd.cmatrices for numpy input")
+        if levels.shape != masks.shape:
+            raise ValueError("Dimensions of image and mask do not match.")
+        levels, masks = levels.to(image_dtype([levels.dtype])).contiguous(), _mask_u8(masks)
+        lib = _lib.load()
+        _lib.raise_for(lib.prad_set_device(levels.device.index if levels.device.index is not None else torch.cuda.current_device()),
+                       "set_device")
+    else:
+        lib, levels, masks, _ = _prep(levels, masks)
     if int(sizes.astype(np.int64).prod(1).sum()) != levels.numel():
         raise ValueError("sizes describe %d voxels, the buffers hold %d" % (int(sizes.astype(np.int64).prod(1).sum()), levels.numel()))
     return lib, levels, masks, sizes
@@ -1033,6 +1050,183 @@ def texture_features_batch(levels, masks, sizes, Ng, classes=("glcm", "glrlm", "
                 rows[b] = vals[0] if f == "ngtdm" else _cm._angle_mean(vals, empty)
         table[f] = rows
     _cm._set_batch_route(routes[0] if all(r == routes[0] for r in routes) else "mixed")
+    return table, status.tolist()
+
+
+# ---- first-order statistics and discretisation of many small ROIs (prad_batch_firstorder_dev / prad_batch_digitize_dev, -------
+# ---- csrc/kernels_batch_firstorder.h): raw intensity boxes in, the table of all six feature classes out ------------------------
+ROI_FEATURE_CLASSES = ("firstorder", "glcm", "glrlm", "glszm", "gldm", "ngtdm")
+_NP_DTYPES = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32, torch.int16: np.int16}
+
+
+def batch_firstorder_max_roi(dtype) -> int:
+    """most ROI voxels (mask != 0) per ROI the batched first-order launch sorts in LDS: 32768, or 16384 for float64"""
+    code = _DTYPE_CODES[dtype] if dtype in _DTYPE_CODES else int(dtype)
+    return int(_lib.load().prad_batch_firstorder_max_roi(code))
+
+
+def batch_digitize_max_edges() -> int:
+    """most bin edges per ROI the batched discretisation stages in LDS (PRAD_BATCH_DIGITIZE_MAX_EDGES)"""
+    return int(_lib.load().prad_batch_digitize_max_edges())
+
+
+def _roi_offsets(sizes):
+    nvox = sizes.astype(np.int64).prod(1)
+    off = np.zeros(len(nvox), dtype=np.int64)
+    off[1:] = np.cumsum(nvox)[:-1]
+    return off, nvox
+
+
+def _roi_view(flat, sizes, off, nvox, b):
+    return flat[int(off[b]):int(off[b] + nvox[b])].view(tuple(int(s) for s in sizes[b]))
+
+
+def _joined_route(routes):
+    return routes[0] if all(r == routes[0] for r in routes) else "mixed"
+
+
+def firstorder_batch(images, masks, sizes=None, voxelArrayShift=0.0):
+    """The first-order statistics of B small ROIs in ONE launch (segment mode, 3-D).  images / masks: lists of 3-D device
+    tensors of one dtype (float32, float64, int32, int16; anything else is widened to float64), or flat device tensors holding
+    the boxes back to back plus `sizes` (int [B, 3]); masks bool or integer, non-zero = ROI.  -> (float64 numpy [B, 15] in the
+    order of FIRSTORDER_FIELDS, status int64 [B] = the launch's verdict per ROI: 0 fine; 1 empty ROI, its row is NaN; 2 a
+    non-finite ROI value and 8 more ROI voxels than batch_firstorder_max_roi(): that ROI's row comes from firstorder_stats).
+    last_batch_route() says "batch", "mixed" (some ROIs went through firstorder_stats) or "looped" (all did)."""
+    lib, images, masks, sizes = _batch_inputs(images, masks, sizes, raw=True)
+    B = int(sizes.shape[0])
+    off, nvox = _roi_offsets(sizes)
+    table = torch.empty((B, 16), dtype=torch.float64, device=images.device)
+    rc = lib.prad_batch_firstorder_dev(C.c_void_p(images.data_ptr()), _DTYPE_CODES[images.dtype], C.c_void_p(masks.data_ptr()),
+                                       _iptr(sizes), _lp(off), B, float(voxelArrayShift), C.c_void_p(table.data_ptr()),
+                                       _stream_ptr())
+    if rc == _lib.PRAD_E_UNSUPPORTED:          # nothing was launched: every ROI takes the single call
+        tab = np.full((B, 16), np.nan)
+        tab[:, 15] = 8
+    else:
+        _lib.raise_for(rc, "batched first-order statistics")
+        tab = table.cpu().numpy()              # the batch's first read-back
+    status = tab[:, 15].astype(np.int64)
+    rows = np.ascontiguousarray(tab[:, :15])
+    rest = np.flatnonzero((status == 2) | (status == 8))
+    for b in rest:
+        st = firstorder_stats(_roi_view(images, sizes, off, nvox, b), _roi_view(masks, sizes, off, nvox, b), voxelArrayShift)
+        rows[b] = [st[f] for f in FIRSTORDER_FIELDS]
+    _cm._set_batch_route("batch" if not len(rest) else ("looped" if len(rest) == B else "mixed"))
+    return rows, status
+
+
+def bin_batch(images, masks, sizes=None, stats=None, **binning):
+    """The discretisation of B small ROIs in ONE launch: every ROI gets its own bin edges -- imageoperations.getBinEdges on its
+    (Minimum, Maximum), as bin_image builds them; binWidth and binCount both work -- and is digitised against them by its own
+    workgroup.  Inputs as firstorder_batch; stats: the (rows, status) pair of firstorder_batch on the same batch (computed here
+    when None).  -> (flat int32 level tensor in the batch layout, Ng int64 [B], list of B float64 edge arrays, list of B int64
+    count arrays [Ng + 1]), ROI by ROI what bin_image(..., with_counts=True) returns.  An empty ROI has Ng 0, no edges, counts
+    [0] and levels 0.  ROIs whose statistics came from the single call (status 2 / 8) or with more than
+    batch_digitize_max_edges() edges go through bin_image; last_batch_route() says "batch", "mixed" or "looped"."""
+    from . import imageoperations
+    lib, images, masks, sizes = _batch_inputs(images, masks, sizes, raw=True)
+    B = int(sizes.shape[0])
+    off, nvox = _roi_offsets(sizes)
+    rows, status = firstorder_batch(images, masks, sizes) if stats is None else stats
+    rows, status = np.asarray(rows, dtype=np.float64).reshape(B, -1), np.asarray(status).reshape(B)
+    np_dtype = _NP_DTYPES[images.dtype]
+    cap = batch_digitize_max_edges()
+    edges = [np.zeros(0, dtype=np.float64)] * B
+    single = []
+    edge_off = np.zeros(B + 1, dtype=np.int64)
+    count_off = np.full(B, -1, dtype=np.int64)
+    ncounts = 0
+    i_min, i_max = FIRSTORDER_FIELDS.index("Minimum"), FIRSTORDER_FIELDS.index("Maximum")
+    for b in range(B):
+        ne = 0
+        if status[b] == 0:
+            e = np.asarray(imageoperations.getBinEdges(np.array([rows[b, i_min], rows[b, i_max]], dtype=np_dtype), **binning),
+                           dtype=np.float64)
+            if len(e) <= cap:
+                edges[b], ne = e, len(e)
+        if status[b] == 1 or ne:
+            count_off[b] = ncounts
+            ncounts += ne + 1
+        else:
+            single.append(b)
+        edge_off[b + 1] = edge_off[b] + ne
+    dev = images.device
+    levels = torch.empty(images.numel(), dtype=torch.int32, device=dev)
+    counts = [None] * B
+    Ng = np.zeros(B, dtype=np.int64)
+    if len(single) < B:
+        flat_edges = np.concatenate(edges) if edge_off[B] else np.zeros(1, dtype=np.float64)
+        d_edges = torch.from_numpy(flat_edges).to(dev)
+        back = torch.empty(ncounts + (B + 1) // 2, dtype=torch.int64, device=dev)      # [counts | top (int32)]: one read-back
+        top = back[ncounts:].view(torch.int32)
+        rc = lib.prad_batch_digitize_dev(C.c_void_p(images.data_ptr()), _DTYPE_CODES[images.dtype], C.c_void_p(masks.data_ptr()),
+                                         _iptr(sizes), _lp(off), B, C.c_void_p(d_edges.data_ptr()), _lp(edge_off),
+                                         C.c_void_p(levels.data_ptr()), C.c_void_p(back.data_ptr()), _lp(count_off),
+                                         C.c_void_p(top.data_ptr()), _stream_ptr())
+        _lib.raise_for(rc, "batched discretisation")
+        host = back.cpu().numpy()              # the batch's second read-back
+        tops = host[ncounts:].view(np.int32)
+        for b in range(B):
+            if count_off[b] >= 0:
+                Ng[b] = int(tops[b])
+                counts[b] = host[int(count_off[b]):int(count_off[b]) + int(Ng[b]) + 1].copy()
+    for b in single:
+        lv, ng, e, c = bin_image(_roi_view(images, sizes, off, nvox, b), _roi_view(masks, sizes, off, nvox, b), with_counts=True,
+                                 **binning)
+        levels[int(off[b]):int(off[b] + nvox[b])] = lv.reshape(-1)
+        Ng[b], edges[b], counts[b] = ng, e, c
+    _cm._set_batch_route("batch" if not single else ("looped" if len(single) == B else "mixed"))
+    return levels, Ng, edges, counts
+
+
+def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, binWidth=None, binCount=None, voxelArrayShift=0,
+                       voxelVolume=1.0, distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True):
+    """The feature table of B small ROIs from their raw intensity boxes and masks (inputs as firstorder_batch): firstorder_batch
+    and bin_batch -- two launches and two read-backs for the whole batch (binWidth, default 25, or binCount) -- then
+    texture_features_batch once per distinct Ng of the batch on the ROIs that share it.  -> ({class: float64 numpy [B, nfeat]},
+    status [B]): "firstorder" has the 19 columns of cmatrices.FIRSTORDER_FEATURES (firstorder.features_from_stats on the
+    statistics, the level counts and voxelVolume, a number or [B]); the texture classes the columns of texture_features_batch.
+    status 0: an empty ROI; its rows are NaN, the others are not affected.  last_batch_route() says "batch", "mixed" or
+    "looped" (texture_features_batch loops the single calls above 64 levels; MCC is not evaluated there -- its column is NaN
+    for a ROI with more than 64 levels, as without `mcc`)."""
+    from . import firstorder as _fo
+    lib, images, masks, sizes = _batch_inputs(images, masks, sizes, raw=True)
+    classes = tuple(classes)
+    if not classes or any(c not in ROI_FEATURE_CLASSES for c in classes):
+        raise ValueError("classes must be a non-empty subset of %s" % (ROI_FEATURE_CLASSES,))
+    binning = {"binCount": binCount} if binCount is not None else {"binWidth": 25 if binWidth is None else binWidth}
+    B = int(sizes.shape[0])
+    off, nvox = _roi_offsets(sizes)
+    routes = []
+    rows, verdict = firstorder_batch(images, masks, sizes, voxelArrayShift)
+    routes.append(last_batch_route())
+    levels, Ng, _, counts = bin_batch(images, masks, sizes, stats=(rows, verdict), **binning)
+    routes.append(last_batch_route())
+    status = (verdict != 1).astype(np.int64)
+    table = {}
+    if "firstorder" in classes:
+        vals = _fo.features_from_stats(rows, [c[1:] for c in counts], voxelVolume)
+        vals[status == 0] = np.nan
+        table["firstorder"] = vals
+    texture = tuple(c for c in classes if c != "firstorder")
+    if texture:
+        for c in texture:
+            table[c] = np.full((B, _FEATURE_ROW[c]), np.nan)
+        for ng in sorted(set(int(g) for g in Ng[status == 1])):
+            idx = np.flatnonzero((Ng == ng) & (status == 1))
+            if len(idx) == B:
+                sub_l, sub_m = levels, masks
+            else:
+                sub_l = torch.cat([levels[int(off[b]):int(off[b] + nvox[b])] for b in idx])
+                sub_m = torch.cat([masks[int(off[b]):int(off[b] + nvox[b])] for b in idx])
+            sub, st = texture_features_batch(sub_l, sub_m, sizes[idx], ng, texture, distances, gldm_a, symmetricalGLCM,
+                                             mcc and ng <= 64)       # (glcm_mcc declines more than 64 occurring levels)
+            routes.append(last_batch_route())
+            for c in texture:
+                table[c][idx] = sub[c]
+            status[idx] &= np.asarray(st, dtype=np.int64)
+    table = {c: table[c] for c in classes}
+    _cm._set_batch_route(_joined_route(routes))
     return table, status.tolist()
 
 

@@ -14,6 +14,51 @@ from .base import RadiomicsFeaturesBase, deprecated, _ENQUEUE_DEFAULT
 from .image import as_array
 
 
+STAT_FIELDS = ("Np", "Energy", "Minimum", "P10", "P25", "Median", "P75", "P90", "Maximum", "Mean", "MAD", "rMAD", "m2", "m3", "m4")
+
+
+def features_from_stats(st, counts, voxelVolume=1.0, names=None):
+    """The feature values of the class from the statistics of B ROIs, with the expressions of RadiomicsFirstOrder's getters.
+    st: {field: float or float64 [B]} (the fields of prad_firstorder_dev) or a float64 array [B, 15] / [15] in that order;
+    counts: per ROI the voxel counts of its grey levels (one array for a single ROI, a list of B arrays otherwise; zero counts
+    are dropped as the class drops absent levels); voxelVolume: the product of the spacings, a number or [B].
+    -> float64 [B, len(names)], names defaulting to cmatrices.FIRSTORDER_FEATURES (all 19)."""
+    from .cmatrices import FIRSTORDER_FEATURES
+    names = list(FIRSTORDER_FEATURES) if names is None else list(names)
+    if not isinstance(st, dict):
+        a = np.asarray(st, dtype=np.float64).reshape(-1, len(STAT_FIELDS))
+        st = {f: a[:, k] for k, f in enumerate(STAT_FIELDS)}
+    st = {k: np.atleast_1d(np.asarray(v, dtype=np.float64)) for k, v in st.items()}
+    B = len(st["Np"])
+    if B == 1 and len(counts) and np.ndim(counts[0]) == 0:
+        counts = [counts]
+    if len(counts) != B:
+        raise ValueError("statistics of %d ROIs, level counts of %d" % (B, len(counts)))
+    vol = np.broadcast_to(np.asarray(voxelVolume, dtype=np.float64), (B,))
+    entropy, uniformity = np.empty(B), np.empty(B)
+    for b in range(B):                                  # (ragged: every ROI has its own present levels)
+        c = np.asarray(counts[b])
+        p_i = c[c > 0].reshape((1, -1)).astype("float")
+        total = np.sum(p_i, 1, keepdims=True)
+        total[total == 0] = 1
+        p_i = p_i / total
+        entropy[b] = (-1.0 * np.sum(p_i * np.log2(p_i + np.spacing(1)), 1))[0]
+        uniformity[b] = np.nansum(p_i ** 2, 1)[0]
+    m2 = st["m2"].copy()
+    m2[m2 == 0] = 1                 # flat region: the moment ratios are 0 (firstorder.py:403-405, :441-443)
+    with np.errstate(all="ignore"):
+        rms = np.sqrt(st["Energy"] / st["Np"])
+        rms[st["Np"] == 0] = 0      # firstorder.py:360-362
+        table = {
+            "Energy": st["Energy"], "TotalEnergy": st["Energy"] * vol, "Entropy": entropy, "Minimum": st["Minimum"],
+            "10Percentile": st["P10"], "90Percentile": st["P90"], "Maximum": st["Maximum"], "Mean": st["Mean"],
+            "Median": st["Median"], "InterquartileRange": st["P75"] - st["P25"], "Range": st["Maximum"] - st["Minimum"],
+            "MeanAbsoluteDeviation": st["MAD"], "RobustMeanAbsoluteDeviation": st["rMAD"], "RootMeanSquared": rms,
+            "StandardDeviation": np.sqrt(st["m2"]), "Skewness": st["m3"] / m2 ** 1.5, "Kurtosis": st["m4"] / m2 ** 2.0,
+            "Variance": np.sqrt(st["m2"]) ** 2, "Uniformity": uniformity}
+    return np.stack([np.asarray(table[n], dtype=np.float64) for n in names], 1)
+
+
 class RadiomicsFirstOrder(RadiomicsFeaturesBase):
     def __init__(self, inputImage, inputMask, **kwargs):
         super().__init__(inputImage, inputMask, **kwargs)
