@@ -630,6 +630,24 @@ int prad_batch_digitize_dev(const void *image, int dtype, const uint8_t *mask, c
                             const double *edges, const long long *edge_off, int32_t *levels, long long *counts,
                             const long long *count_off, int *top, void *stream);
 
+/* ---- the boxes of many labels of one label map, packed for the calls above (csrc/kernels_batch_gather.h) -----------------
+ * prad_batch_gather_dev copies B boxes out of a 3-D volume into the batch layout in ONE launch: ROI b is the box of extent
+ * box[b] ([B][3], z y x) whose first voxel is lo[b] ([B][3]); its voxels go, z-major, to elements offsets[b] .. of out_image
+ * (the image's own dtype: codes 0 float32, 1 float64, 2 int32, 3 int16; values are moved bit for bit) and of out_mask (uint8:
+ * labelmap == labels[b], so voxels of other labels inside the box are outside the ROI; label codes of prad_label_census_dev:
+ * 2 int32, 3 int16, 4 uint8).  image / out_image NULL: masks only; labelmap / out_mask NULL: images only.  image, labelmap and
+ * the outputs are DEVICE buffers; size ([3]), labels, lo, box and offsets are HOST arrays.
+ * Work is divided by output elements -- workgroups take 1024 consecutive elements of the packed output and find their ROIs in a
+ * device table -- so one large box among hundreds of small ones does not serialise on one workgroup.  Volumes and batches
+ * above 2^31 elements are legal: every index is 64-bit.  The device table is kept between calls: a call whose tables equal
+ * those of the previous call on this thread, device and stream (the masks, then every derived image of one label map) uploads
+ * nothing.  One launch on `stream`, no host synchronisation; kernel family "batch_gather", prad_last_variant "batch-gather".
+ * PRAD_E_ARG, before anything is launched: a box that leaves the volume, an extent < 1, offsets[b] before the end of ROI b - 1,
+ * an input without its output, a dtype code outside the lists. */
+int prad_batch_gather_dev(const void *image, int image_dtype, const void *labelmap, int label_dtype, const int *size, int B,
+                          const int *labels, const int *lo, const int *box, const long long *offsets, void *out_image,
+                          unsigned char *out_mask, void *stream);
+
 /* ---- filter stack in front of the matrices (radiomics/imageoperations.py:756-970) ---------------------------
  * The arithmetic of both filters lives in third-party wheels (PyWavelets, SimpleITK/ITK) that are not part of
  * the reference tree; these entry points implement their published algorithms (see oracle/filters_oracle.py):

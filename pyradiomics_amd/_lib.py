@@ -127,6 +127,8 @@ SYMBOLS = {
     "prad_batch_digitize_max_edges": (C.c_int, []),
     "prad_batch_digitize_dev": (C.c_int, [_vp, C.c_int, _vp, _ip, C.POINTER(C.c_longlong), C.c_int, _vp, C.POINTER(C.c_longlong),
                                           _vp, _vp, C.POINTER(C.c_longlong), _vp, _vp]),
+    "prad_batch_gather_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _ip, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_longlong), _vp,
+                                        _vp, _vp]),
     "prad_swt_level1": (C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp]),
     "prad_swt_level1_dev": (C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp, _vp]),
     "prad_swt_level1_any_dev": (C.c_int, [_vp, C.c_int, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp, _vp]),

@@ -643,6 +643,16 @@ def _angle_mean(per_angle, empty):
         return np.nanmean(kept, 0)
 
 
+def _mcc_angle_mean(per_angle):
+    """MCC of a segment from its per-angle values, as the feature class reports it: np.nanmean over the flat vector (empty
+    angles are NaN and drop out).  The batched label route calls this too: a 1-D mean and the column mean of _angle_mean add
+    the angles in different orders, and the two must agree to the last bit."""
+    import warnings
+    with np.errstate(invalid="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        return float(np.nanmean(per_angle))
+
+
 def segment_features(cls, image, mask, Ng, features, distances=(1,), force2D=False, force2Ddimension=0, alpha=0,
                      symmetrical=True, Ns=None):
     """-> {feature name: float} of feature class `cls` ("glcm" | "glrlm" | "glszm" | "gldm" | "ngtdm") in segment mode with the
@@ -708,10 +718,7 @@ def segment_image_enqueue(levels, mask, Ng, Ns, requests, force2D=False, force2D
             vals = part(0, Na * 23).reshape(Na, 23)
             r = named(rq, _angle_mean(vals, flags(1, Na) != 0)) if rq["feats"] else {}
             if rq["mcc"] and lay[2] >= 0 and res[lay[2] + Na] == 0:
-                import warnings
-                with np.errstate(invalid="ignore"), warnings.catch_warnings():
-                    warnings.simplefilter("ignore", RuntimeWarning)
-                    r["MCC"] = float(np.nanmean(res[lay[2]:lay[2] + Na]))
+                r["MCC"] = _mcc_angle_mean(res[lay[2]:lay[2] + Na])
             return r
         out["glcm"] = fin_glcm
     if "glrlm" in take:
@@ -849,10 +856,7 @@ def segment_features_enqueue(cls, image, mask, Ng, features, distances=(1,), for
         def finish():
             res = named(mean_of(pair)) if features else {}
             if mcc is not None and not (dfr and mcc[-1] != 0):
-                import warnings
-                with np.errstate(invalid="ignore"), warnings.catch_warnings():
-                    warnings.simplefilter("ignore", RuntimeWarning)
-                    res["MCC"] = float(np.nanmean(mcc[:-1] if dfr else mcc))
+                res["MCC"] = _mcc_angle_mean(mcc[:-1] if dfr else mcc)
             return res
         return finish
     if cls == "glrlm":

@@ -1936,6 +1936,7 @@ int prad_release_workspace(void) {
   c.arena_pos = 0;
   release_image_queues();
   c.angles_cached.clear();   // (the cached angle tables and the deferred flag lived in the workspace)
+  c.tables_cached.clear();
   StageRing &r = stage_ring();
   for (int i = 0; i < kStageRing; i++) {
     r.buf[i] = nullptr;

@@ -53,6 +53,12 @@ struct DevBuf {
   size_t cap = 0;
 };
 
+// host copy of an argument table that stays on the device between calls, with the stream its upload was queued on
+struct TableCache {
+  std::vector<char> bytes;
+  void *stream = nullptr;
+};
+
 struct KernelTime {
   std::string family;
   hipEvent_t a, b;
@@ -87,6 +93,8 @@ struct Context {
   // workspace buffer: keyed like the device buffer it describes (lane AND device -- a thread that alternates between two
   // GPUs must not take GPU 1's table for GPU 0's)
   std::map<std::string, std::vector<int>> angles_cached;
+  // the same for the ROI table of prad_batch_gather_dev (one upload serves the masks and every derived image of a label map)
+  std::map<std::string, TableCache> tables_cached;
   // Lanes: deferred whole-volume GLCM/GLRLM calls alternate between `lanes` internal streams, each with a workspace of
   // its own, so that the kernels of consecutive volumes share the GPU: the HBM-bound pack of one volume runs while the
   // issue-bound sweep of the previous one holds other CUs, launch gaps and kernel tails are filled (512^3: 0.63 ->

@@ -504,15 +504,10 @@ class LabelRangeError(ValueError):
 _LABEL_CODES = {torch.int32: 2, torch.int16: 3, torch.uint8: 4}
 
 
-def label_census(mask: torch.Tensor, max_label=None):
-    """Every label of an integer label map in one pass over it (prad_label_census_dev): -> (labels int64 [K], counts int64 [K],
-    lo int64 [K, Nd], hi int64 [K, Nd]) for the labels 1..max_label that occur, ascending; lo / hi are the inclusive index
-    bounds in array (z, y, x) order.  Nd is 2 or 3.  Without `max_label` the table is sized by the map's largest value
-    (prad_mask_max_dev).  Values below 1 or above max_label are ignored; max_label above 65535 raises LabelRangeError, a
-    ValueError (the caller then works on the host).  One device-to-host copy: the table."""
-    lib = _lib.load()
+def _label_tensor(mask: torch.Tensor, what: str) -> torch.Tensor:
+    """an integer label map as a contiguous tensor of one of the element types the label kernels read (_LABEL_CODES)"""
     if not mask.is_cuda:
-        raise ValueError("engine.label_census expects a CUDA/HIP tensor")
+        raise ValueError("engine.%s expects a CUDA/HIP tensor" % what.replace(" ", "_"))
     if mask.dtype == torch.bool:
         mask = mask.view(torch.uint8)
     elif mask.dtype == torch.int8:
@@ -521,11 +516,21 @@ def label_census(mask: torch.Tensor, max_label=None):
         # the operator boundary is 32-bit (Image.device_tensor narrows the same way, after the same range check): a value
         # that does not fit must not wrap into the label range
         if mask.numel() and (int(mask.max()) > 2**31 - 1 or int(mask.min()) < -2**31):
-            raise LabelRangeError("label census: int64 label map holds values outside the int32 range")
+            raise LabelRangeError("%s: int64 label map holds values outside the int32 range" % what)
         mask = mask.to(torch.int32)
     if mask.dtype not in _LABEL_CODES:
-        raise ValueError("label census needs an integer label map, not %s" % mask.dtype)
-    mask = mask.contiguous()
+        raise ValueError("%s needs an integer label map, not %s" % (what, mask.dtype))
+    return mask.contiguous()
+
+
+def label_census(mask: torch.Tensor, max_label=None):
+    """Every label of an integer label map in one pass over it (prad_label_census_dev): -> (labels int64 [K], counts int64 [K],
+    lo int64 [K, Nd], hi int64 [K, Nd]) for the labels 1..max_label that occur, ascending; lo / hi are the inclusive index
+    bounds in array (z, y, x) order.  Nd is 2 or 3.  Without `max_label` the table is sized by the map's largest value
+    (prad_mask_max_dev).  Values below 1 or above max_label are ignored; max_label above 65535 raises LabelRangeError, a
+    ValueError (the caller then works on the host).  One device-to-host copy: the table."""
+    lib = _lib.load()
+    mask = _label_tensor(mask, "label census")
     nd = mask.dim()
     dev = mask.device.index if mask.device.index is not None else torch.cuda.current_device()
     _lib.raise_for(lib.prad_set_device(dev), "set_device")
@@ -1014,14 +1019,16 @@ def batch_features_per_angle(mats, Ng, glszm=None, symmetric=True, mcc=True):
 
 
 def texture_features_batch(levels, masks, sizes, Ng, classes=("glcm", "glrlm", "glszm", "gldm", "ngtdm"),
-                           distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True):
+                           distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True, mcc_angles=False):
     """The texture FEATURES of B small ROIs (segment mode, 3-D; inputs as texture_matrices_batch): texture_matrices_batch,
     glszm_batch(compact=True), the formulas of all matrices in two launches (batch_features_per_angle) and, per ROI, the mean
     over the angles the reference keeps (cmatrices._angle_mean).  -> ({class: float64 numpy [B, nfeat]}, status [B]): glcm 24
     columns (cmatrices.VOXEL_GLCM_FEATURES, then MCC -- NaN without `mcc`), glrlm / gldm / glszm 16 (the shared zone numbering),
     ngtdm 5.  status 0: a masked level outside [1, Ng]; that ROI's rows are NaN, the others are not affected.  weightingNorm is
     not offered.  Outside the native domain (Ng > 64, boxes above the batch caps) the single calls are looped and give the same
-    values; last_batch_route() says "batch", "mixed" or "looped"."""
+    values; last_batch_route() says "batch", "mixed" or "looped".  mcc_angles=True adds the entry "glcm_mcc_angles": per ROI the
+    MCC of every angle (float64 [Na], NaN for an empty angle; None with status 0) -- what the feature class averages as a flat
+    vector (cmatrices._mcc_angle_mean), in another order of additions than the column mean of the table."""
     lib, levels, masks, sizes = _batch_inputs(levels, masks, sizes)
     classes = tuple(classes)
     unknown = [c for c in classes if c not in FEATURE_FAMILIES]
@@ -1049,6 +1056,8 @@ def texture_features_batch(levels, masks, sizes, Ng, classes=("glcm", "glrlm", "
                 vals, empty = per[f][b]
                 rows[b] = vals[0] if f == "ngtdm" else _cm._angle_mean(vals, empty)
         table[f] = rows
+    if mcc_angles and "glcm" in classes:
+        table["glcm_mcc_angles"] = [per["glcm"][b][0][:, 23].copy() if status[b] else None for b in range(B)]
     _cm._set_batch_route(routes[0] if all(r == routes[0] for r in routes) else "mixed")
     return table, status.tolist()
 
@@ -1180,7 +1189,7 @@ def bin_batch(images, masks, sizes=None, stats=None, **binning):
 
 
 def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, binWidth=None, binCount=None, voxelArrayShift=0,
-                       voxelVolume=1.0, distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True):
+                       voxelVolume=1.0, distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True, extras=False):
     """The feature table of B small ROIs from their raw intensity boxes and masks (inputs as firstorder_batch): firstorder_batch
     and bin_batch -- two launches and two read-backs for the whole batch (binWidth, default 25, or binCount) -- then
     texture_features_batch once per distinct Ng of the batch on the ROIs that share it.  -> ({class: float64 numpy [B, nfeat]},
@@ -1188,7 +1197,9 @@ def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, b
     statistics, the level counts and voxelVolume, a number or [B]); the texture classes the columns of texture_features_batch.
     status 0: an empty ROI; its rows are NaN, the others are not affected.  last_batch_route() says "batch", "mixed" or
     "looped" (texture_features_batch loops the single calls above 64 levels; MCC is not evaluated there -- its column is NaN
-    for a ROI with more than 64 levels, as without `mcc`)."""
+    for a ROI with more than 64 levels, as without `mcc`).  extras=True adds two entries the label route of the feature extractor
+    needs to report what the feature classes report: "gray_levels" int64 [B], the number of grey levels that occur in the ROI, and
+    (with glcm) "glcm_mcc_angles", see texture_features_batch."""
     from . import firstorder as _fo
     lib, images, masks, sizes = _batch_inputs(images, masks, sizes, raw=True)
     classes = tuple(classes)
@@ -1209,6 +1220,7 @@ def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, b
         vals[status == 0] = np.nan
         table["firstorder"] = vals
     texture = tuple(c for c in classes if c != "firstorder")
+    angles = [None] * B
     if texture:
         for c in texture:
             table[c] = np.full((B, _FEATURE_ROW[c]), np.nan)
@@ -1220,14 +1232,80 @@ def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, b
                 sub_l = torch.cat([levels[int(off[b]):int(off[b] + nvox[b])] for b in idx])
                 sub_m = torch.cat([masks[int(off[b]):int(off[b] + nvox[b])] for b in idx])
             sub, st = texture_features_batch(sub_l, sub_m, sizes[idx], ng, texture, distances, gldm_a, symmetricalGLCM,
-                                             mcc and ng <= 64)       # (glcm_mcc declines more than 64 occurring levels)
+                                             mcc and ng <= 64,       # (glcm_mcc declines more than 64 occurring levels)
+                                             mcc_angles=extras and mcc and ng <= 64)
             routes.append(last_batch_route())
+            for k, b in enumerate(idx):
+                if "glcm_mcc_angles" in sub:
+                    angles[b] = sub["glcm_mcc_angles"][k]
             for c in texture:
                 table[c][idx] = sub[c]
             status[idx] &= np.asarray(st, dtype=np.int64)
     table = {c: table[c] for c in classes}
+    if extras:
+        table["gray_levels"] = np.array([int((np.asarray(c[1:]) > 0).sum()) for c in counts], dtype=np.int64)
+        if "glcm" in classes:
+            table["glcm_mcc_angles"] = angles
     _cm._set_batch_route(_joined_route(routes))
     return table, status.tolist()
+
+
+# ---- the boxes of many labels of one label map in the batch layout (prad_batch_gather_dev, csrc/kernels_batch_gather.h) ---------
+def gather_rois_batch(image, labelmap, labels, lo, hi, masks=True, images=True):
+    """The boxes of B labels cut out of one 3-D volume in ONE launch, packed the way _batch_inputs(..., raw=True) takes them.
+    image / labelmap: device tensors of one shape (either may be None when its output is not asked for); labels int [B]; lo / hi
+    int [B, 3]: inclusive (z, y, x) bounds, as label_census returns them (boxes may overlap).  -> (flat image tensor, flat uint8
+    mask tensor, sizes int32 [B, 3]); the mask of ROI b is labelmap == labels[b] inside its box, the image keeps its dtype where
+    it is one of the four the batched kernels read (float32, float64, int32, int16; anything else is widened to float64) and
+    its values bit for bit.  masks=False / images=False leave that output None.  The label map is narrowed as label_census
+    narrows it.  A box that leaves the volume, hi < lo or tensors on two devices raise ValueError before anything is launched.
+    No read-back and no host synchronisation; the table of boxes stays on the device while consecutive calls repeat it."""
+    lib = _lib.load()
+    if not masks and not images:
+        raise ValueError("gather_rois_batch: neither masks nor images asked for")
+    ref = image if images else labelmap
+    if (images and image is None) or (masks and labelmap is None):
+        raise ValueError("gather_rois_batch: the %s is missing" % ("image" if images and image is None else "label map"))
+    if not ref.is_cuda:
+        raise ValueError("engine.gather_rois_batch expects CUDA/HIP tensors")
+    if images and masks and (not labelmap.is_cuda or image.device != labelmap.device):
+        raise ValueError("gather_rois_batch: image on %s, label map on %s" % (image.device, labelmap.device))
+    if ref.dim() != 3 or (images and masks and image.shape != labelmap.shape):
+        raise ValueError("gather_rois_batch takes a 3-D image and a label map of the same shape")
+    lo = np.ascontiguousarray(np.asarray(lo, dtype=np.int64).reshape(-1, 3))
+    hi = np.ascontiguousarray(np.asarray(hi, dtype=np.int64).reshape(-1, 3))
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    B = int(lo.shape[0])
+    if B < 1 or hi.shape[0] != B or labels.shape[0] != B:
+        raise ValueError("gather_rois_batch: %d lower bounds, %d upper bounds, %d labels" % (B, hi.shape[0], labels.shape[0]))
+    if (hi < lo).any():
+        raise ValueError("gather_rois_batch: ROI %d has hi < lo" % int(np.flatnonzero((hi < lo).any(1))[0]))
+    if (lo < 0).any() or (hi >= np.asarray(ref.shape, dtype=np.int64)).any():
+        raise ValueError("gather_rois_batch: ROI %d leaves the volume %s"
+                         % (int(np.flatnonzero(((lo < 0) | (hi >= np.asarray(ref.shape))).any(1))[0]), tuple(ref.shape)))
+    if (labels > 2**31 - 1).any() or (labels < -2**31).any():
+        raise ValueError("gather_rois_batch: labels outside the int32 range")
+    if images:
+        image = (image if image.dtype in _DTYPE_CODES else image.to(torch.float64)).contiguous()
+    if masks:
+        labelmap = _label_tensor(labelmap, "gather rois batch")
+    sizes = np.ascontiguousarray((hi - lo + 1).astype(np.intc))
+    off, nvox = _roi_offsets(sizes)
+    total = int(nvox.sum())
+    dev = ref.device
+    _lib.raise_for(lib.prad_set_device(dev.index if dev.index is not None else torch.cuda.current_device()), "set_device")
+    out_i = torch.empty(total, dtype=image.dtype, device=dev) if images else None
+    out_m = torch.empty(total, dtype=torch.uint8, device=dev) if masks else None
+    size = np.array(ref.shape, dtype=np.intc)
+    lo32, lab32 = np.ascontiguousarray(lo.astype(np.intc)), np.ascontiguousarray(labels.astype(np.intc))
+    rc = lib.prad_batch_gather_dev(C.c_void_p(image.data_ptr()) if images else None, _DTYPE_CODES[image.dtype] if images else 0,
+                                   C.c_void_p(labelmap.data_ptr()) if masks else None,
+                                   _LABEL_CODES[labelmap.dtype] if masks else 0, _iptr(size), B,
+                                   _iptr(lab32), _iptr(lo32), _iptr(sizes), _lp(off),
+                                   C.c_void_p(out_i.data_ptr()) if images else None,
+                                   C.c_void_p(out_m.data_ptr()) if masks else None, _stream_ptr())
+    _lib.raise_for(rc, "batched ROI gather")
+    return out_i, out_m, sizes
 
 
 NEIGH_GLDM, NEIGH_NGTDM = 0, 1

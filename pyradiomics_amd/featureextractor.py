@@ -69,6 +69,20 @@ class RadiomicsFeatureExtractor:
             self.enabledImagetypes = {"Original": {}}
             self.enabledFeatures = {n: [] for n in self.featureClassNames}
 
+    _labelsRoute = None
+
+    def lastLabelsRoute(self):
+        """{"batched": [...], "single": [...], "mixed": [...]}: which way the labels of the last FINISHED executeLabels call
+        went, each list in the order the results were yielded.  "batched": every value came from the batched small-ROI
+        kernels; "mixed": batched, with at least one (label, derived image) pair recomputed by the per-label class pipeline;
+        "single": the per-label steps (every label without `batched=True`).  Skipped labels are in no list."""
+        route = self._labelsRoute or {}
+        return {k: list(route.get(k, ())) for k in ("batched", "single", "mixed")}
+
+    def lastLabelsRecomputed(self):
+        """[(label, image type name)] of that call: the pairs of its "mixed" labels the per-label class pipeline recomputed"""
+        return list((self._labelsRoute or {}).get("recomputed", ()))
+
     @staticmethod
     def _getDefaultSettings():
         # featureextractor.py:139-163 (keys that reach the accelerated path keep their defaults)
@@ -224,7 +238,7 @@ class RadiomicsFeatureExtractor:
                 if state is not None and state[0] is not None:
                     state[0].close()                 # (abandons what the unfinished case queued)
 
-    def executeLabels(self, imageFilepath, maskFilepath, labels=None, label_channel=None):
+    def executeLabels(self, imageFilepath, maskFilepath, labels=None, label_channel=None, batched=False):
         """Generator of (label, result) over the labels of ONE label map: every label the map holds, ascending, or `labels` in
         their order.  Each result is execute(image, mask, label=l), key for key and bit for bit, diagnostics included; what
         does not depend on the label is done once per call instead of once per label:
@@ -242,7 +256,13 @@ class RadiomicsFeatureExtractor:
         execute() holds the ones in flight.
         With labels=None a label that fails an ROI check of execute() (minimumROIDimensions, minimumROISize, absent after
         processing) is skipped with a logged warning; with an explicit list the ValueError of execute() is raised at that
-        label's position, after the results of the labels before it.  Segment-based extraction only."""
+        label's position, after the results of the labels before it.  Segment-based extraction only.
+        batched=True: the labels inside the domain of the batched small-ROI kernels (_batchedLabels) are not run one by one:
+        their boxes are gathered on the device (one launch for the masks, one per derived image) and every derived image
+        costs one engine.roi_features_batch for all of them.  Results, order, failures and warnings are those of the default
+        mode -- texture features, order statistics and counts bit for bit; the summed first-order features come from the
+        batched kernel's own summation order -- and every other label takes the per-label steps unchanged.
+        lastLabelsRoute() tells which label went which way."""
         s = self.settings.copy()
         if labels is not None:
             labels = [l for l in labels]
@@ -268,16 +288,30 @@ class RadiomicsFeatureExtractor:
             s["label"] = self.settings.get("label", 1)
             base = imageoperations.normalizeImage(image, **s) if s.get("normalize", False) else image
             shared = (base, list(self._derivedImages(base, mask, s)))
+        route = {"batched": [], "single": [], "mixed": []}
+        ready, mixed = {}, {}
+        if batched and shared is not None and on_dev:
+            ready, mixed = self._batchedLabels(image, mask, labels, shared, s)
         prev, cur = None, None
         try:
             for lab in labels:
+                feats = ready.get(self._labelKey(lab)) if ready else None
+                if feats is not None:                # (computed with the whole batched set, before the first result)
+                    if prev is not None:
+                        last, prev = prev, None
+                        yield last[0], self._finishSteps(last[1:])
+                    prev = (lab, None, self._batchedResult(image, mask, lab, label_channel, on_dev, feats))
+                    route["mixed" if self._labelKey(lab) in mixed else "batched"].append(lab)
+                    continue
                 steps = self._executeSteps(image, mask, lab, label_channel, False, shared=shared)
                 failed = None
                 try:
                     next(steps)                      # head of this label: ROI checks, its first crop queued
                     cur = (lab, steps, None)
+                    route["single"].append(lab)
                 except StopIteration as done:
                     cur = (lab, None, done.value)
+                    route["single"].append(lab)
                 except ValueError as e:
                     if discover:
                         logger.warning("label %s skipped: %s", lab, e)
@@ -297,10 +331,134 @@ class RadiomicsFeatureExtractor:
             if prev is not None:
                 last, prev = prev, None
                 yield last[0], self._finishSteps(last[1:])
+            route["recomputed"] = [(lab, name) for lab in route["mixed"] for name in mixed[self._labelKey(lab)]]
+            self._labelsRoute = route
         finally:
             for state in (prev, cur):
                 if state is not None and state[1] is not None:
                     state[1].close()                 # (abandons what the unfinished label queued: _abandonFeatures)
+
+    # -- executeLabels(batched=True): the labels the batched small-ROI kernels take ------------------------------
+    @staticmethod
+    def _labelKey(label):
+        """the census's key of a label (int), None for what the census does not count"""
+        try:
+            return int(label) if label == int(label) and int(label) >= 1 else None
+        except (TypeError, ValueError):
+            return None
+
+    def _batchedColumns(self):
+        """{class: [(feature name, column of engine.roi_features_batch's table)]} for the enabled features, in the order
+        execute() returns them (the names given to enableFeaturesByName, or every feature that is not deprecated), or None
+        when a feature is enabled that the batched tables do not hold"""
+        from . import cmatrices
+        classes = getFeatureClasses()
+        cols = {}
+        for cname, fnames in self.enabledFeatures.items():
+            if cname not in classes:
+                continue
+            held = cmatrices.FIRSTORDER_FEATURES if cname == "firstorder" else cmatrices.batch_feature_names(cname)
+            names = (list(dict.fromkeys(fnames)) if fnames
+                     else [n for n, dep in classes[cname].getFeatureNames().items() if not dep])
+            if not names or any(n not in held for n in names):
+                return None
+            cols[cname] = [(n, held.index(n)) for n in names]
+        return cols or None
+
+    def _batchedLabels(self, image, mask, labels, shared, s):
+        """The feature values of every label of `labels` inside the batched domain: -> ({label: OrderedDict of its
+        <imageType>_<class>_<feature> values in execute()'s order}, {label: [image type names]} of the recomputed pairs).
+        Domain of the call: 3-D image, no weightingNorm, no force2D, the fused device formulas (`fusedSegment`), every enabled
+        feature a column of the batched tables.  Domain of a label: present, no axis of extent 1, passes minimumROISize /
+        minimumROIDimensions.  The boxes are those cropToTumorMask(padDistance=0, alignRows=True) cuts, so the batched
+        kernels read the very arrays the per-label classes read.  A (label, derived image) pair whose row lacks a value --
+        MCC above 64 grey levels, a derived image of an element type the kernels do not read -- is recomputed by the class
+        pipeline on that crop: NaN never stands in for a value execute() has."""
+        derived = shared[1]
+        cols = self._batchedColumns()
+        if cols is None or not derived or len(image.shape) != 3 or len(mask.shape) != 3:
+            return {}, {}
+        for _img, _name, kw in derived:
+            if kw.get("weightingNorm") is not None or kw.get("force2D", False) or not kw.get("fusedSegment", True):
+                return {}, {}
+        if s.get("minimumROIDimensions", 2) > 3:
+            return {}, {}
+        chosen = {}
+        for lab in labels:
+            key = self._labelKey(lab)
+            known = imageoperations.censusLookup(mask, lab) if key is not None else None
+            if known is None or known[0] == 0 or key in chosen:
+                continue
+            count, lo, hi = known
+            if (hi - lo + 1 <= 1).any() or (s.get("minimumROISize") is not None and count <= s["minimumROISize"]):
+                continue
+            chosen[key] = (lo, hi)
+        if not chosen:
+            return {}, {}
+        from . import cmatrices
+        engine = imageoperations._engine()
+        keys = list(chosen)
+        lo, hi = imageoperations.alignedBox(np.stack([chosen[k][0] for k in keys]), np.stack([chosen[k][1] for k in keys]),
+                                            mask.shape)
+        labelmap = mask.device_tensor()
+        _, flat_m, sizes = engine.gather_rois_batch(None, labelmap, keys, lo, hi, masks=True, images=False)
+        feats = {k: collections.OrderedDict() for k in keys}
+        mixed = {}
+        for dimg, typeName, kw in derived:
+            t = dimg.device_tensor()
+            table = None
+            if t.dtype in engine._DTYPE_CODES and tuple(t.shape) == tuple(labelmap.shape):
+                flat_i, _, _ = engine.gather_rois_batch(t, None, keys, lo, hi, masks=False, images=True)
+                table, status = engine.roi_features_batch(
+                    flat_i, flat_m, sizes, classes=tuple(cols), binWidth=kw.get("binWidth"), binCount=kw.get("binCount"),
+                    voxelArrayShift=kw.get("voxelArrayShift", 0), voxelVolume=np.multiply.reduce(dimg.GetSpacing()),
+                    distances=[int(d) for d in np.asarray(kw.get("distances", [1])).ravel()], gldm_a=int(kw.get("gldm_a", 0)),
+                    symmetricalGLCM=bool(kw.get("symmetricalGLCM", True)), extras=True)
+            for b, k in enumerate(keys):
+                block = collections.OrderedDict()
+                whole = table is not None and bool(status[b])
+                if whole:
+                    for cname, pairs in cols.items():
+                        row = table[cname][b]
+                        for fname, col in pairs:
+                            value = row[col]
+                            if cname == "glcm" and fname == "MCC":
+                                # as RadiomicsGLCM reports it: 1 for a ROI of one grey level, else the flat mean over the angles
+                                per_angle = table["glcm_mcc_angles"][b]
+                                value = (1.0 if table["gray_levels"][b] < 2 else
+                                         np.nan if per_angle is None else cmatrices._mcc_angle_mean(per_angle))
+                            block["%s_%s_%s" % (typeName, cname, fname)] = np.array(value)
+                    whole = not any(np.isnan(v) for v in block.values())
+                if not whole:
+                    cimg, cmask = imageoperations.cropToTumorMask(dimg, mask, k, padDistance=0, deviceResident=True)
+                    block = self.computeFeatures(cimg, cmask, typeName, **dict(kw, label=k))
+                    mixed.setdefault(k, []).append(typeName)
+                feats[k].update(block)
+        return feats, mixed
+
+    def _batchedResult(self, image, mask, label, label_channel, on_dev, feats):
+        """the result of one batched label: execute()'s diagnostics, from the census, in front of its feature values"""
+        s = self.settings.copy()
+        s["label"] = label
+        if label_channel is not None:
+            s["label_channel"] = label_channel
+        s["deviceResident"] = on_dev
+        out = collections.OrderedDict()
+        if s.get("additionalInfo", True):
+            nvox, blo, bhi = imageoperations.censusLookup(mask, label)
+            out["diagnostics_Versions_PyRadiomicsAMD"] = __version__
+            out["diagnostics_Versions_Numpy"] = np.__version__
+            out["diagnostics_Configuration_Settings"] = {k: v for k, v in s.items()}
+            out["diagnostics_Configuration_EnabledImageTypes"] = dict(self.enabledImagetypes)
+            out["diagnostics_Image-original_Spacing"] = image.GetSpacing()
+            out["diagnostics_Image-original_Size"] = image.GetSize()
+            out["diagnostics_Mask-original_Spacing"] = mask.GetSpacing()
+            out["diagnostics_Mask-original_Size"] = mask.GetSize()
+            out["diagnostics_Mask-original_BoundingBox"] = tuple(int(v) for v in blo[::-1]) + \
+                tuple(int(v) for v in (bhi - blo + 1)[::-1])
+            out["diagnostics_Mask-original_VoxelNum"] = nvox
+        out.update(feats)
+        return out
 
     @staticmethod
     def _finishSteps(state):

@@ -163,6 +163,18 @@ def censusLookup(mask, label):
     return int(memo["counts"][i]), memo["lo"][i].astype(int), memo["hi"][i].astype(int)
 
 
+def alignedBox(lo, hi, shape):
+    """The box the device crop cuts for inclusive bounds lo / hi (int [Nd] or [B, Nd], array order): its x extent grown to a
+    multiple of four voxels, to the right as far as the volume reaches and to the left for the rest (at both edges the box
+    stays short).  -> (lo, hi), new arrays.  Pure host arithmetic."""
+    lo, hi = np.array(lo), np.array(hi)
+    need = (-(hi[..., -1] - lo[..., -1] + 1)) % 4
+    grow = np.minimum(need, int(shape[-1]) - 1 - hi[..., -1])
+    hi[..., -1] += grow
+    lo[..., -1] -= np.minimum(need - grow, lo[..., -1])
+    return lo, hi
+
+
 def cropToTumorMask(image, mask, label=1, padDistance=0, deviceResident=False, alignRows=True):
     """Crops image and mask to the ROI bounding box padded by `padDistance` voxels, clipped to the image
     (imageoperations.py:407-445).  Accepts / returns pyradiomics_amd.image.Image.  With `deviceResident` the crop
@@ -188,12 +200,7 @@ def cropToTumorMask(image, mask, label=1, padDistance=0, deviceResident=False, a
         # Rows of a multiple of 4 voxels keep every kernel on its packed 4-voxels-per-lane path (a 231-wide crop of a
         # 256^3 case sent GLSZM, GLDM and NGTDM down their one-voxel-per-lane kernels: 2-3x slower).  The extra columns
         # lie outside the ROI's bounding box, so they are outside the ROI: no matrix, no statistic sees them.
-        need = (-(int(hi[-1]) - int(lo[-1]) + 1)) % 4
-        grow = min(need, int(msk.shape[-1]) - 1 - int(hi[-1]))
-        hi = hi.copy()
-        lo = lo.copy()
-        hi[-1] += grow
-        lo[-1] -= min(need - grow, int(lo[-1]))
+        lo, hi = alignedBox(lo, hi, msk.shape)
     sl = tuple(slice(int(a), int(b) + 1) for a, b in zip(lo, hi))
     nd = len(img.shape)
     d = np.array(img.direction, dtype=float).reshape(nd, nd)

@@ -53,6 +53,10 @@ def get_parser():
     g.add_argument("--all-labels", action="store_true",
                    help="Segment mode: extract every label the mask holds (one output row per label, its value in the "
                         "Label column) in one pass per case; a Label column of the batch file is ignored")
+    g.add_argument("--batch-labels", action="store_true",
+                   help="Segment mode: --all-labels with the labels' boxes gathered on the device and run through the batched "
+                        "small-ROI kernels (executeLabels(batched=True): the same rows; labels outside that route's domain "
+                        "are extracted one by one as without this option)")
     g.add_argument("--validate", action="store_true", help="Only check that the input files exist")
     o = p.add_argument_group("Output")
     o.add_argument("--out", "-o", metavar="FILE", type=argparse.FileType("a"), default=sys.stdout,
@@ -183,16 +187,17 @@ def extract_segment(case_idx, case, extractor, out_dir=None):
     return fv
 
 
-def extract_segment_labels(case_idx, case, extractor):
+def extract_segment_labels(case_idx, case, extractor, batched=False):
     """--all-labels: one row per label of the case's mask (RadiomicsFeatureExtractor.executeLabels: the case is loaded,
     uploaded and filtered once), the label in the `Label` column the reference's batch files use (scripts/segment.py:60-66).
-    A case that fails keeps the rows of the labels extracted before the failure, or its bare row when there is none."""
+    `batched` (--batch-labels) is handed on to executeLabels.  A case that fails keeps the rows of the labels extracted before the failure, or its bare row when there is none."""
     rows = []
     try:
         t = time.perf_counter()
         channel = case.get("Label_channel") or None
         for label, result in extractor.executeLabels(case["Image"], case["Mask"],
-                                                     label_channel=int(channel) if channel is not None else None):
+                                                     label_channel=int(channel) if channel is not None else None,
+                                                     **({"batched": True} if batched else {})):
             fv = collections.OrderedDict(case)
             fv["Label"] = int(label)
             fv.update((k, _scalar(v)) for k, v in result.items())
@@ -233,24 +238,25 @@ def extract_voxel(case_idx, case, extractor, out_dir=None, unix_path=False):
 
 
 def _run_case(job):
-    case_idx, case, mode, out_dir, unix_path, all_labels = job
+    case_idx, case, mode, out_dir, unix_path, all_labels = job[:6]
     ex = _WORKER["extractor"]
     if mode == "segment" and all_labels:
-        return case_idx, extract_segment_labels(case_idx, case, ex)       # (a list of rows)
+        return case_idx, extract_segment_labels(case_idx, case, ex, *job[6:])       # (a list of rows)
     if mode == "segment":
         return case_idx, extract_segment(case_idx, case, ex, out_dir)
     return case_idx, extract_voxel(case_idx, case, ex, out_dir, unix_path)
 
 
 def process_cases(cases, param, overrides, mode="segment", jobs=1, gpus=None, out_dir=None, unix_path=False,
-                  log_level="WARNING", all_labels=False):
-    """-> [feature row per case, input order]; with all_labels (segment mode) one row per label of every case.  jobs == 1
-    runs in this process on the current GPU."""
+                  log_level="WARNING", all_labels=False, batch_labels=False):
+    """-> [feature row per case, input order]; with all_labels (segment mode) one row per label of every case, with
+    batch_labels (which implies all_labels) through executeLabels(batched=True).  jobs == 1 runs in this process on the
+    current GPU."""
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
     jobs = max(1, min(jobs, len(cases)))
-    all_labels = bool(all_labels) and mode == "segment"
-    work = [(i, c, mode, out_dir, unix_path, all_labels) for i, c in cases]
+    all_labels = (bool(all_labels) or bool(batch_labels)) and mode == "segment"
+    work = [(i, c, mode, out_dir, unix_path, all_labels) + ((True,) if batch_labels else ()) for i, c in cases]
 
     def flat(rows):
         return [r for per_case in rows for r in per_case] if all_labels else rows
@@ -340,10 +346,14 @@ def main(argv=None):
     if not cases:
         logger.error("No cases to process...")
         return 1
+    if args.batch_labels and args.mode != "segment":
+        logger.error("--batch-labels is a segment mode option (the batched kernels have no voxel-based form)")
+        return 1
     try:
         gpus = [int(g) for g in args.gpus.split(",")] if args.gpus else None
         results = process_cases(cases, args.param, parse_overrides(args.setting, args.label), args.mode, args.jobs,
-                                gpus, args.out_dir, args.unix_path, level, all_labels=args.all_labels)
+                                gpus, args.out_dir, args.unix_path, level, all_labels=args.all_labels or args.batch_labels,
+                                batch_labels=args.batch_labels)
         write_results(results, args.out, args.format, args.skip_nans, args.format_path, args.unix_path, start)
     except (KeyboardInterrupt, SystemExit):
         logger.info("Cancelling Extraction")
