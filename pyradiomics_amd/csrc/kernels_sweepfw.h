@@ -89,6 +89,12 @@ struct FwSet {
   int nrows;         // rows of the packed volume
   int xcd;           // 1: chunks are handed out per XCD (each XCD's L2 then serves ONE z-slab of the level volume to all roles)
   int first_block[PRAD_MAX_SWEEP + 1];   // role r owns workgroups [first_block[r], first_block[r + 1]) of the 1-D grid
+  // the x angle as the TRAILING role `count` of the launch (workgroups [first_block[count], first_block[count + 1]); none: the
+  // grid ends at first_block[count]), see sweep_fw_kernel
+  int xslot;         // its output column
+  int xRS;           // length slots of ITS table (smaller than the walk's: the staging tiles share the LDS)
+  int xwaves;        // waves of an x workgroup that walk rows (one staging tile each); the others only zero and flush
+  int xgpd;          // row groups one dequeue hands out
   FwDesc d[PRAD_MAX_SWEEP];
 };
 
@@ -957,11 +963,28 @@ __device__ __forceinline__ void fw_row_word(const FwTab &T, u32 one, int &s, u32
 #undef PRAD_FW_RCOL_NZ
 }
 
-// the walk along x for workgroup bx of nblocks; the LDS table (layout h, zeroed by the caller) sits at address 0
+// row groups of the x angle: 64 rows each, 8 rows apart on volumes of 4096 rows and more (fw_rows_role)
+__host__ __device__ inline long long fw_row_groups(long long nrows) {
+  return nrows >= 4096 ? ((nrows + 511) / 512) * 8 : (nrows + 63) / 64;
+}
+
+// the walk along x for workgroup bx of nblocks, wave `wave` of its wpb walking waves; the LDS table (layout h, zeroed by the
+// caller) sits at address 0.  Hand-out of the row groups: a wave's first group is its index among the nblocks * wpb walking
+// waves; the rest are dealt out statically (heads == nullptr: the launch of its own, whose workgroups all start together)
+// or pulled from counters (the trailing role of sweep_fw_kernel, whose workgroups start whenever a CU comes free: one that
+// starts early then walks more of the angle).  The groups behind the static ones are cut into PRAD_FW_DOMAINS contiguous
+// ranges with a head word each (a cache line of its own, zeroed per volume); a wave pulls `gpd` groups at a time from the
+// range of its XCD and moves on to the next range when that one is empty.  Up to 2048 waves pull and a group takes ~20 us:
+// one head would sit near the ~90 pulls per microsecond a word can serve, eight stay far below it -- with ONE group per
+// pull, which is what ships: at 512^3 a wave walks two groups, and a pull of two leaves one wave with three and another
+// with one (the launch 0.452 ms against 0.442; four per pull 0.478: profiles/fw_xrole_measurements.md).  A head is READ
+// before it is pulled (a plain load of an exhausted head costs no atomic: every wave ends with eight of those instead of
+// eight pulls that fail).  Which range a wave starts with only matters for speed.
 template <bool LONG, bool ZA>
 __device__ __forceinline__ void fw_rows_role(const HistLayout &h, const FwTab &T, u32 *lds, const uint8_t *__restrict__ L,
-                                             long long nrows, int NX, int pitch, int bx, int nblocks) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+                                             long long nrows, int NX, int pitch, int bx, int nblocks, int wave, int wpb,
+                                             int *heads, int gpd) {
+  const int lane = threadIdx.x & 63;
   const int dummy = T.dummy0b + 4 * lane;
   u32 one = 1;
   asm volatile("" : "+v"(one));
@@ -972,10 +995,18 @@ __device__ __forceinline__ void fw_rows_role(const HistLayout &h, const FwTab &T
   // serialise: the x angle of the smooth 512^3 volume took 0.12 ms against 0.06 on iid levels).  Every row is its own
   // set of cache lines either way.  (Small volumes keep adjacent rows: their last group of 512 would be mostly empty.)
   const int RSTEP = nrows >= 4096 ? 8 : 1;
-  const long long ngroups = RSTEP == 8 ? ((nrows + 511) / 512) * 8 : (nrows + 63) / 64;
+  const long long ngroups = fw_row_groups(nrows);
   const long long nwaves = (long long)nblocks * wpb;
   const bool vec16 = (pitch & 15) == 0 && ((uintptr_t)L & 15) == 0;
-  for (long long grp = (long long)bx * wpb + wave; grp < ngroups; grp += nwaves) {
+  // pulled groups: the batch in hand [bnext, bend), the range being served and how many ranges were found empty
+  const int ndyn = (heads && ngroups > nwaves) ? (int)(ngroups - nwaves) : 0;   // (groups stay below 2^25: volumes below 2^31 voxels)
+  int bnext = 0, bend = 0, dom = 0, tried = 0;
+  if (ndyn > 0) {
+    int id;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(id));
+    dom = id & (PRAD_FW_DOMAINS - 1);
+  }
+  for (long long grp = (long long)bx * wpb + wave; grp < ngroups;) {
     const long long r0 = RSTEP == 8 ? (grp >> 3) * 512 + (grp & 7) : grp * 64;     // row of tile slot i: r0 + RSTEP * i
     int s = 0;     // run state of this lane's row
     u32 pw = 0;    // previous staged word (its last byte is the previous voxel)
@@ -1055,13 +1086,40 @@ __device__ __forceinline__ void fw_rows_role(const HistLayout &h, const FwTab &T
       __builtin_amdgcn_wave_barrier();
     }
     fw_checked<LONG>(T, dummy, s, (int)(pw >> 24), 0, false);   // the row ends: close its open run
+    if (!heads) {
+      grp += nwaves;
+      continue;
+    }
+    grp = ngroups;   // (nothing left unless a pull says otherwise)
+    if (bnext >= bend) {
+      while (tried < PRAD_FW_DOMAINS && ndyn > 0) {
+        const int lo = (int)((long long)ndyn * dom / PRAD_FW_DOMAINS), hi = (int)((long long)ndyn * (dom + 1) / PRAD_FW_DOMAINS);
+        int got = hi;
+        if (lane == 0) {
+          int *head = heads + dom * PRAD_FW_WORK_STRIDE;
+          got = lo + __hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (got < hi) got = lo + atomicAdd(head, gpd);
+        }
+        got = __builtin_amdgcn_readfirstlane(got);
+        if (got < hi) {
+          bnext = got;
+          bend = min(got + gpd, hi);
+          break;
+        }
+        tried++;
+        dom = (dom + 1) & (PRAD_FW_DOMAINS - 1);
+      }
+    }
+    if (bnext < bend) grp = nwaves + bnext++;
   }
 }
 
-// the angle along x as a launch of its own (8-wave workgroups: table + 8 staging tiles).  As a ROLE of sweep_fw_kernel
-// (16-wave workgroups next to the line roles') the same walk measured slower per CU -- 22.9 CU-ms instead of 14 at 512^3,
-// the whole launch 0.477 ms against 0.38 + 0.055 for the two launches -- and its code made the line roles' kernel half as
-// large again (profiles/r03_probes.md), so it stays a kernel of its own.
+// the angle along x as a launch of its own (8-wave workgroups: table + 8 staging tiles): what PRAD_FW_XROLE=0 runs, and
+// every call that is not a fused-table GLCM + GLRLM call.  Round 3 tried the same walk as a STATIC role of sweep_fw_kernel --
+// 16-wave workgroups that held their CUs from the start of the launch, their number a guess -- and measured 22.9 CU-ms
+// instead of 14 at 512^3, the whole launch 0.477 ms against 0.38 + 0.055 for the two launches (profiles/r03_probes.md).
+// The role sweep_fw_kernel has now is another one: TRAILING workgroups that are dispatched as the line roles' workgroups
+// retire and pull their row groups from counters (profiles/fw_xrole_measurements.md).
 template <bool LONG>
 __global__ void __launch_bounds__(1024) sweep_fw_rows_kernel(const uint8_t *__restrict__ L, long long nrows, int NX, int pitch,
                                                             int slot, int Ng, int Nr, int RS, u32 *__restrict__ glcm_acc,
@@ -1077,12 +1135,14 @@ __global__ void __launch_bounds__(1024) sweep_fw_rows_kernel(const uint8_t *__re
   __syncthreads();
   FwTab T;
   T.init(h, Nr, glrlm_acc + (size_t)slot * Ng * Nr);
-  if (flags[3] != 0) fw_rows_role<LONG, true>(h, T, lds, L, nrows, NX, pitch, (int)blockIdx.x, (int)gridDim.x);
-  else fw_rows_role<LONG, false>(h, T, lds, L, nrows, NX, pitch, (int)blockIdx.x, (int)gridDim.x);   // (no voxel outside the ROI)
+  const int wave = (int)(threadIdx.x >> 6), wpb = (int)(blockDim.x >> 6);
+  if (flags[3] != 0) fw_rows_role<LONG, true>(h, T, lds, L, nrows, NX, pitch, (int)blockIdx.x, (int)gridDim.x, wave, wpb, nullptr, 0);
+  else fw_rows_role<LONG, false>(h, T, lds, L, nrows, NX, pitch, (int)blockIdx.x, (int)gridDim.x, wave, wpb, nullptr, 0);   // (no voxel outside the ROI)
   flush_block_hist<true, true, true>(lds + Ng + 1, h, Nr, slot, glcm_acc, glrlm_acc);
 }
 
-// One launch per volume: a 1-D grid of one 16-wave workgroup per CU, cut into ROLES -- one per line angle -- plus, with PACK,
+// One launch per volume: a 1-D grid of one 16-wave workgroup per CU, cut into ROLES -- one per line angle, and behind them the
+// x angle's trailing workgroups when the call has one (see there) -- plus, with PACK,
 // the pack of the NEXT volume as a side job of the walking waves (PackJob; the instantiation without it spares the walk
 // the side job's registers: 0.39 instead of 0.405 ms per 512^3 volume).  A volume whose pack found irregular levels
 // (flags[0]) is skipped -- the generic kernels redo that call -- but the side job still runs.
@@ -1092,12 +1152,43 @@ __global__ void __launch_bounds__(1024) sweep_fw_kernel(FwSet set, PackJob pj, c
                                                         u32 *__restrict__ glcm_acc, u32 *__restrict__ glrlm_acc,
                                                         int *__restrict__ work, int *__restrict__ flags) {
   extern __shared__ u32 lds[];
+  const int wpb = (int)(blockDim.x >> 6);
+  if ((int)blockIdx.x >= set.first_block[set.count]) {
+    // The x angle: the workgroups BEHIND the line roles'.  The line roles fill every CU, so these are dispatched as CUs come
+    // free -- they take up the time in which a finished line workgroup would wait for the slowest one -- and they pull their
+    // row groups from counters (fw_rows_role), so a CU that comes free early walks more of the angle.  Only speed depends on
+    // that order: an x workgroup shares nothing with the others but the read-only level volume, waits for nobody, has a
+    // table layout (set.xRS), an accumulator column (set.xslot) and counters (those of role index `count`) of its own, and
+    // owns no unit of the pack.  One without a row group of its own has none to pull either: it leaves the LDS alone.
+    const int bx = (int)blockIdx.x - set.first_block[set.count], nblocks = set.first_block[set.count + 1] - set.first_block[set.count];
+    if (flags[0] != 0 || (long long)bx * set.xwaves >= fw_row_groups(set.nrows)) return;
+    if ((unsigned)(size_t)((lds_u32 *)lds) != 0u) {
+      if (threadIdx.x == 0) atomicExch(flags + 2, 1);
+      return;
+    }
+    const HistLayout hx = hist_layout(true, true, true, Ng, set.xRS);
+    for (int i = threadIdx.x; i < hx.words + Ng + 1; i += blockDim.x) lds[i] = 0;
+    __syncthreads();
+    FwTab T;
+    T.init(hx, Nr, glrlm_acc + (size_t)set.xslot * Ng * Nr);
+    const int wave = (int)(threadIdx.x >> 6);
+    if (wave < set.xwaves) {
+      int *heads = work + PRAD_FW_WORK_STRIDE * PRAD_FW_DOMAINS * set.count;
+      // Always the checked form (LONG), also where the table holds every run length (xRS >= Nr: the rows kernel then takes the
+      // plain form).  It is correct for any table -- the plain form is the checked one without the margin ballot per 16 steps,
+      // which short rows now pay -- and it keeps the role at two copies of the row walk per kernel instead of four: the role's
+      // code sits in all 24 instantiations of this kernel.
+      if (flags[3] != 0) fw_rows_role<true, true>(hx, T, lds, L, set.nrows, set.NX, set.pitch, bx, nblocks, wave, set.xwaves, heads, set.xgpd);
+      else fw_rows_role<true, false>(hx, T, lds, L, set.nrows, set.NX, set.pitch, bx, nblocks, wave, set.xwaves, heads, set.xgpd);
+    }
+    flush_block_hist<true, true, true>(lds + Ng + 1, hx, Nr, set.xslot, glcm_acc, glrlm_acc);
+    return;
+  }
   int role = 0;
   while (role + 1 < set.count && (int)blockIdx.x >= set.first_block[role + 1]) role++;
   const int bx = (int)blockIdx.x - set.first_block[role], nblocks = set.first_block[role + 1] - set.first_block[role];
-  const int wpb = (int)(blockDim.x >> 6);
   const long long pw = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * wpb + (threadIdx.x >> 6)));
-  PackWave pk(pj, pw, (long long)gridDim.x * wpb);
+  PackWave pk(pj, pw, (long long)set.first_block[set.count] * wpb);   // (the pack's units are dealt over the line roles' waves)
   FwClock clk;
   clk.start();
 #ifdef PRAD_FW_SETPRIO   // experiment: issue priority over co-resident waves of another launch

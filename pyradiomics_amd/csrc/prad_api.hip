@@ -278,6 +278,7 @@ struct SweepPlan {
   size_t lds_fw = 0;
   int RSfw_rows = 0;           // length slots of the rows role's table (it shares the LDS with 16 staging tiles)
   size_t lds_fw_rows = 0;      // the x angle as a launch of its own (sweep_fw_rows_kernel)
+  int fw_xblocks = 0;          // > 0: the x angle is the trailing role of the fixed-window launch, this many workgroups behind fw_blocks
   // two-table fixed-window kernel (kernels_sweepfw2.h): 45+ grey levels
   bool fw2 = false;
   int RS2 = 0;                 // run-length slots per level row
@@ -516,10 +517,12 @@ SweepPlan plan_sweep(const Call &k, int Ng, int Nr, bool want_glcm, bool want_gl
       p.RSfw_rows = rs;
       p.lds_fw_rows = ((fw_lds_bytes(hist_layout(true, true, true, Ng, rs)) + 15) & ~(size_t)15) + tiles;
     }
+    int nroles_x = 0;
     {
       // Roles of the one launch (kernels_sweepfw.h sweep_fw_kernel): one per line angle, one 16-wave workgroup per CU over
       // all of them (1-D grid; the remainder of the division goes to the first roles)
       const int nroles = p.lines.count;
+      nroles_x = nroles;
       int total = cu_count();
       if (const char *e = getenv("PRAD_FW_BLOCKS")) total = std::max(nroles, atoi(e));   // tuning override: workgroups of the launch
       if (const char *e = getenv("PRAD_FW_THREADS")) p.fw_threads = std::max(64, std::min(1024, atoi(e) & ~63));   // ... and their size
@@ -545,6 +548,29 @@ SweepPlan plan_sweep(const Call &k, int Ng, int Nr, bool want_glcm, bool want_gl
       for (int r = 0; r < nroles; r++) p.fwset.first_block[r + 1] = p.fwset.first_block[r] + total / nroles + bonus[r];
       for (int r = nroles + 1; r < PRAD_MAX_SWEEP + 1; r++) p.fwset.first_block[r] = p.fwset.first_block[nroles];
       p.fw_blocks = p.fwset.first_block[nroles];
+    }
+    // The x angle of a fused-table GLCM + GLRLM call: trailing workgroups of the same launch (kernels_sweepfw.h sweep_fw_kernel),
+    // as many as its own launch would have, shaped like that launch's (fw_rows_threads / 64 walking waves, one staging tile each,
+    // behind a table of RSfw_rows length slots).  PRAD_FW_XROLE=0: the two launches, as before.
+    p.fwset.xslot = -1;
+    p.fwset.xRS = 0;
+    p.fwset.xwaves = 0;
+    p.fwset.xgpd = 1;
+    {
+      const char *e = getenv("PRAD_FW_XROLE");
+      if (p.fw && p.fused && p.row_slot >= 0 && p.fw_threads == 1024 && !(e && atoi(e) == 0)) {
+        const long long groups = fw_row_groups((long long)p.Nz * p.Ny);
+        const int wpb = p.fw_rows_threads / 64;
+        long long xb = std::min<long long>((groups + wpb - 1) / wpb, (long long)cu_count());
+        if (const char *b = getenv("PRAD_FW_XBLOCKS")) xb = std::min<long long>(atoll(b), 4096);   // tuning override
+        p.fw_xblocks = (int)std::max<long long>(1, xb);
+        p.fwset.first_block[nroles_x + 1] = p.fw_blocks + p.fw_xblocks;
+        p.fwset.xslot = p.row_slot;
+        p.fwset.xRS = p.RSfw_rows;
+        p.fwset.xwaves = wpb;
+        p.fwset.xgpd = 1;   // (groups per pull: more only coarsens the hand-out, see fw_rows_role)
+        if (const char *g = getenv("PRAD_FW_XGPD")) p.fwset.xgpd = std::max(1, std::min(64, atoi(g)));   // tuning override
+      }
     }
     int per_wave = 6;
     if (const char *e = getenv("PRAD_FW_PER_WAVE")) per_wave = std::max(1, atoi(e));
@@ -624,9 +650,11 @@ int launch_lines(Call &k, const SweepPlan &p, const uint8_t *levels, int Ng, int
 template <bool LNG, int K, bool HASPAD, bool PACK>
 int launch_fw_kpp(Call &k, const SweepPlan &p, const PackJob &pj, const uint8_t *levels, const uint8_t *rowzero, int Ng, int Nr,
                   u32 *glcm_acc, u32 *glrlm_acc, int *multi, int *flags_d) {
+  // one block size and one LDS size per grid: the x angle's trailing workgroups (table + staging tiles) may need more than the walk's
+  const size_t lds = p.fw_xblocks > 0 ? std::max(p.lds_fw, p.lds_fw_rows) : p.lds_fw;
   PRAD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_fw_kernel<LNG, K, HASPAD, PACK>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_fw));
-  hipLaunchKernelGGL((sweep_fw_kernel<LNG, K, HASPAD, PACK>), dim3(p.fw_blocks), dim3(p.fw_threads), p.lds_fw, k.s, p.fwset, pj,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((sweep_fw_kernel<LNG, K, HASPAD, PACK>), dim3(p.fw_blocks + p.fw_xblocks), dim3(p.fw_threads), lds, k.s, p.fwset, pj,
                      levels, rowzero, Ng, Nr, p.RSfw, glcm_acc, glrlm_acc, multi + 2 * PRAD_MAX_SWEEP + PRAD_FW_WORK_STRIDE, flags_d);
   return check_launch("sweep_fw_kernel");
 }
@@ -690,7 +718,7 @@ int launch_fw2(Call &k, const SweepPlan &p, const PackJob &pj, const uint8_t *le
 
 template <bool LNG>
 int launch_fw_rows(Call &k, const SweepPlan &p, const uint8_t *levels, int Ng, int Nr, u32 *glcm_acc, u32 *glrlm_acc, int *flags_d) {
-  const long long nrows = (long long)p.Nz * p.Ny, groups = nrows >= 4096 ? ((nrows + 511) / 512) * 8 : (nrows + 63) / 64;
+  const long long nrows = (long long)p.Nz * p.Ny, groups = fw_row_groups(nrows);
   const int wpb = p.fw_rows_threads / 64;
   const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((groups + wpb - 1) / wpb, (long long)cu_count()));
   PRAD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_fw_rows_kernel<LNG>),
@@ -871,39 +899,11 @@ template <bool G, bool R, bool F>
 int launch_sweeps(Call &k, const VolState &v, const PackJob &pj) {
   const SweepPlan &p = v.p;
   if (p.lines.count > 0 && p.fw && G && R && F) {
-    // PRAD_ROWS_STREAM=1 (round-6 experiment): the x angle's launch on a side stream, concurrent with the walk launch -- it only
-    // needs the packed levels, writes its own accumulator slots, and its 8-wave workgroups could take the CUs the walk's
-    // workgroups leave in the launch's last 10 % (roles finish up to 8 % apart)
-    static const bool rows_side = getenv("PRAD_ROWS_STREAM") != nullptr;
-    if (rows_side && p.row_slot >= 0) {
-      static thread_local hipStream_t side = nullptr;
-      static thread_local hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (!side) {
-        int lo = 0, hi = 0;
-        PRAD_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));      // (lo = the numerically largest = least urgent)
-        PRAD_HIP(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, getenv("PRAD_ROWS_STREAM_PRIO") ? atoi(getenv("PRAD_ROWS_STREAM_PRIO")) : lo));
-        PRAD_HIP(hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-        PRAD_HIP(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-      }
-      PRAD_HIP(hipEventRecord(e0, k.s));
-      PRAD_HIP(hipStreamWaitEvent(side, e0, 0));
-      {
-        Timed t(*k.c, "sweep", k.s);
-        PRAD_TRY(launch_fw(k, p, pj, v.levels, v.rowzero, v.Ng, v.Nr, v.glcm_acc, v.glrlm_acc, v.multi, v.flags_d));
-      }
-      Call k2 = k;
-      k2.s = side;
-      if (p.RSfw_rows < v.Nr) PRAD_TRY(launch_fw_rows<true>(k2, p, v.levels, v.Ng, v.Nr, v.glcm_acc, v.glrlm_acc, v.flags_d));
-      else PRAD_TRY(launch_fw_rows<false>(k2, p, v.levels, v.Ng, v.Nr, v.glcm_acc, v.glrlm_acc, v.flags_d));
-      PRAD_HIP(hipEventRecord(e1, side));
-      PRAD_HIP(hipStreamWaitEvent(k.s, e1, 0));
-      return PRAD_OK;
-    }
     {
       Timed t(*k.c, "sweep", k.s);
       PRAD_TRY(launch_fw(k, p, pj, v.levels, v.rowzero, v.Ng, v.Nr, v.glcm_acc, v.glrlm_acc, v.multi, v.flags_d));
     }
-    if (p.row_slot >= 0) {
+    if (p.row_slot >= 0 && p.fw_xblocks == 0) {   // (else the x angle ran as the trailing role of that launch)
       Timed t(*k.c, "rows", k.s);
       if (p.RSfw_rows < v.Nr) PRAD_TRY(launch_fw_rows<true>(k, p, v.levels, v.Ng, v.Nr, v.glcm_acc, v.glrlm_acc, v.flags_d));
       else PRAD_TRY(launch_fw_rows<false>(k, p, v.levels, v.Ng, v.Nr, v.glcm_acc, v.glrlm_acc, v.flags_d));
