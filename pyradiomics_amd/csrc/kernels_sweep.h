@@ -913,4 +913,172 @@ __global__ void finalize_glrlm_kernel(const u32 *__restrict__ acc, const int *__
   out[idx] = (r == 0 && !multi[a]) ? 0.0 : (double)acc[(size_t)a * Ng * Nr + gr];
 }
 
+// ---- the three finalize launches of a GLCM + GLRLM volume (diagonal from the runs) as ONE launch -----------------------
+// finalize_glcm_diag_kernel -> multi_check_kernel -> finalize_glrlm_kernel are three launches because of ONE dependency:
+// column "run length 1" of the GLRLM of angle a needs multi[a] (and, under SKIP1, the restored counts).  Here everything
+// that depends on multi[a] belongs to ONE workgroup per angle, so no workgroup reads what another one of the launch wrote:
+//   blockIdx.x <  Na             angle workgroup a: diagonal, SKIP1 restore, multi[a] (cheap verdict, else the exact test),
+//                                column r == 0 of the GLRLM output
+//   the next nbR workgroups      GLRLM conversion without column r == 0
+//   the rest                     off-diagonal GLCM conversion
+// The angle workgroups come first in the grid: they are the longest.
+
+// exact "some line of the angle holds >= 2 masked voxels", by all threads of one workgroup: a lane per line START (a voxel
+// whose predecessor lies outside the box), enumerated face by face -- the plane z == z0 when dz != 0, then y == y0 without
+// that plane, then x == x0 without both -- so that nobody scans the voxels inside.  Steps go in batches of 8 loads in flight.
+template <typename T>
+__device__ void lines_hold_two(const T *__restrict__ L, int Nz, int Ny, int Nx, int pitch, int dz, int dy, int dx,
+                               volatile int *hit) {
+  const int z0 = dz > 0 ? 0 : Nz - 1, y0 = dy > 0 ? 0 : Ny - 1, x0 = dx > 0 ? 0 : Nx - 1;
+  const long long NzR = Nz - (dz != 0), NyR = Ny - (dy != 0);
+  const long long SZ = dz ? (long long)Ny * Nx : 0, SY = dy ? NzR * Nx : 0, SX = dx ? NzR * NyR : 0;
+  const long long dp = ((long long)dz * Ny + dy) * pitch + dx;
+  for (long long s = threadIdx.x; s < SZ + SY + SX; s += blockDim.x) {
+    if (*hit) return;
+    int z, y, x;
+    if (s < SZ) {
+      z = z0;
+      y = (int)(s / Nx);
+      x = (int)(s - (long long)y * Nx);
+    } else if (s < SZ + SY) {
+      const long long t = s - SZ;
+      const int zr = (int)(t / Nx);
+      x = (int)(t - (long long)zr * Nx);
+      y = y0;
+      z = zr + (dz > 0);
+    } else {
+      const long long t = s - SZ - SY;
+      const int zr = (int)(t / NyR);
+      x = x0;
+      y = (int)(t - zr * NyR) + (dy > 0);
+      z = zr + (dz > 0);
+    }
+    int len = 0x7fffffff;   // voxels of the line inside the box
+    if (dz) len = min(len, dz > 0 ? Nz - z : z + 1);
+    if (dy) len = min(len, dy > 0 ? Ny - y : y + 1);
+    if (dx) len = min(len, dx > 0 ? Nx - x : x + 1);
+    long long p = ((long long)z * Ny + y) * pitch + x;
+    int cnt = 0;
+    for (int k = 0; k < len; k += 8, p += 8 * dp) {
+#pragma unroll
+      for (int u = 0; u < 8; u++)
+        if (k + u < len) cnt += L[p + u * dp] != 0;
+      if (cnt > 1) {
+        *hit = 1;
+        return;
+      }
+    }
+  }
+}
+
+// T / pitch: as multi_check_kernel.  flags / sticky (deferred calls, sticky may be null): the levels verdict of the call
+template <typename T>
+__global__ void __launch_bounds__(1024) finalize_volume_kernel(AngleSet A, const T *__restrict__ L, int Nz, int Ny, int Nx, int pitch,
+                                                               const u32 *__restrict__ glcm_acc, u32 *glrlm_acc,
+                                                               int Ng, int Nr, int Na, int nbR, double *__restrict__ glcm_out,
+                                                               double *__restrict__ glrlm_out, int *__restrict__ multi,
+                                                               int restore_from, const int *__restrict__ flags,
+                                                               int *__restrict__ sticky) {
+  // per level i of the angle (Ng <= 255): sum (len-1) * runs, runs of length >= 2, voxels N_i (SKIP1), GLRLM_a[i][1]
+  __shared__ u64 s_pairs[256], s_longer[256], s_nvox[256];
+  __shared__ u32 s_run1[256];
+  __shared__ int s_found, s_hit;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (b >= Na + nbR) {   // off-diagonal GLCM counts -> float64
+    const long long idx = (long long)(b - Na - nbR) * blockDim.x + tid;
+    if (idx >= (long long)Ng * Ng * Na) return;
+    const int a = (int)(idx % Na);
+    const long long ij = idx / Na;
+    const int i = (int)(ij / Ng), j = (int)(ij - (long long)i * Ng);
+    if (i == j) return;  // the diagonal comes from the runs (angle workgroups)
+    glcm_out[idx] = (double)glcm_acc[(size_t)a * Ng * Ng + ij];
+    return;
+  }
+  if (b >= Na) {         // run counts -> float64, all columns but r == 0 (angle workgroups)
+    const long long idx = (long long)(b - Na) * blockDim.x + tid;
+    if (idx >= (long long)Ng * Nr * Na) return;
+    const int a = (int)(idx % Na);
+    const long long gr = idx / Na;
+    if (gr % Nr == 0) return;
+    glrlm_out[idx] = (double)glrlm_acc[(size_t)a * Ng * Nr + gr];
+    return;
+  }
+  // Angle workgroup.  The tables are read FLAT, up to 40 independent loads per thread in flight (a wave per level with a lane per
+  // 64th length is a chain of dependent round trips: 8 per row at Nr = 512, once per level the wave owns); the few non-zero
+  // counts go to per-level LDS sums.  Integer sums: the order does not matter.
+  const int a = b, lane = tid & 63, nt = (int)blockDim.x;
+  const int nrun = Ng * Nr, npair = Ng * Ng;   // (the host keeps Ng * Nr below 2^31)
+  const bool restore = restore_from >= 0 && a != restore_from;
+  // (a round of loads costs a memory round trip whatever its size: the first pair rows go out in front of the barrier, both run
+  //  tables together behind it)
+  const u32 *gtab = glcm_acc + (size_t)a * npair;
+  u32 g[8];
+#pragma unroll
+  for (int u = 0; u < 8; u++) g[u] = (u * nt + tid < npair) ? gtab[u * nt + tid] : 0u;
+  for (int i = tid; i < 256; i += nt) {
+    s_pairs[i] = 0;
+    s_longer[i] = 0;
+    s_nvox[i] = 0;
+    s_run1[i] = 0;
+  }
+  if (tid == 0) {
+    s_found = multi[a] != 0;   // (a rows kernel of an earlier launch may have set it)
+    s_hit = 0;
+    if (sticky && a == 0 && (flags[0] || flags[2])) sticky[0] = 1;
+  }
+  __syncthreads();
+  int found = 0;
+  u32 *tab = glrlm_acc + (size_t)a * nrun;
+  const u32 *xtab = glrlm_acc + (size_t)(restore ? restore_from : a) * nrun;   // N_i comes from the x angle's complete run table
+  for (int e0 = 0; e0 < nrun; e0 += 16 * nt) {
+    u32 v[16], x[16];
+#pragma unroll
+    for (int u = 0; u < 16; u++) v[u] = (e0 + u * nt + tid < nrun) ? tab[e0 + u * nt + tid] : 0u;
+#pragma unroll
+    for (int u = 0; u < 16; u++) x[u] = (restore && e0 + u * nt + tid < nrun) ? xtab[e0 + u * nt + tid] : 0u;
+#pragma unroll
+    for (int u = 0; u < 16; u++)
+      if (v[u] | x[u]) {
+        const int e = e0 + u * nt + tid, i = e / Nr, r = e - i * Nr;
+        if (x[u]) atomicAdd(&s_nvox[i], (u64)(r + 1) * x[u]);
+        if (v[u] && r == 0) {
+          s_run1[i] = v[u];
+        } else if (v[u]) {   // a run longer than 1: the angle has a line of two voxels
+          found = 1;
+          atomicAdd(&s_pairs[i], (u64)r * v[u]);
+          atomicAdd(&s_longer[i], (u64)v[u]);
+        }
+      }
+  }
+  // a non-empty off-diagonal row: two adjacent voxels of different levels
+#pragma unroll
+  for (int u = 0; u < 8; u++) found |= (g[u] != 0);
+  for (int e0 = 8 * nt; e0 < npair; e0 += 8 * nt) {
+#pragma unroll
+    for (int u = 0; u < 8; u++) g[u] = (e0 + u * nt + tid < npair) ? gtab[e0 + u * nt + tid] : 0u;
+#pragma unroll
+    for (int u = 0; u < 8; u++) found |= (g[u] != 0);
+  }
+  if (__ballot(found) != 0 && lane == 0) s_found = 1;
+  __syncthreads();
+  int m = s_found;   // uniform: nobody writes s_found behind the barrier
+  if (!m) {   // every masked voxel isolated along the angle (rare): the exact test of multi_check_kernel
+    lines_hold_two<T>(L, Nz, Ny, Nx, pitch, A.off[a][0], A.off[a][1], A.off[a][2], &s_hit);
+    __syncthreads();
+    m = s_hit;
+  }
+  for (int i = tid; i < Ng; i += nt) {
+    const u64 pairs = s_pairs[i];
+    glcm_out[((size_t)i * Ng + i) * Na + a] = (double)pairs;   // GLCM diagonal: the pairs inside the runs
+    u32 run1 = s_run1[i];
+    if (restore) {   // SKIP1: GLRLM_a[i][1] = N_i - sum_{len >= 2} len * GLRLM_a[i][len]
+      run1 = (u32)(s_nvox[i] - (pairs + s_longer[i]));
+      tab[(size_t)i * Nr] = run1;   // the accumulators hold what the three launches left in them
+    }
+    // cmatrices.c:524-534: an angle without any line of >= 2 masked voxels loses its run-length-1 column
+    glrlm_out[(size_t)i * Nr * Na + a] = m ? (double)run1 : 0.0;
+  }
+  if (tid == 0) multi[a] = m;
+}
+
 }  // namespace prad

@@ -967,6 +967,13 @@ int latch_neigh(Context &c, Call &k) {
   return check_launch("latch_any_flag_kernel");
 }
 
+// PRAD_FINALIZE_ONE=0: the three finalize launches of a GLCM + GLRLM volume instead of finalize_volume_kernel (A/B, and the
+// checker of that kernel); read on every call so that a test can flip it
+bool finalize_one() {
+  const char *e = getenv("PRAD_FINALIZE_ONE");
+  return !(e && atoi(e) == 0 && e[0] != '\0');
+}
+
 // u32 accumulators -> float64 matrices in the reference layouts; `sticky` (deferred calls): latch the levels verdict
 int vol_finalize(Call &k, const VolState &v, int *sticky) {
   Context &c = *k.c;
@@ -981,6 +988,22 @@ int vol_finalize(Call &k, const VolState &v, int *sticky) {
     // matrices and the x angle's complete run table (plans with skip1 always carry them: plan_sweep clears the flag otherwise)
     if (p.fw2 && p.skip1 && p.lines.count > 0 && !(glcm && glrlm && p.row_slot >= 0))
       return fail(PRAD_E_UNSUPPORTED, "sweep plan derives runs of length 1 but the call cannot restore them");
+    if (glcm && glrlm && runs_diag && finalize_one() && (long long)Ng * Nr < (1LL << 30)) {
+      // ONE launch (finalize_volume_kernel): Na angle workgroups, then the two element-wise conversions
+      const int nbR = (int)blocks_for((long long)Ng * Nr * Na, 1024), nbG = (int)blocks_for((long long)Ng * Ng * Na, 1024);
+      const int restore_from = (p.fw2 && p.skip1 && p.lines.count > 0) ? p.row_slot : -1;
+      if (v.levels)
+        hipLaunchKernelGGL(finalize_volume_kernel<uint8_t>, dim3(Na + nbR + nbG), dim3(1024), 0, k.s, p.aset, (const uint8_t *)v.levels,
+                           p.Nz, p.Ny, p.Nx, p.pitch, v.glcm_acc, v.glrlm_acc, Ng, Nr, Na, nbR, glcm, glrlm, v.multi,
+                           restore_from, (const int *)v.flags_d, sticky);
+      else
+        hipLaunchKernelGGL(finalize_volume_kernel<unsigned short>, dim3(Na + nbR + nbG), dim3(1024), 0, k.s, p.aset,
+                           reinterpret_cast<const unsigned short *>(v.levels16), p.Nz, p.Ny, p.Nx, p.pitch16 / 2, v.glcm_acc,
+                           v.glrlm_acc, Ng, Nr, Na, nbR, glcm, glrlm, v.multi, restore_from, (const int *)v.flags_d, sticky);
+      PRAD_TRY(check_launch("finalize_volume_kernel"));
+      latched = sticky != nullptr;
+      glcm = glrlm = nullptr;   // both matrices are complete
+    }
     if (glcm && glrlm && runs_diag) {
       const int nb1 = (int)blocks_for((long long)Ng * Ng * Na), nb2 = (Ng * Na + 3) / 4;
       hipLaunchKernelGGL(finalize_glcm_diag_kernel, dim3(nb1 + nb2), dim3(256), 0, k.s, v.glcm_acc, v.glrlm_acc, Ng, Nr, Na, nb1,
