@@ -376,27 +376,97 @@ def _one_voxel_matrices(level, masked, Ng, fam):
     return out
 
 
-def _looped_matrices(image, mask, Ng, families, dist, alpha, shapes_b):
-    """one ROI through the single calls (host arrays or device tensors) -> ({family: numpy matrix}, status)"""
-    try:
-        if int(np.prod(image.shape)) == 1:
-            lv, mk = int(image.reshape(-1)[0]), bool(mask.reshape(-1)[0])
-            return {f: _one_voxel_matrices(lv, mk, Ng, f) for f in families}, _lib.PRAD_OK
-        out = {}
-        if "glcm" in families:
-            out["glcm"] = calculate_glcm(image, mask, dist, Ng, False, 0)[0][0]
-        if "glrlm" in families:
-            out["glrlm"] = calculate_glrlm(image, mask, Ng, int(max(image.shape)), False, 0)[0][0]
-        if "gldm" in families:
-            out["gldm"] = calculate_gldm(image, mask, dist, Ng, alpha, False, 0)[0]
-        if "ngtdm" in families:
-            out["ngtdm"] = calculate_ngtdm(image, mask, dist, Ng, False, 0)[0]
-        return out, _lib.PRAD_OK
-    except IndexError:          # a masked level outside [1, Ng]: as the native route, the matrices of an empty mask
-        out = {f: np.zeros(shapes_b[f]) for f in families}
-        if "ngtdm" in out:
-            out["ngtdm"][:, 2] = np.arange(1, Ng + 1)
-        return out, _lib.PRAD_INDEX_ERROR
+def _looped_matrices(rois, Ng, families, shapes, single, wrap=lambda a: a):
+    """The looped route: every ROI of `rois`, pairs (image, mask), through the single calls -> ({family: [B matrices]}, status).
+    single[f](image, mask) is the call of family f; wrap makes the caller's kind of result of a numpy matrix (the device route
+    puts it where its other results are)."""
+    _set_batch_route("looped")
+    mats, status = {f: [] for f in families}, []
+    for b, (image, mask) in enumerate(rois):
+        try:
+            if int(np.prod(image.shape)) == 1:      # no angle exists: the single calls refuse the box
+                lv, mk = int(image.reshape(-1)[0]), bool(mask.reshape(-1)[0])
+                one = {f: wrap(_one_voxel_matrices(lv, mk, Ng, f)) for f in families}
+            else:
+                one = {f: single[f](image, mask) for f in BATCH_FAMILIES if f in families}
+            status.append(_lib.PRAD_OK)
+        except IndexError:          # a masked level outside [1, Ng]: as the native route, the matrices of an empty mask
+            one = {f: np.zeros(shapes[f][b]) for f in families}
+            if "ngtdm" in one:
+                one["ngtdm"][:, 2] = np.arange(1, Ng + 1)
+            one = {f: wrap(m) for f, m in one.items()}
+            status.append(_lib.PRAD_INDEX_ERROR)
+        for f in families:
+            mats[f].append(one[f])
+    return mats, status
+
+
+def _one_voxel_glszm(level, masked, Ng, compact, wrap):
+    """the GLSZM of a 1 x 1 x 1 box (no angle exists: the single call refuses it), dense or as calculate_glszm_compact"""
+    if masked and not 1 <= level <= Ng:
+        raise IndexError("level outside [1, Ng]")
+    P = np.zeros((Ng, 1))
+    if masked:
+        P[level - 1, 0] = 1
+    if not compact:
+        return wrap(P)
+    return (wrap(P), np.ones(1, dtype=np.intc)) if masked else (wrap(P[:, :0]), np.zeros(0, dtype=np.intc))
+
+
+def _looped_glszm(rois, Ng, compact, single, wrap=lambda a: a):
+    """every ROI of `rois`, pairs (image, mask), through the single call -> (results, status): single(image, mask, Ns) is that
+    call, dense or compact as asked for; wrap as in _looped_matrices"""
+    results, status = [], []
+    for image, mask in rois:
+        try:
+            if int(np.prod(image.shape)) == 1:
+                results.append(_one_voxel_glszm(int(image.reshape(-1)[0]), bool(mask.reshape(-1)[0]), Ng, compact, wrap))
+            else:
+                results.append(single(image, mask, max(1, int(mask.sum()))))
+            status.append(_lib.PRAD_OK)
+        except IndexError:          # as the native route: status 0, the result of an empty mask
+            results.append(_one_voxel_glszm(0, False, Ng, compact, wrap))
+            status.append(_lib.PRAD_INDEX_ERROR)
+    return results, status
+
+
+def _host_roi_batch(images, masks, noun, raw=False, loops=False):
+    """Lists of host arrays -> (images, masks, sizes intc [B, 3], upload).  Levels and bool masks are parsed as the single calls
+    parse them (_parse_arrays); raw=True: intensity boxes, which keep their dtype where it is one of the four the kernels read
+    and all share it (float64 otherwise), and masks of any dtype, non-zero = ROI.  upload() -> (flat data tensor, flat uint8 mask
+    tensor) on the current device, ONE copy each.  loops=True: the caller can loop the single calls, so an empty list is fine
+    and so is a machine without a device (upload is None there); otherwise both raise.  `noun` names the batch in the messages."""
+    if len(images) != len(masks):
+        raise ValueError("images and masks differ in number")
+    if raw:
+        imgs = [np.ascontiguousarray(np.asarray(i)) for i in images]
+        msks = [np.ascontiguousarray(np.asarray(m)) for m in masks]
+    else:
+        parsed = [_parse_arrays(i, m) for i, m in zip(images, masks)]
+        imgs, msks = [p[0] for p in parsed], [p[1] for p in parsed]
+    if not (imgs or loops) or any(i.ndim != 3 or i.shape != m.shape for i, m in zip(imgs, msks)):
+        raise ValueError("the batched %s %s %s3-D ROIs%s" % (noun, "takes" if noun == "GLSZM" else "take",
+                                                             "" if loops else "a non-empty list of ",
+                                                             " with masks of the same shape" if raw else ""))
+    sizes = np.array([i.shape for i in imgs], dtype=np.intc).reshape(-1, 3)
+    if _lib.load().prad_device_count() < 1:
+        if not loops:
+            raise RuntimeError("no HIP device: the batched %s are evaluated on the device" % noun)
+        return imgs, msks, sizes, None
+
+    def upload():
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        dt = np.dtype(np.intc)
+        if raw:
+            dt = imgs[0].dtype if (imgs[0].dtype in (np.float32, np.float64, np.int32, np.int16)
+                                   and all(i.dtype == imgs[0].dtype for i in imgs)) else np.dtype(np.float64)
+        if not imgs:
+            return torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.uint8, device=dev)
+        flat_i = torch.from_numpy(np.concatenate([i.ravel().astype(dt, copy=False) for i in imgs])).to(dev)
+        flat_m = torch.from_numpy(np.concatenate([(m.ravel() != 0 if raw else m.ravel()).view(np.uint8) for m in msks])).to(dev)
+        return flat_i, flat_m
+    return imgs, msks, sizes, upload
 
 
 def calculate_matrices_batch(images, masks, Ng, families=BATCH_FAMILIES, distances=(1,), gldm_a=0):
@@ -408,31 +478,19 @@ def calculate_matrices_batch(images, masks, Ng, families=BATCH_FAMILIES, distanc
     tells which.  GLSZM: calculate_glszm_batch."""
     families = tuple(families)
     batch_family_bits(families)
-    if len(images) != len(masks):
-        raise ValueError("images and masks differ in number")
-    parsed = [_parse_arrays(i, m) for i, m in zip(images, masks)]
-    if any(p[0].ndim != 3 for p in parsed):
-        raise ValueError("the batched matrices take 3-D ROIs")
+    imgs, msks, sizes, upload = _host_roi_batch(images, masks, "matrices", loops=True)
     dist = [int(d) for d in np.asarray(distances).ravel()]
-    sizes = np.array([p[2] for p in parsed], dtype=np.intc).reshape(-1, 3)
     covered, offsets, Na = batch_plan(sizes, Ng, families, dist)
     shapes = batch_shapes(sizes, int(Ng), Na)
-    B = len(parsed)
-    if not covered or _lib.load().prad_device_count() < 1:
-        _set_batch_route("looped")
-        mats, status = {f: [] for f in families}, []
-        for b, (img, msk, _) in enumerate(parsed):
-            one, st = _looped_matrices(img, msk, int(Ng), families, dist, int(gldm_a), {f: shapes[f][b] for f in families})
-            for f in families:
-                mats[f].append(one[f])
-            status.append(st)
-        return mats, status
-    import torch
-    engine = _engine()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    flat_l = torch.from_numpy(np.concatenate([p[0].ravel() for p in parsed])).to(dev) if B else torch.empty(0, dtype=torch.int32, device=dev)
-    flat_m = torch.from_numpy(np.concatenate([p[1].ravel().view(np.uint8) for p in parsed])).to(dev) if B else torch.empty(0, dtype=torch.uint8, device=dev)
-    flat, status = engine.texture_matrices_batch_flat(flat_l, flat_m, sizes, int(Ng), families, dist, int(gldm_a))
+    B = len(imgs)
+    if not covered or upload is None:
+        single = {"glcm": lambda i, m: calculate_glcm(i, m, dist, int(Ng), False, 0)[0][0],
+                  "glrlm": lambda i, m: calculate_glrlm(i, m, int(Ng), int(max(i.shape)), False, 0)[0][0],
+                  "gldm": lambda i, m: calculate_gldm(i, m, dist, int(Ng), int(gldm_a), False, 0)[0],
+                  "ngtdm": lambda i, m: calculate_ngtdm(i, m, dist, int(Ng), False, 0)[0]}
+        return _looped_matrices(zip(imgs, msks), int(Ng), families, shapes, single)
+    flat_l, flat_m = upload()
+    flat, status = _engine().texture_matrices_batch_flat(flat_l, flat_m, sizes, int(Ng), families, dist, int(gldm_a))
     mats = {}
     for f in families:
         host = flat[f].cpu().numpy()
@@ -448,43 +506,17 @@ def calculate_glszm_batch(images, masks, Ng, compact=False):
     max(maxRegion, 1)] of calculate_glszm (without its leading axis); compact=True: (P [Ng, k], sizes int32 [k]) as
     calculate_glszm_compact.  With no device visible the single calls are looped ROI by ROI (and raise as they do without a
     device); last_batch_route() tells which route ran."""
-    if len(images) != len(masks):
-        raise ValueError("images and masks differ in number")
-    parsed = [_parse_arrays(i, m) for i, m in zip(images, masks)]
-    if any(p[0].ndim != 3 for p in parsed):
-        raise ValueError("the batched GLSZM takes 3-D ROIs")
+    imgs, msks, sizes, upload = _host_roi_batch(images, masks, "GLSZM", loops=True)
     Ng = int(Ng)
-    B = len(parsed)
-    if _lib.load().prad_device_count() < 1:
+    if upload is None:
+        def single(img, msk, Ns):
+            P = calculate_glszm(img, msk, Ng, Ns, False, 0)[0]
+            cols = np.flatnonzero(P.any(0))
+            return (np.ascontiguousarray(P[:, cols]), (cols + 1).astype(np.intc)) if compact else P
         _set_batch_route("looped")
-        results, status = [], []
-        for img, msk, _ in parsed:
-            try:
-                if img.size == 1:       # no angle exists: the single call refuses the box
-                    lv, mk = int(img.reshape(-1)[0]), bool(msk.reshape(-1)[0])
-                    if mk and not 1 <= lv <= Ng:
-                        raise IndexError("level outside [1, Ng]")
-                    P = np.zeros((Ng, 1))
-                    if mk:
-                        P[lv - 1, 0] = 1
-                else:
-                    P = calculate_glszm(img, msk, Ng, max(1, int(msk.sum())), False, 0)[0]
-                st = _lib.PRAD_OK
-            except IndexError:
-                P, st = np.zeros((Ng, 1)), _lib.PRAD_INDEX_ERROR
-            if compact:
-                cols = np.flatnonzero(P.any(0))
-                P = (np.ascontiguousarray(P[:, cols]), (cols + 1).astype(np.intc))
-            results.append(P)
-            status.append(st)
-        return results, status
-    import torch
-    engine = _engine()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    sizes = np.array([p[2] for p in parsed], dtype=np.intc).reshape(-1, 3)
-    flat_l = torch.from_numpy(np.concatenate([p[0].ravel() for p in parsed])).to(dev) if B else torch.empty(0, dtype=torch.int32, device=dev)
-    flat_m = torch.from_numpy(np.concatenate([p[1].ravel().view(np.uint8) for p in parsed])).to(dev) if B else torch.empty(0, dtype=torch.uint8, device=dev)
-    results, status = engine.glszm_batch(flat_l, flat_m, sizes, Ng, compact=compact)
+        return _looped_glszm(zip(imgs, msks), Ng, compact, single)
+    flat_l, flat_m = upload()
+    results, status = _engine().glszm_batch(flat_l, flat_m, sizes, Ng, compact=compact)
     if compact:
         return [(P.cpu().numpy(), s) for P, s in results], status
     return [P.cpu().numpy() for P in results], status
@@ -501,22 +533,10 @@ def calculate_features_batch(images, masks, Ng, classes=("glcm", "glrlm", "glszm
     calls and the batched formulas of engine.texture_features_batch.  -> {class: {feature name: float64 [B]}}; a ROI with a masked level
     outside [1, Ng] (the single calls' IndexError) has NaN everywhere, the others are not affected.  The names are those of the feature classes
     (VOXEL_*_FEATURES, plus "MCC").  Needs a device (RuntimeError without one); last_batch_route() tells which route ran."""
-    if len(images) != len(masks):
-        raise ValueError("images and masks differ in number")
-    parsed = [_parse_arrays(i, m) for i, m in zip(images, masks)]
-    if not parsed or any(p[0].ndim != 3 for p in parsed):
-        raise ValueError("the batched features take a non-empty list of 3-D ROIs")
-    if _lib.load().prad_device_count() < 1:
-        raise RuntimeError("no HIP device: the batched features are evaluated on the device")
-    import torch
-    engine = _engine()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    sizes = np.array([p[2] for p in parsed], dtype=np.intc).reshape(-1, 3)
-    flat_l = torch.from_numpy(np.concatenate([p[0].ravel() for p in parsed])).to(dev)
-    flat_m = torch.from_numpy(np.concatenate([p[1].ravel().view(np.uint8) for p in parsed])).to(dev)
-    table, _ = engine.texture_features_batch(flat_l, flat_m, sizes, int(Ng), tuple(classes),
-                                             [int(d) for d in np.asarray(distances).ravel()], int(gldm_a),
-                                             bool(symmetricalGLCM), bool(mcc))
+    _, _, sizes, upload = _host_roi_batch(images, masks, "features")
+    table, _ = _engine().texture_features_batch(*upload(), sizes, int(Ng), tuple(classes),
+                                                [int(d) for d in np.asarray(distances).ravel()], int(gldm_a),
+                                                bool(symmetricalGLCM), bool(mcc))
     return {cls: {name: table[cls][:, i].copy() for i, name in enumerate(batch_feature_names(cls)) if name}
             for cls in table}
 
@@ -535,26 +555,6 @@ def batch_firstorder_plan(sizes, dtype):
     return rc == _lib.PRAD_OK, int(lds.value), inside[:B].astype(bool)
 
 
-def _upload_roi_batch(images, masks, what):
-    """lists of host arrays (raw intensity boxes, masks) -> (flat image tensor, flat uint8 mask tensor, sizes) in ONE upload each"""
-    if len(images) != len(masks):
-        raise ValueError("images and masks differ in number")
-    imgs = [np.ascontiguousarray(np.asarray(i)) for i in images]
-    msks = [np.ascontiguousarray(np.asarray(m)) for m in masks]
-    if not imgs or any(i.ndim != 3 or i.shape != m.shape for i, m in zip(imgs, msks)):
-        raise ValueError("the batched %s take a non-empty list of 3-D ROIs with masks of the same shape" % what)
-    if _lib.load().prad_device_count() < 1:
-        raise RuntimeError("no HIP device: the batched %s are evaluated on the device" % what)
-    import torch
-    dev = torch.device("cuda", torch.cuda.current_device())
-    dt = imgs[0].dtype if (imgs[0].dtype in (np.float32, np.float64, np.int32, np.int16)
-                           and all(i.dtype == imgs[0].dtype for i in imgs)) else np.dtype(np.float64)
-    sizes = np.array([i.shape for i in imgs], dtype=np.intc).reshape(-1, 3)
-    flat_i = torch.from_numpy(np.concatenate([i.ravel().astype(dt, copy=False) for i in imgs])).to(dev)
-    flat_m = torch.from_numpy(np.concatenate([(m.ravel() != 0).view(np.uint8) for m in msks])).to(dev)
-    return flat_i, flat_m, sizes
-
-
 def calculate_firstorder_batch(images, masks, voxelArrayShift=0.0, voxelVolume=1.0, **binning):
     """The first-order features of B small 3-D ROIs (lists of host arrays: raw intensities, masks): one upload, then
     engine.roi_features_batch with the first-order class alone -- two launches and two read-backs for the whole batch.  binning:
@@ -571,11 +571,10 @@ def calculate_roi_features_batch(images, masks, classes=("firstorder", "glcm", "
     then engine.roi_features_batch.  -> {class: {feature name: float64 [B]}} (FIRSTORDER_FEATURES / batch_feature_names); an
     empty ROI has NaN everywhere, the others are not affected.  Needs a device (RuntimeError without one); last_batch_route()
     tells which route ran."""
-    flat_i, flat_m, sizes = _upload_roi_batch(images, masks, "ROI features")
-    engine = _engine()
-    table, _ = engine.roi_features_batch(flat_i, flat_m, sizes, tuple(classes), binWidth, binCount, float(voxelArrayShift), voxelVolume,
-                                         [int(d) for d in np.asarray(distances).ravel()], int(gldm_a), bool(symmetricalGLCM),
-                                         bool(mcc))
+    _, _, sizes, upload = _host_roi_batch(images, masks, "ROI features", raw=True)
+    table, _ = _engine().roi_features_batch(*upload(), sizes, tuple(classes), binWidth, binCount, float(voxelArrayShift),
+                                            voxelVolume, [int(d) for d in np.asarray(distances).ravel()], int(gldm_a),
+                                            bool(symmetricalGLCM), bool(mcc))
     names = {cls: (FIRSTORDER_FEATURES if cls == "firstorder" else batch_feature_names(cls)) for cls in table}
     return {cls: {name: table[cls][:, i].copy() for i, name in enumerate(names[cls]) if name} for cls in table}
 

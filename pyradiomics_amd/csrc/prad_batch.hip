@@ -1,6 +1,7 @@
 // prad_batch.hip -- C ABI of the batched small-ROI texture matrices (include/pyradiomics_amd.h: prad_batch_plan,
 // prad_calculate_batch_dev); translation unit of libpyradiomics_amd.so.
 #include "kernels_batch.h"
+#include "prad_batch_common.h"
 
 #include <algorithm>
 
@@ -21,12 +22,13 @@ struct BatchLayout {
 // GLCM [Ng][Ng][Na], GLRLM [Ng][max(size)][Na1] (distance 1), GLDM [Ng][2 Nb + 1] with Nb = 2 Na, NGTDM [Ng][3].
 // Host only: no device is touched.
 int batch_layout(const int *sizes, int B, int Ng, int families, const int *distances, int Ndist, BatchLayout *lay) {
-  if (B < 0 || (B > 0 && !sizes)) return fail(PRAD_E_ARG, "batch: B=%d, sizes=%p", B, (const void *)sizes);
+  PRAD_TRY(roi_count_check("batch", sizes, B, 0));
   if (Ng < 1) return fail(PRAD_E_ARG, "batch: Ng=%d < 1", Ng);
   if (!distances || Ndist < 1) return fail(PRAD_E_ARG, "batch: no distances");
   if (families < 1 || families > PRAD_BATCH_ALL) return fail(PRAD_E_ARG, "batch: families=%d outside [1, %d]", families, PRAD_BATCH_ALL);
   for (int k = 0; k < Ndist; k++)
     if (distances[k] < 1) return fail(PRAD_E_ARG, "batch: distance %d < 1", distances[k]);
+  PRAD_TRY(roi_sizes_check("batch", sizes, B, nullptr));
   lay->offsets.assign((size_t)4 * (B + 1), 0);
   lay->na.assign((size_t)2 * B, 0);
   if (Ng > PRAD_BATCH_MAX_NG) {
@@ -36,9 +38,7 @@ int batch_layout(const int *sizes, int B, int Ng, int families, const int *dista
   long long *o = lay->offsets.data();
   for (int b = 0; b < B; b++) {
     const int *sz = sizes + 3 * b;
-    for (int d = 0; d < 3; d++)
-      if (sz[d] < 1) return fail(PRAD_E_ARG, "batch: ROI %d has size[%d]=%d < 1", b, d, sz[d]);
-    const long long nvox = (long long)sz[0] * sz[1] * sz[2];
+    const long long nvox = roi_nvox(sizes, b);
     const int na = prad_get_angle_count(sz, distances, 3, Ndist, 0, -1);
     const int na1 = prad_get_angle_count(sz, &kOne, 3, 1, 0, -1);
     lay->na[b] = na;
@@ -89,8 +89,7 @@ extern "C" int prad_calculate_batch_dev(const int32_t *levels, const uint8_t *ma
   }
   if (!levels || !mask || !off || !status) return fail(PRAD_E_ARG, "batch: NULL pointer");
   if (alpha < 0) return fail(PRAD_E_ARG, "batch: alpha=%d < 0", alpha);
-  for (int b = 0; b < B; b++)
-    if (off[b] < 0) return fail(PRAD_E_ARG, "batch: off[%d]=%lld < 0", b, off[b]);
+  PRAD_TRY(roi_offsets_check("batch", off, B));
   Context &c = ctx();
   PRAD_TRY(c.ensure_device());
   hipStream_t s = (hipStream_t)stream;
@@ -99,13 +98,10 @@ extern "C" int prad_calculate_batch_dev(const int32_t *levels, const uint8_t *ma
   const bool runs = (families & PRAD_BATCH_GLRLM) != 0, same = Ndist == 1 && distances[0] == 1;
   size_t nang = 0;
   for (int b = 0; b < B; b++) nang += (size_t)lay.na[b] + (runs && !same ? (size_t)lay.na[(size_t)B + b] : 0);
-  const size_t roi_bytes = (sizeof(BatchRoi) * (size_t)B + 15) & ~(size_t)15;
-  const size_t meta_bytes = roi_bytes + sizeof(int) * 3 * std::max<size_t>(nang, 1);
-  void *h_meta = nullptr, *d_meta = nullptr;
-  PRAD_TRY(c.get_pinned("batch_meta", meta_bytes, &h_meta));
-  PRAD_TRY(c.get("batch_meta", meta_bytes, &d_meta));
-  BatchRoi *rois = (BatchRoi *)h_meta;
-  int *angles = (int *)((char *)h_meta + roi_bytes);
+  RecordTable<BatchRoi> table;
+  PRAD_TRY(table.reserve(c, "batch_meta", (size_t)B, sizeof(int) * 3 * std::max<size_t>(nang, 1)));
+  BatchRoi *rois = table.host;
+  int *angles = (int *)table.host_tail();
   long long max_vox = 1;
   int max_na = 0, max_nr = 1;
   size_t row = 0;
@@ -129,7 +125,7 @@ extern "C" int prad_calculate_batch_dev(const int32_t *levels, const uint8_t *ma
         return fail(PRAD_E_ARG, "batch: distance-1 angles of ROI %d", b);
       row += (size_t)r.na_run;
     }
-    max_vox = std::max(max_vox, (long long)sz[0] * sz[1] * sz[2]);
+    max_vox = std::max(max_vox, roi_nvox(sizes, b));
     max_na = std::max(max_na, r.na);
     max_nr = std::max(max_nr, std::max(sz[0], std::max(sz[1], sz[2])));
   }
@@ -138,8 +134,8 @@ extern "C" int prad_calculate_batch_dev(const int32_t *levels, const uint8_t *ma
   BatchArgs A;
   A.levels = levels;
   A.mask = mask;
-  A.rois = (const BatchRoi *)d_meta;
-  A.angles = (const int *)((const char *)d_meta + roi_bytes);
+  A.rois = table.dev;
+  A.angles = (const int *)table.dev_tail();
   A.Ng = Ng;
   A.alpha = alpha;
   A.glcm = outs[0], A.glrlm = outs[1], A.gldm = outs[2], A.ngtdm = outs[3];
@@ -169,20 +165,10 @@ extern "C" int prad_calculate_batch_dev(const int32_t *levels, const uint8_t *ma
   const long long jobs = A.groups_glcm + A.groups_glrlm + A.neigh;
   if ((long long)B * jobs > 0x7fffffffLL) return fail(PRAD_E_UNSUPPORTED, "batch: %d ROIs x %lld jobs", B, jobs);
 
-  PRAD_TRY(c.begin_call(s));
-  PRAD_HIP(hipMemcpyAsync(d_meta, h_meta, meta_bytes, hipMemcpyHostToDevice, s));
-  if (lds > 64 * 1024)
-    PRAD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_rois_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int rc;
-  {
+  return batch_call(c, s, table, "batch-lds", [&]() {
+    PRAD_TRY(allow_dynamic_lds(&batch_rois_kernel, lds));
     Timed t(c, "batch", s);
     hipLaunchKernelGGL(batch_rois_kernel, dim3((unsigned)(B * jobs)), dim3(PRAD_BATCH_THREADS), lds, s, A);
-    rc = check_launch("batch_rois_kernel");
-  }
-  PRAD_TRY(c.end_call(s));
-  if (rc != PRAD_OK) return rc;
-  PRAD_HIP(hipStreamSynchronize(s));   // (the pinned record block is reused by the next call)
-  c.last_path = "batch";
-  c.last_variant = "batch-lds";
-  return PRAD_OK;
+    return check_launch("batch_rois_kernel");
+  });
 }

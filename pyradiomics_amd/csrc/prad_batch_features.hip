@@ -1,6 +1,7 @@
 // prad_batch_features.hip -- C ABI of the batched feature formulas (include/pyradiomics_amd.h: prad_batch_features_plan,
 // prad_batch_features_dev); translation unit of libpyradiomics_amd.so.
 #include "kernels_batch_features.h"
+#include "prad_batch_common.h"
 
 #include <algorithm>
 
@@ -88,17 +89,15 @@ extern "C" int prad_batch_features_dev(const int *sizes, int B, int Ng, int fami
   Context &c = ctx();
   PRAD_TRY(c.ensure_device());
   hipStream_t s = (hipStream_t)stream;
-  const size_t meta_bytes = sizeof(BatchFeatRec) * (size_t)lay.nrec;
-  void *h_meta = nullptr, *d_meta = nullptr;
+  RecordTable<BatchFeatRec> table;
   double *d_scr = nullptr;
   int *d_flag = nullptr;
-  PRAD_TRY(c.get_pinned("batch_feat_meta", meta_bytes, &h_meta));
-  PRAD_TRY(c.get("batch_feat_meta", meta_bytes, &d_meta));
+  PRAD_TRY(table.reserve(c, "batch_feat_meta", (size_t)lay.nrec));
   PRAD_TRY(c.get<double>("batch_feat_scratch", (size_t)std::max(lay.scratch, 1LL), &d_scr));
   PRAD_TRY(c.get<int>("batch_feat_flag", 4, &d_flag));
 
   // ---- the record table: GLCM angles first (the MCC launch runs over them alone), then family by family, ROI by ROI ----------
-  BatchFeatRec *recs = (BatchFeatRec *)h_meta;
+  BatchFeatRec *recs = table.host;
   size_t k = 0;
   long long scr = 0;
   for (int f = 0; f < BF_KINDS; f++) {
@@ -134,7 +133,7 @@ extern "C" int prad_batch_features_dev(const int *sizes, int B, int Ng, int fami
   const bool mcc = want_mcc && lay.nglcm > 0;
 
   BatchFeatArgs A;
-  A.recs = (const BatchFeatRec *)d_meta;
+  A.recs = table.dev;
   for (int f = 0; f < BF_KINDS; f++) A.mats[f] = mats[f];
   A.sizes = glszm_sizes;
   A.scratch = d_scr;
@@ -145,27 +144,16 @@ extern "C" int prad_batch_features_dev(const int *sizes, int B, int Ng, int fami
   const size_t lds = sizeof(double) * batch_features_lds_doubles(Ng);
   const size_t mcc_lds = ((mcc_scratch_bytes(Ng, Ng) + 15) & ~(size_t)15) + sizeof(double) * (size_t)Ng * Ng;   // staged
 
-  PRAD_TRY(c.begin_call(s));
-  PRAD_HIP(hipMemcpyAsync(d_meta, h_meta, meta_bytes, hipMemcpyHostToDevice, s));
-  if (mcc) {
-    PRAD_HIP(hipMemsetAsync(d_flag, 0, sizeof(int) * 4, s));
-    if (mcc_lds > 64 * 1024)
-      PRAD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_mcc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mcc_lds));
-  }
-  int rc;
-  {
+  return batch_call(c, s, table, "batch-features", [&]() {
+    if (mcc) {
+      PRAD_HIP(hipMemsetAsync(d_flag, 0, sizeof(int) * 4, s));
+      PRAD_TRY(allow_dynamic_lds(&batch_mcc_kernel, mcc_lds));
+    }
     Timed t(c, "batch_features", s);
     hipLaunchKernelGGL(batch_features_kernel, dim3((unsigned)lay.nrec), dim3(PRAD_FEAT_THREADS), lds, s, A);
-    rc = check_launch("batch_features_kernel");
-    if (rc == PRAD_OK && mcc) {
-      hipLaunchKernelGGL(batch_mcc_kernel, dim3((unsigned)lay.nglcm), dim3(PRAD_MCC_BT), mcc_lds, s, A, d_flag);
-      rc = check_launch("batch_mcc_kernel");
-    }
-  }
-  PRAD_TRY(c.end_call(s));
-  if (rc != PRAD_OK) return rc;
-  PRAD_HIP(hipStreamSynchronize(s));   // (the pinned record block is reused by the next call)
-  c.last_path = "batch";
-  c.last_variant = "batch-features";
-  return PRAD_OK;
+    PRAD_TRY(check_launch("batch_features_kernel"));
+    if (!mcc) return (int)PRAD_OK;
+    hipLaunchKernelGGL(batch_mcc_kernel, dim3((unsigned)lay.nglcm), dim3(PRAD_MCC_BT), mcc_lds, s, A, d_flag);
+    return check_launch("batch_mcc_kernel");
+  });
 }

@@ -1,55 +1,36 @@
 // prad_batch_glszm.hip -- C ABI of the batched small-ROI GLSZM (include/pyradiomics_amd.h: prad_batch_glszm_max_vox,
 // prad_batch_glszm_dev, prad_batch_glszm_fill_dev); translation unit of libpyradiomics_amd.so.
 #include "kernels_batch_glszm.h"
+#include "prad_batch_common.h"
 
 #include <algorithm>
 
 using namespace prad;
 
-namespace {
-
-// Host only: no device is touched.  *why is set (and PRAD_OK returned) when the arguments are valid but outside the domain.
-int zone_batch_check(const int *sizes, int B, int Ng, long long *max_vox, char *why, size_t why_len) {
-  why[0] = 0;
-  *max_vox = 1;
-  if (B < 0 || (B > 0 && !sizes)) return fail(PRAD_E_ARG, "batch GLSZM: B=%d, sizes=%p", B, (const void *)sizes);
-  if (Ng < 1) return fail(PRAD_E_ARG, "batch GLSZM: Ng=%d < 1", Ng);
-  if (Ng > PRAD_BZ_MAX_NG) snprintf(why, why_len, "Ng=%d above %d", Ng, PRAD_BZ_MAX_NG);
-  for (int b = 0; b < B; b++) {
-    const int *sz = sizes + 3 * b;
-    for (int d = 0; d < 3; d++)
-      if (sz[d] < 1) return fail(PRAD_E_ARG, "batch GLSZM: ROI %d has size[%d]=%d < 1", b, d, sz[d]);
-    const long long nvox = (long long)sz[0] * sz[1] * sz[2];
-    if (!why[0] && nvox > PRAD_BATCH_GLSZM_MAX_VOX)
-      snprintf(why, why_len, "ROI %d holds %lld voxels, above %d", b, nvox, PRAD_BATCH_GLSZM_MAX_VOX);
-    *max_vox = std::max(*max_vox, nvox);
-  }
-  return PRAD_OK;
-}
-
-}  // namespace
-
 extern "C" int prad_batch_glszm_max_vox(void) { return PRAD_BATCH_GLSZM_MAX_VOX; }
 
 extern "C" int prad_batch_glszm_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B,
                                     int Ng, int *zones, int *summary, int *status, void *stream) {
+  PRAD_TRY(roi_count_check("batch GLSZM", sizes, B, 0));
+  if (Ng < 1) return fail(PRAD_E_ARG, "batch GLSZM: Ng=%d < 1", Ng);
   long long max_vox = 1;
-  char why[160];
-  PRAD_TRY(zone_batch_check(sizes, B, Ng, &max_vox, why, sizeof(why)));
+  PRAD_TRY(roi_sizes_check("batch GLSZM", sizes, B, &max_vox));
   if (B > 0 && (!levels || !mask || !off || !zones || !summary || !status)) return fail(PRAD_E_ARG, "batch GLSZM: NULL pointer");
+  PRAD_TRY(roi_offsets_check("batch GLSZM", off, B));
+  // valid arguments outside the domain: nothing is launched
+  if (Ng > PRAD_BZ_MAX_NG) return fail(PRAD_E_UNSUPPORTED, "batch GLSZM: Ng=%d above %d (use the single call per ROI)", Ng, PRAD_BZ_MAX_NG);
   for (int b = 0; b < B; b++)
-    if (off[b] < 0) return fail(PRAD_E_ARG, "batch GLSZM: off[%d]=%lld < 0", b, off[b]);
-  if (why[0]) return fail(PRAD_E_UNSUPPORTED, "batch GLSZM: %s (use the single call per ROI)", why);   // nothing launched
+    if (roi_nvox(sizes, b) > PRAD_BATCH_GLSZM_MAX_VOX)
+      return fail(PRAD_E_UNSUPPORTED, "batch GLSZM: ROI %d holds %lld voxels, above %d (use the single call per ROI)", b,
+                  roi_nvox(sizes, b), PRAD_BATCH_GLSZM_MAX_VOX);
   if (B == 0) return PRAD_OK;
   Context &c = ctx();
   PRAD_TRY(c.ensure_device());
   hipStream_t s = (hipStream_t)stream;
 
-  const size_t meta_bytes = sizeof(BatchZoneRoi) * (size_t)B;
-  void *h_meta = nullptr, *d_meta = nullptr;
-  PRAD_TRY(c.get_pinned("batch_glszm_meta", meta_bytes, &h_meta));
-  PRAD_TRY(c.get("batch_glszm_meta", meta_bytes, &d_meta));
-  BatchZoneRoi *rois = (BatchZoneRoi *)h_meta;
+  RecordTable<BatchZoneRoi> table;
+  PRAD_TRY(table.reserve(c, "batch_glszm_meta", (size_t)B));
+  BatchZoneRoi *rois = table.host;
   for (int b = 0; b < B; b++) {
     rois[b].off = off[b];
     rois[b].nz = sizes[3 * b], rois[b].ny = sizes[3 * b + 1], rois[b].nx = sizes[3 * b + 2];
@@ -58,7 +39,7 @@ extern "C" int prad_batch_glszm_dev(const int32_t *levels, const uint8_t *mask, 
   BatchZoneArgs A;
   A.levels = levels;
   A.mask = mask;
-  A.rois = (const BatchZoneRoi *)d_meta;
+  A.rois = table.dev;
   A.Ng = Ng;
   A.vox_bytes = (int)((max_vox + 15) & ~15LL);
   A.zones = zones;
@@ -67,22 +48,12 @@ extern "C" int prad_batch_glszm_dev(const int32_t *levels, const uint8_t *mask, 
   const size_t lds = PRAD_BZ_MISC_BYTES + 3 * (size_t)A.vox_bytes;
   if (lds > 160 * 1024) return fail(PRAD_E_HIP, "batch GLSZM: %zu bytes of LDS per workgroup", lds);
 
-  PRAD_TRY(c.begin_call(s));
-  PRAD_HIP(hipMemcpyAsync(d_meta, h_meta, meta_bytes, hipMemcpyHostToDevice, s));
-  if (lds > 64 * 1024)
-    PRAD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_glszm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  int rc;
-  {
+  return batch_call(c, s, table, "batch-glszm-lds", [&]() {
+    PRAD_TRY(allow_dynamic_lds(&batch_glszm_kernel, lds));
     Timed t(c, "batch_glszm", s);
     hipLaunchKernelGGL(batch_glszm_kernel, dim3((unsigned)B), dim3(PRAD_BZ_THREADS), lds, s, A);
-    rc = check_launch("batch_glszm_kernel");
-  }
-  PRAD_TRY(c.end_call(s));
-  if (rc != PRAD_OK) return rc;
-  PRAD_HIP(hipStreamSynchronize(s));   // (the pinned record block is reused by the next call)
-  c.last_path = "batch";
-  c.last_variant = "batch-glszm-lds";
-  return PRAD_OK;
+    return check_launch("batch_glszm_kernel");
+  });
 }
 
 extern "C" int prad_batch_glszm_fill_dev(const int *zones, const int *summary_host, const long long *off, int B, int Ng,
@@ -104,11 +75,9 @@ extern "C" int prad_batch_glszm_fill_dev(const int *zones, const int *summary_ho
   Context &c = ctx();
   PRAD_TRY(c.ensure_device());
   hipStream_t s = (hipStream_t)stream;
-  const size_t meta_bytes = sizeof(BatchFillRoi) * (size_t)B;
-  void *h_meta = nullptr, *d_meta = nullptr;
-  PRAD_TRY(c.get_pinned("batch_glszm_fill_meta", meta_bytes, &h_meta));
-  PRAD_TRY(c.get("batch_glszm_fill_meta", meta_bytes, &d_meta));
-  BatchFillRoi *rois = (BatchFillRoi *)h_meta;
+  RecordTable<BatchFillRoi> table;
+  PRAD_TRY(table.reserve(c, "batch_glszm_fill_meta", (size_t)B));
+  BatchFillRoi *rois = table.host;
   for (int b = 0; b < B; b++) {
     rois[b].zones = 2 * off[b];
     rois[b].out = out_offsets[b];
@@ -118,19 +87,10 @@ extern "C" int prad_batch_glszm_fill_dev(const int *zones, const int *summary_ho
     rois[b].nsizes = summary_host[3 * b + 2];
     rois[b].pad = 0;
   }
-  PRAD_TRY(c.begin_call(s));
-  PRAD_HIP(hipMemcpyAsync(d_meta, h_meta, meta_bytes, hipMemcpyHostToDevice, s));
-  int rc;
-  {
+  return batch_call(c, s, table, "batch-glszm-lds", [&]() {
     Timed t(c, "batch_glszm", s);
-    hipLaunchKernelGGL(batch_glszm_fill_kernel, dim3((unsigned)B), dim3(PRAD_BZ_THREADS), 0, s, zones,
-                       (const BatchFillRoi *)d_meta, Ng, compact ? 1 : 0, out, sizes_out);
-    rc = check_launch("batch_glszm_fill_kernel");
-  }
-  PRAD_TRY(c.end_call(s));
-  if (rc != PRAD_OK) return rc;
-  PRAD_HIP(hipStreamSynchronize(s));   // (the pinned record block is reused by the next call)
-  c.last_path = "batch";
-  c.last_variant = "batch-glszm-lds";
-  return PRAD_OK;
+    hipLaunchKernelGGL(batch_glszm_fill_kernel, dim3((unsigned)B), dim3(PRAD_BZ_THREADS), 0, s, zones, table.dev, Ng,
+                       compact ? 1 : 0, out, sizes_out);
+    return check_launch("batch_glszm_fill_kernel");
+  });
 }

@@ -650,664 +650,6 @@ def gldm_ngtdm(image: torch.Tensor, mask: torch.Tensor, Ng: int, alpha: int = 0,
     return g, n
 
 
-# ---- many small ROIs, one launch (prad_calculate_batch_dev, csrc/kernels_batch.h) ----------------------------------
-def batch_max_vox() -> int:
-    """voxels of the largest ROI box the batched call takes (PRAD_BATCH_MAX_VOX)"""
-    return int(_lib.load().prad_batch_max_vox())
-
-
-def last_batch_route() -> str:
-    """ "batch" when the last texture_matrices_batch / glszm_batch call was served by the native launch, "looped" when it went
-    through the single calls ROI by ROI, "mixed" (glszm_batch only) when some ROIs of the batch took each route"""
-    return _cm.last_batch_route()
-
-
-def _batch_inputs(levels, masks, sizes, raw=False):
-    """-> (flat int32 levels, flat uint8 mask, sizes int32 [B, 3]) on one device.  raw: intensity images instead of levels; they
-    keep their dtype where it is one of the four the kernels read (float32, float64, int32, int16; anything else, or a list of
-    mixed dtypes, becomes float64)"""
-    def image_dtype(dts):
-        if not raw:
-            return torch.int32
-        return dts[0] if dts[0] in _DTYPE_CODES and all(d == dts[0] for d in dts) else torch.float64
-    if isinstance(levels, (list, tuple)):
-        if len(levels) != len(masks):
-            raise ValueError("levels and masks differ in number")
-        if any(l.dim() != 3 or l.shape != m.shape for l, m in zip(levels, masks)):
-            raise ValueError("the batched matrices take 3-D ROIs with masks of the same shape")
-        sizes = np.array([tuple(l.shape) for l in levels], dtype=np.intc).reshape(-1, 3)
-        if not len(levels):
-            raise ValueError("empty batch")
-        dt = image_dtype([l.dtype for l in levels])
-        levels = torch.cat([l.reshape(-1).to(dt) for l in levels])
-        masks = torch.cat([(m if m.dtype in (torch.bool, torch.uint8) else m != 0).reshape(-1).view(torch.uint8) for m in masks])
-    elif sizes is None:
-        raise ValueError("flat level / mask tensors need `sizes`")
-    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
-    levels, masks = levels.reshape(-1), masks.reshape(-1)
-    if raw:
-        if not levels.is_cuda or not masks.is_cuda:
-            raise ValueError("engine.* expects CUDA/HIP tensors; use pyradiomics_amd.cmatrices for numpy input")
-        if levels.shape != masks.shape:
-            raise ValueError("Dimensions of image and mask do not match.")
-        levels, masks = levels.to(image_dtype([levels.dtype])).contiguous(), _mask_u8(masks)
-        lib = _lib.load()
-        _lib.raise_for(lib.prad_set_device(levels.device.index if levels.device.index is not None else torch.cuda.current_device()),
-                       "set_device")
-    else:
-        lib, levels, masks, _ = _prep(levels, masks)
-    if int(sizes.astype(np.int64).prod(1).sum()) != levels.numel():
-        raise ValueError("sizes describe %d voxels, the buffers hold %d" % (int(sizes.astype(np.int64).prod(1).sum()), levels.numel()))
-    return lib, levels, masks, sizes
-
-
-def texture_matrices_batch_flat(levels, masks, sizes, Ng, families=_cm.BATCH_FAMILIES, distances=(1,), gldm_a=0):
-    """the native call alone: -> ({family: flat float64 device buffer}, status list), or None when it declines the batch"""
-    lib, levels, masks, sizes = _batch_inputs(levels, masks, sizes)
-    families = tuple(families)
-    dist = np.ascontiguousarray(np.asarray(list(distances), dtype=np.intc).ravel())
-    B = int(sizes.shape[0])
-    covered, offsets, _ = _cm.batch_plan(sizes, Ng, families, dist)
-    if not covered:
-        return None
-    off = np.zeros(B, dtype=np.int64)
-    off[1:] = np.cumsum(sizes.astype(np.int64).prod(1))[:-1]
-    dev = levels.device
-    flat = {f: torch.empty(int(offsets[_cm.BATCH_FAMILIES.index(f), B]), dtype=torch.float64, device=dev) for f in families}
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    ptr = [C.c_void_p(flat[f].data_ptr()) if f in flat else None for f in _cm.BATCH_FAMILIES]
-    rc = lib.prad_calculate_batch_dev(C.c_void_p(levels.data_ptr()), C.c_void_p(masks.data_ptr()), _iptr(sizes),
-                                      off.ctypes.data_as(C.POINTER(C.c_longlong)), B, int(Ng), _cm.batch_family_bits(families),
-                                      _iptr(dist), int(dist.shape[0]), int(gldm_a), ptr[0], ptr[1], ptr[2], ptr[3],
-                                      C.c_void_p(status.data_ptr()), _stream_ptr())
-    if rc == _lib.PRAD_E_UNSUPPORTED:
-        return None
-    _lib.raise_for(rc, "batched texture matrices")
-    _cm._set_batch_route("batch")
-    return flat, status.tolist()
-
-
-def texture_matrices_batch(levels, masks, sizes, Ng, families=_cm.BATCH_FAMILIES, distances=(1,), gldm_a=0):
-    """GLCM / GLRLM / GLDM / NGTDM of B small ROIs in ONE launch (segment mode, 3-D).  levels / masks: lists of 3-D device
-    tensors (concatenated here; `sizes` is then ignored), or flat device tensors holding the ROIs back to back plus `sizes`
-    (int [B, 3]).  -> ({family: [B float64 device tensors, views into one flat buffer, in the single calls' layouts:
-    glcm [Ng, Ng, Na], glrlm [Ng, max(size), Na1], gldm [Ng, 2 * Nb + 1] with Nb = 2 * Na, ngtdm [Ng, 3]]}, status [B]: 1,
-    or 0 for a ROI with a masked level outside [1, Ng] -- the single calls' IndexError; its matrices are void).
-    Covered: Ng <= 64, boxes of at most batch_max_vox() voxels, at most 127 angles; otherwise the single calls are looped ROI
-    by ROI (same results, separate tensors) and last_batch_route() says "looped".  GLSZM: glszm_batch."""
-    lib, levels, masks, sizes = _batch_inputs(levels, masks, sizes)
-    families = tuple(families)
-    dist = [int(d) for d in distances]
-    B = int(sizes.shape[0])
-    _, offsets, Na = _cm.batch_plan(sizes, Ng, families, dist)
-    shapes = _cm.batch_shapes(sizes, int(Ng), Na)
-    res = texture_matrices_batch_flat(levels, masks, sizes, Ng, families, dist, gldm_a)
-    if res is not None:
-        flat, status = res
-        mats = {}
-        for f in families:
-            o = offsets[_cm.BATCH_FAMILIES.index(f)]
-            mats[f] = [flat[f][int(o[b]):int(o[b + 1])].view(shapes[f][b]) for b in range(B)]
-        return mats, status
-    _cm._set_batch_route("looped")
-    mats, status = {f: [] for f in families}, []
-    dev, start = levels.device, 0
-    for b in range(B):
-        shape = tuple(int(s) for s in sizes[b])
-        n = shape[0] * shape[1] * shape[2]
-        img, msk = levels[start:start + n].view(shape), masks[start:start + n].view(shape)
-        start += n
-        try:
-            if n == 1:      # no angle exists: the single calls refuse the box
-                one = {f: torch.from_numpy(_cm._one_voxel_matrices(int(img.item()), bool(msk.item()), int(Ng), f)).to(dev)
-                       for f in families}
-            else:
-                one = {}
-                if "glcm" in families:
-                    one["glcm"] = glcm(img, msk, int(Ng), dist)[0]
-                if "glrlm" in families:
-                    one["glrlm"] = glcm_glrlm(img, msk, int(Ng), max(shape), want_glcm=False)[1]
-                if "gldm" in families:
-                    one["gldm"] = gldm(img, msk, int(Ng), int(gldm_a), dist)
-                if "ngtdm" in families:
-                    one["ngtdm"] = ngtdm(img, msk, int(Ng), dist)
-            st = _lib.PRAD_OK
-        except IndexError:          # as the native route: status 0, the matrices of an empty mask
-            one = {f: torch.zeros(shapes[f][b], dtype=torch.float64, device=dev) for f in families}
-            if "ngtdm" in one:
-                one["ngtdm"][:, 2] = torch.arange(1, int(Ng) + 1, dtype=torch.float64, device=dev)
-            st = _lib.PRAD_INDEX_ERROR
-        for f in families:
-            mats[f].append(one[f])
-        status.append(st)
-    return mats, status
-
-
-# ---- GLSZM of many small ROIs (prad_batch_glszm_dev / prad_batch_glszm_fill_dev, csrc/kernels_batch_glszm.h) -------------------
-def batch_glszm_max_vox() -> int:
-    """voxels of the largest ROI box the batched GLSZM takes (PRAD_BATCH_GLSZM_MAX_VOX)"""
-    return int(_lib.load().prad_batch_glszm_max_vox())
-
-
-def _lp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_longlong))
-
-
-def _glszm_batch_label(lib, levels, masks, sizes, off, Ng):
-    """the labelling launch on the ROIs (sizes[b], off[b]) of the flat buffers -> (zones int32 device buffer indexed by
-    2 * off[b], summary int32 numpy [B, 3], status int32 numpy [B]); summary and status come back in ONE copy"""
-    B = int(sizes.shape[0])
-    dev = levels.device
-    zones = torch.empty(2 * levels.numel(), dtype=torch.int32, device=dev)
-    meta = torch.empty(4 * B, dtype=torch.int32, device=dev)
-    rc = lib.prad_batch_glszm_dev(C.c_void_p(levels.data_ptr()), C.c_void_p(masks.data_ptr()), _iptr(sizes), _lp(off), B, int(Ng),
-                                  C.c_void_p(zones.data_ptr()), C.c_void_p(meta.data_ptr()),
-                                  C.c_void_p(meta.data_ptr() + 12 * B), _stream_ptr())
-    _lib.raise_for(rc, "batched GLSZM")
-    host = meta.cpu().numpy()
-    return zones, np.ascontiguousarray(host[:3 * B].reshape(B, 3)), host[3 * B:].copy()
-
-
-def _glszm_batch_split(sizes, Ng):
-    """-> (element offset of every ROI, indices of the ROIs the native launch covers)"""
-    nvox = sizes.astype(np.int64).prod(1)
-    off = np.zeros(len(nvox), dtype=np.int64)
-    off[1:] = np.cumsum(nvox)[:-1]
-    covered = np.flatnonzero(nvox <= batch_glszm_max_vox()) if int(Ng) <= 64 else np.zeros(0, dtype=np.int64)
-    return off, covered
-
-
-def _one_voxel_glszm(level, masked, Ng, compact, dev):
-    """the GLSZM of a 1 x 1 x 1 box (no angle exists: the single call refuses it)"""
-    if masked and not 1 <= level <= Ng:
-        raise IndexError("level outside [1, Ng]")
-    P = torch.zeros((Ng, 1), dtype=torch.float64, device=dev)
-    if masked:
-        P[level - 1, 0] = 1
-    if not compact:
-        return P
-    return (P, np.ones(1, dtype=np.intc)) if masked else (P[:, :0], np.zeros(0, dtype=np.intc))
-
-
-class _GlszmBatch(list):
-    """the result list of glszm_batch; `flat` describes the device buffers the native route's results are views of"""
-    flat = None
-
-
-def glszm_batch_zones(levels, masks, sizes, Ng):
-    """the zone lists of B small ROIs from the labelling launch alone -> (list of B int32 device tensors [nzones, 2] of
-    (level, size) in raster order of each zone's first voxel -- views into one buffer --, summary int32 numpy [B, 3]: zones,
-    largest zone, distinct sizes; status int32 numpy [B]).  Raises NotImplementedError outside the native domain (Ng > 64, a box
-    above batch_glszm_max_vox() voxels)."""
-    lib, levels, masks, sizes = _batch_inputs(levels, masks, sizes)
-    off, _ = _glszm_batch_split(sizes, Ng)
-    zones, summary, status = _glszm_batch_label(lib, levels, masks, sizes, off, Ng)
-    _cm._set_batch_route("batch")
-    return [zones[2 * int(o):2 * int(o) + 2 * int(n)].view(-1, 2) for o, n in zip(off, summary[:, 0])], summary, status
-
-
-def glszm_batch(levels, masks, sizes, Ng, compact=True):
-    """GLSZM of B small ROIs in two launches (segment mode, 3-D, the full neighbourhood): zones labelled in LDS by one workgroup
-    per ROI, one read-back of the per-ROI summary, one fill.  Inputs as texture_matrices_batch.  -> (list of B results, status
-    [B]: 1, or 0 for a ROI with a masked level outside [1, Ng] -- the single call's IndexError; its result is that of an empty
-    mask).  compact=True: a result is (P float64 [Ng, k] device tensor, sizes int32 numpy [k] ascending) as glszm_compact
-    returns; compact=False: the dense [Ng, max(maxRegion, 1)] tensor as glszm returns.  The results of the native route are
-    views into one flat buffer.  ROIs above batch_glszm_max_vox() voxels, or every ROI when Ng > 64, go through glszm_compact /
-    glszm one by one (Ns = max(1, masked voxels)); last_batch_route() says "batch", "mixed" or "looped"."""
-    lib, levels, masks, sizes = _batch_inputs(levels, masks, sizes)
-    Ng = int(Ng)
-    B = int(sizes.shape[0])
-    dev = levels.device
-    off, covered = _glszm_batch_split(sizes, Ng)
-    results, status = [None] * B, [_lib.PRAD_OK] * B
-    if len(covered):
-        csz, coff = np.ascontiguousarray(sizes[covered]), np.ascontiguousarray(off[covered])
-        zones, summary, st = _glszm_batch_label(lib, levels, masks, csz, coff, Ng)
-        cols = np.maximum(summary[:, 2 if compact else 1], 1).astype(np.int64)
-        out_off = np.zeros(len(covered) + 1, dtype=np.int64)
-        out_off[1:] = np.cumsum(Ng * cols)
-        k = summary[:, 2].astype(np.int64)
-        s_off = np.zeros(len(covered) + 1, dtype=np.int64)
-        s_off[1:] = np.cumsum(k)
-        flat = torch.empty(int(out_off[-1]), dtype=torch.float64, device=dev)
-        sizes_dev = torch.empty(max(int(s_off[-1]), 1), dtype=torch.int32, device=dev)
-        rc = lib.prad_batch_glszm_fill_dev(C.c_void_p(zones.data_ptr()), _iptr(summary), _lp(coff), len(covered), Ng,
-                                           1 if compact else 0, C.c_void_p(flat.data_ptr()), _lp(out_off),
-                                           C.c_void_p(sizes_dev.data_ptr()), _lp(s_off), _stream_ptr())
-        _lib.raise_for(rc, "batched GLSZM fill")
-        sizes_host = sizes_dev.cpu().numpy() if compact else None
-        for i, b in enumerate(covered):
-            P = flat[int(out_off[i]):int(out_off[i + 1])].view(Ng, int(cols[i]))
-            results[b] = (P[:, :int(k[i])], sizes_host[s_off[i]:s_off[i + 1]].copy()) if compact else P
-            status[b] = int(st[i])
-    results = _GlszmBatch(results)
-    if len(covered):      # (batch_features_per_angle evaluates the formulas on these buffers, in place)
-        results.flat = {"P": flat, "covered": covered, "out_off": out_off, "cols": cols, "compact": bool(compact),
-                        "sizes": sizes_dev if compact else None, "s_off": s_off, "k": k}
-    rest = sorted(set(range(B)) - set(int(b) for b in covered))
-    for b in rest:
-        shape = tuple(int(s) for s in sizes[b])
-        n = shape[0] * shape[1] * shape[2]
-        img, msk = levels[int(off[b]):int(off[b]) + n].view(shape), masks[int(off[b]):int(off[b]) + n].view(shape)
-        try:
-            if n == 1:
-                results[b] = _one_voxel_glszm(int(img.item()), bool(msk.item()), Ng, compact, dev)
-            else:
-                Ns = max(1, int(msk.sum().item()))
-                results[b] = glszm_compact(img, msk, Ng, Ns) if compact else glszm(img, msk, Ng, Ns)
-        except IndexError:          # as the native route: status 0, the result of an empty mask
-            results[b] = _one_voxel_glszm(0, False, Ng, compact, dev)
-            status[b] = _lib.PRAD_INDEX_ERROR
-    _cm._set_batch_route("looped" if not len(covered) else ("mixed" if rest else "batch"))
-    return results, status
-
-
-# ---- feature formulas of many small ROIs (prad_batch_features_dev, csrc/kernels_batch_features.h) ----------------------------
-FEATURE_FAMILIES = ("glcm", "glrlm", "gldm", "ngtdm", "glszm")       # bit f of the C `families` argument, row f of its offsets
-_FEATURE_ROW = {"glcm": 24, "glrlm": 16, "gldm": 16, "ngtdm": 5, "glszm": 16}
-
-
-def _flat_offsets(tensors):
-    """element offsets of the tensors in the ONE storage they all are contiguous views of (-> base pointer, int64 offsets),
-    or None when they are separate tensors (the looped routes' results)"""
-    if not tensors:
-        return None
-    base = tensors[0].untyped_storage().data_ptr()
-    if any((not t.is_cuda) or t.dtype != torch.float64 or not t.is_contiguous() or t.untyped_storage().data_ptr() != base
-           for t in tensors):
-        return None
-    return base, np.array([t.storage_offset() for t in tensors], dtype=np.int64)
-
-
-def _single_glszm_features(item, Ng):
-    """the single call on one glszm_batch result (compact pair or dense tensor); a ROI without zones is an empty matrix"""
-    P, jv = item if isinstance(item, tuple) else (item, np.arange(1, item.shape[1] + 1))
-    if P.shape[1] == 0:
-        return np.full((1, 16), np.nan), np.ones(1, dtype=bool)
-    return zone_matrix_features(P, jv)
-
-
-def _single_features(f, M, symmetric, mcc):
-    """family f of one ROI through the single calls -> (float64 [rows, nfeat], bool [rows])"""
-    if f == "ngtdm":
-        return ngtdm_features(M).reshape(1, 5).copy(), np.array([not bool((M[:, 0] > 0).any().item())])
-    if f == "glcm":
-        Na = int(M.shape[2])
-        vals, empty = (glcm_features(M, symmetric) if Na else (np.empty((0, 23)), np.zeros(0, dtype=bool)))
-        last = glcm_mcc(M, symmetric) if (mcc and Na) else np.full(Na, np.nan)
-        return np.concatenate([vals, last.reshape(Na, 1)], axis=1), empty
-    if M.dim() == 3 and M.shape[2] == 0:
-        return np.empty((0, 16)), np.zeros(0, dtype=bool)
-    return zone_matrix_features(M, np.arange(1, M.shape[1] + 1))
-
-
-def batch_features_per_angle(mats, Ng, glszm=None, symmetric=True, mcc=True):
-    """The feature formulas on the matrices of a batch: `mats` is the dict of texture_matrices_batch, `glszm` the result list of
-    glszm_batch (compact or dense) or None.  -> {family: [B pairs (float64 numpy [rows, nfeat], bool numpy [rows] = matrix
-    empty)]}, rows = angles for glcm (24 columns: the 23 of glcm_features, then glcm_mcc; NaN without `mcc`) and glrlm (16),
-    one row for gldm (16), ngtdm (5; its flag says that no level occurs) and glszm (16): the arrays the single calls return,
-    bit for bit.  Matrices that are views of the flat buffers of the batched calls are evaluated in two launches
-    (prad_batch_features_dev: Ng <= 64); anything else goes through the single calls, one by one."""
-    lib = _lib.load()
-    Ng = int(Ng)
-    fams = [f for f in FEATURE_FAMILIES[:4] if f in mats]
-    B = len(mats[fams[0]]) if fams else len(glszm or [])
-    if any(len(mats[f]) != B for f in fams) or (glszm is not None and len(glszm) != B):
-        raise ValueError("the families differ in their number of ROIs")
-    out = {f: [None] * B for f in fams}
-    if glszm is not None:
-        out["glszm"] = [None] * B
-    views = {f: _flat_offsets(list(mats[f])) for f in fams} if Ng <= 64 else {f: None for f in fams}
-    zflat = getattr(glszm, "flat", None) if (glszm is not None and Ng <= 64) else None
-    native = [f for f in fams if views[f] is not None]
-    if (native or zflat is not None) and B:
-        dev = (mats[native[0]][0] if native else zflat["P"]).device
-        lib.prad_set_device(dev.index or 0)
-        # the angle counts and the longest axis as the matrices' shapes give them (the C call takes them as prad_batch_plan does)
-        Na = np.zeros((2, B), dtype=np.intc)
-        sizes = np.ones((B, 3), dtype=np.intc)
-        for b in range(B):
-            if "glcm" in native:
-                Na[0, b] = mats["glcm"][b].shape[2]
-            elif "gldm" in native:
-                Na[0, b] = (mats["gldm"][b].shape[1] - 1) // 4
-            if "glrlm" in native:
-                sizes[b, 0], Na[1, b] = mats["glrlm"][b].shape[1], mats["glrlm"][b].shape[2]
-        offsets = np.zeros((4, B + 1), dtype=np.int64)
-        ptrs = [None] * 4
-        bits = 0
-        for f in native:
-            i = FEATURE_FAMILIES.index(f)
-            ptrs[i], offsets[i, :B] = C.c_void_p(views[f][0]), views[f][1]
-            bits |= 1 << i
-        cols = np.zeros(B, dtype=np.intc)
-        zoff, soff = np.zeros(B, dtype=np.int64), np.full(B, -1, dtype=np.int64)
-        zptr = sptr = None
-        if zflat is not None:
-            bits |= 16
-            cov = zflat["covered"]
-            cols[cov] = zflat["cols"]
-            zoff[cov] = zflat["out_off"][:-1]
-            zptr = C.c_void_p(zflat["P"].data_ptr())
-            if zflat["compact"]:
-                soff[cov] = np.where(zflat["k"] > 0, zflat["s_off"][:-1], -1)      # (no zone: one zero column, no size list)
-                sptr = C.c_void_p(zflat["sizes"].data_ptr())
-        lay = np.zeros((2, 5, B + 1), dtype=np.int64)
-        nrec = np.zeros(3, dtype=np.int64)
-        rc = lib.prad_batch_features_plan(_iptr(sizes), B, Ng, bits, _iptr(Na), _iptr(cols), _lp(lay), _lp(nrec))
-        _lib.raise_for(rc, "batched features plan")
-        nout, nrows = int(lay[0, 4, B]), int(lay[1, 4, B])
-        # values and flags in one device block: one read-back
-        block = torch.empty(nout + (nrows + 1) // 2 + 1, dtype=torch.float64, device=dev)
-        flags = block[nout:].view(torch.int32)
-        rc = lib.prad_batch_features_dev(_iptr(sizes), B, Ng, bits, _iptr(Na), _iptr(cols), ptrs[0], ptrs[1], ptrs[2], ptrs[3],
-                                         _lp(offsets), zptr, _lp(zoff), sptr, _lp(soff), 1 if symmetric else 0, 1 if mcc else 0,
-                                         C.c_void_p(block.data_ptr()), C.c_void_p(flags.data_ptr()), _stream_ptr())
-        _lib.raise_for(rc, "batched features")
-        host = block.cpu().numpy()
-        vals, empty = host[:nout], host[nout:].view(np.int32)[:nrows] != 0
-        for f in native + (["glszm"] if zflat is not None else []):
-            i, w = FEATURE_FAMILIES.index(f), _FEATURE_ROW[f]
-            for b in (range(B) if f != "glszm" else zflat["covered"]):
-                e0, e1, r0, r1 = int(lay[0, i, b]), int(lay[0, i, b + 1]), int(lay[1, i, b]), int(lay[1, i, b + 1])
-                out[f][b] = (vals[e0:e1].reshape(r1 - r0, w).copy(), empty[r0:r1].copy())
-    for f in out:      # whatever the native call did not take
-        for b in range(B):
-            if out[f][b] is None:
-                out[f][b] = _single_glszm_features(glszm[b], Ng) if f == "glszm" else _single_features(f, mats[f][b], symmetric, mcc)
-    return out
-
-
-def texture_features_batch(levels, masks, sizes, Ng, classes=("glcm", "glrlm", "glszm", "gldm", "ngtdm"),
-                           distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True, mcc_angles=False):
-    """The texture FEATURES of B small ROIs (segment mode, 3-D; inputs as texture_matrices_batch): texture_matrices_batch,
-    glszm_batch(compact=True), the formulas of all matrices in two launches (batch_features_per_angle) and, per ROI, the mean
-    over the angles the reference keeps (cmatrices._angle_mean).  -> ({class: float64 numpy [B, nfeat]}, status [B]): glcm 24
-    columns (cmatrices.VOXEL_GLCM_FEATURES, then MCC -- NaN without `mcc`), glrlm / gldm / glszm 16 (the shared zone numbering),
-    ngtdm 5.  status 0: a masked level outside [1, Ng]; that ROI's rows are NaN, the others are not affected.  weightingNorm is
-    not offered.  Outside the native domain (Ng > 64, boxes above the batch caps) the single calls are looped and give the same
-    values; last_batch_route() says "batch", "mixed" or "looped".  mcc_angles=True adds the entry "glcm_mcc_angles": per ROI the
-    MCC of every angle (float64 [Na], NaN for an empty angle; None with status 0) -- what the feature class averages as a flat
-    vector (cmatrices._mcc_angle_mean), in another order of additions than the column mean of the table."""
-    lib, levels, masks, sizes = _batch_inputs(levels, masks, sizes)
-    classes = tuple(classes)
-    unknown = [c for c in classes if c not in FEATURE_FAMILIES]
-    if unknown or not classes:
-        raise ValueError("classes must be a non-empty subset of %s" % (FEATURE_FAMILIES,))
-    B = int(sizes.shape[0])
-    fams = tuple(f for f in FEATURE_FAMILIES[:4] if f in classes)
-    status = np.ones(B, dtype=np.int64)
-    routes = []
-    mats, zones = {}, None
-    if fams:
-        mats, st = texture_matrices_batch(levels, masks, sizes, Ng, fams, distances, gldm_a)
-        routes.append(last_batch_route())
-        status &= np.asarray(st, dtype=np.int64) == _lib.PRAD_OK
-    if "glszm" in classes:
-        zones, st = glszm_batch(levels, masks, sizes, Ng, compact=True)
-        routes.append(last_batch_route())
-        status &= np.asarray(st, dtype=np.int64) == _lib.PRAD_OK
-    per = batch_features_per_angle(mats, Ng, zones, symmetricalGLCM, mcc)
-    table = {}
-    for f in classes:
-        rows = np.full((B, _FEATURE_ROW[f]), np.nan)
-        for b in range(B):
-            if status[b]:
-                vals, empty = per[f][b]
-                rows[b] = vals[0] if f == "ngtdm" else _cm._angle_mean(vals, empty)
-        table[f] = rows
-    if mcc_angles and "glcm" in classes:
-        table["glcm_mcc_angles"] = [per["glcm"][b][0][:, 23].copy() if status[b] else None for b in range(B)]
-    _cm._set_batch_route(routes[0] if all(r == routes[0] for r in routes) else "mixed")
-    return table, status.tolist()
-
-
-# ---- first-order statistics and discretisation of many small ROIs (prad_batch_firstorder_dev / prad_batch_digitize_dev, -------
-# ---- csrc/kernels_batch_firstorder.h): raw intensity boxes in, the table of all six feature classes out ------------------------
-ROI_FEATURE_CLASSES = ("firstorder", "glcm", "glrlm", "glszm", "gldm", "ngtdm")
-_NP_DTYPES = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32, torch.int16: np.int16}
-
-
-def batch_firstorder_max_roi(dtype) -> int:
-    """most ROI voxels (mask != 0) per ROI the batched first-order launch sorts in LDS: 32768, or 16384 for float64"""
-    code = _DTYPE_CODES[dtype] if dtype in _DTYPE_CODES else int(dtype)
-    return int(_lib.load().prad_batch_firstorder_max_roi(code))
-
-
-def batch_digitize_max_edges() -> int:
-    """most bin edges per ROI the batched discretisation stages in LDS (PRAD_BATCH_DIGITIZE_MAX_EDGES)"""
-    return int(_lib.load().prad_batch_digitize_max_edges())
-
-
-def _roi_offsets(sizes):
-    nvox = sizes.astype(np.int64).prod(1)
-    off = np.zeros(len(nvox), dtype=np.int64)
-    off[1:] = np.cumsum(nvox)[:-1]
-    return off, nvox
-
-
-def _roi_view(flat, sizes, off, nvox, b):
-    return flat[int(off[b]):int(off[b] + nvox[b])].view(tuple(int(s) for s in sizes[b]))
-
-
-def _joined_route(routes):
-    return routes[0] if all(r == routes[0] for r in routes) else "mixed"
-
-
-def firstorder_batch(images, masks, sizes=None, voxelArrayShift=0.0):
-    """The first-order statistics of B small ROIs in ONE launch (segment mode, 3-D).  images / masks: lists of 3-D device
-    tensors of one dtype (float32, float64, int32, int16; anything else is widened to float64), or flat device tensors holding
-    the boxes back to back plus `sizes` (int [B, 3]); masks bool or integer, non-zero = ROI.  -> (float64 numpy [B, 15] in the
-    order of FIRSTORDER_FIELDS, status int64 [B] = the launch's verdict per ROI: 0 fine; 1 empty ROI, its row is NaN; 2 a
-    non-finite ROI value and 8 more ROI voxels than batch_firstorder_max_roi(): that ROI's row comes from firstorder_stats).
-    last_batch_route() says "batch", "mixed" (some ROIs went through firstorder_stats) or "looped" (all did)."""
-    lib, images, masks, sizes = _batch_inputs(images, masks, sizes, raw=True)
-    B = int(sizes.shape[0])
-    off, nvox = _roi_offsets(sizes)
-    table = torch.empty((B, 16), dtype=torch.float64, device=images.device)
-    rc = lib.prad_batch_firstorder_dev(C.c_void_p(images.data_ptr()), _DTYPE_CODES[images.dtype], C.c_void_p(masks.data_ptr()),
-                                       _iptr(sizes), _lp(off), B, float(voxelArrayShift), C.c_void_p(table.data_ptr()),
-                                       _stream_ptr())
-    if rc == _lib.PRAD_E_UNSUPPORTED:          # nothing was launched: every ROI takes the single call
-        tab = np.full((B, 16), np.nan)
-        tab[:, 15] = 8
-    else:
-        _lib.raise_for(rc, "batched first-order statistics")
-        tab = table.cpu().numpy()              # the batch's first read-back
-    status = tab[:, 15].astype(np.int64)
-    rows = np.ascontiguousarray(tab[:, :15])
-    rest = np.flatnonzero((status == 2) | (status == 8))
-    for b in rest:
-        st = firstorder_stats(_roi_view(images, sizes, off, nvox, b), _roi_view(masks, sizes, off, nvox, b), voxelArrayShift)
-        rows[b] = [st[f] for f in FIRSTORDER_FIELDS]
-    _cm._set_batch_route("batch" if not len(rest) else ("looped" if len(rest) == B else "mixed"))
-    return rows, status
-
-
-def bin_batch(images, masks, sizes=None, stats=None, **binning):
-    """The discretisation of B small ROIs in ONE launch: every ROI gets its own bin edges -- imageoperations.getBinEdges on its
-    (Minimum, Maximum), as bin_image builds them; binWidth and binCount both work -- and is digitised against them by its own
-    workgroup.  Inputs as firstorder_batch; stats: the (rows, status) pair of firstorder_batch on the same batch (computed here
-    when None).  -> (flat int32 level tensor in the batch layout, Ng int64 [B], list of B float64 edge arrays, list of B int64
-    count arrays [Ng + 1]), ROI by ROI what bin_image(..., with_counts=True) returns.  An empty ROI has Ng 0, no edges, counts
-    [0] and levels 0.  ROIs whose statistics came from the single call (status 2 / 8) or with more than
-    batch_digitize_max_edges() edges go through bin_image; last_batch_route() says "batch", "mixed" or "looped"."""
-    from . import imageoperations
-    lib, images, masks, sizes = _batch_inputs(images, masks, sizes, raw=True)
-    B = int(sizes.shape[0])
-    off, nvox = _roi_offsets(sizes)
-    rows, status = firstorder_batch(images, masks, sizes) if stats is None else stats
-    rows, status = np.asarray(rows, dtype=np.float64).reshape(B, -1), np.asarray(status).reshape(B)
-    np_dtype = _NP_DTYPES[images.dtype]
-    cap = batch_digitize_max_edges()
-    edges = [np.zeros(0, dtype=np.float64)] * B
-    single = []
-    edge_off = np.zeros(B + 1, dtype=np.int64)
-    count_off = np.full(B, -1, dtype=np.int64)
-    ncounts = 0
-    i_min, i_max = FIRSTORDER_FIELDS.index("Minimum"), FIRSTORDER_FIELDS.index("Maximum")
-    for b in range(B):
-        ne = 0
-        if status[b] == 0:
-            e = np.asarray(imageoperations.getBinEdges(np.array([rows[b, i_min], rows[b, i_max]], dtype=np_dtype), **binning),
-                           dtype=np.float64)
-            if len(e) <= cap:
-                edges[b], ne = e, len(e)
-        if status[b] == 1 or ne:
-            count_off[b] = ncounts
-            ncounts += ne + 1
-        else:
-            single.append(b)
-        edge_off[b + 1] = edge_off[b] + ne
-    dev = images.device
-    levels = torch.empty(images.numel(), dtype=torch.int32, device=dev)
-    counts = [None] * B
-    Ng = np.zeros(B, dtype=np.int64)
-    if len(single) < B:
-        flat_edges = np.concatenate(edges) if edge_off[B] else np.zeros(1, dtype=np.float64)
-        d_edges = torch.from_numpy(flat_edges).to(dev)
-        back = torch.empty(ncounts + (B + 1) // 2, dtype=torch.int64, device=dev)      # [counts | top (int32)]: one read-back
-        top = back[ncounts:].view(torch.int32)
-        rc = lib.prad_batch_digitize_dev(C.c_void_p(images.data_ptr()), _DTYPE_CODES[images.dtype], C.c_void_p(masks.data_ptr()),
-                                         _iptr(sizes), _lp(off), B, C.c_void_p(d_edges.data_ptr()), _lp(edge_off),
-                                         C.c_void_p(levels.data_ptr()), C.c_void_p(back.data_ptr()), _lp(count_off),
-                                         C.c_void_p(top.data_ptr()), _stream_ptr())
-        _lib.raise_for(rc, "batched discretisation")
-        host = back.cpu().numpy()              # the batch's second read-back
-        tops = host[ncounts:].view(np.int32)
-        for b in range(B):
-            if count_off[b] >= 0:
-                Ng[b] = int(tops[b])
-                counts[b] = host[int(count_off[b]):int(count_off[b]) + int(Ng[b]) + 1].copy()
-    for b in single:
-        lv, ng, e, c = bin_image(_roi_view(images, sizes, off, nvox, b), _roi_view(masks, sizes, off, nvox, b), with_counts=True,
-                                 **binning)
-        levels[int(off[b]):int(off[b] + nvox[b])] = lv.reshape(-1)
-        Ng[b], edges[b], counts[b] = ng, e, c
-    _cm._set_batch_route("batch" if not single else ("looped" if len(single) == B else "mixed"))
-    return levels, Ng, edges, counts
-
-
-def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, binWidth=None, binCount=None, voxelArrayShift=0,
-                       voxelVolume=1.0, distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True, extras=False):
-    """The feature table of B small ROIs from their raw intensity boxes and masks (inputs as firstorder_batch): firstorder_batch
-    and bin_batch -- two launches and two read-backs for the whole batch (binWidth, default 25, or binCount) -- then
-    texture_features_batch once per distinct Ng of the batch on the ROIs that share it.  -> ({class: float64 numpy [B, nfeat]},
-    status [B]): "firstorder" has the 19 columns of cmatrices.FIRSTORDER_FEATURES (firstorder.features_from_stats on the
-    statistics, the level counts and voxelVolume, a number or [B]); the texture classes the columns of texture_features_batch.
-    status 0: an empty ROI; its rows are NaN, the others are not affected.  last_batch_route() says "batch", "mixed" or
-    "looped" (texture_features_batch loops the single calls above 64 levels; MCC is not evaluated there -- its column is NaN
-    for a ROI with more than 64 levels, as without `mcc`).  extras=True adds two entries the label route of the feature extractor
-    needs to report what the feature classes report: "gray_levels" int64 [B], the number of grey levels that occur in the ROI, and
-    (with glcm) "glcm_mcc_angles", see texture_features_batch."""
-    from . import firstorder as _fo
-    lib, images, masks, sizes = _batch_inputs(images, masks, sizes, raw=True)
-    classes = tuple(classes)
-    if not classes or any(c not in ROI_FEATURE_CLASSES for c in classes):
-        raise ValueError("classes must be a non-empty subset of %s" % (ROI_FEATURE_CLASSES,))
-    binning = {"binCount": binCount} if binCount is not None else {"binWidth": 25 if binWidth is None else binWidth}
-    B = int(sizes.shape[0])
-    off, nvox = _roi_offsets(sizes)
-    routes = []
-    rows, verdict = firstorder_batch(images, masks, sizes, voxelArrayShift)
-    routes.append(last_batch_route())
-    levels, Ng, _, counts = bin_batch(images, masks, sizes, stats=(rows, verdict), **binning)
-    routes.append(last_batch_route())
-    status = (verdict != 1).astype(np.int64)
-    table = {}
-    if "firstorder" in classes:
-        vals = _fo.features_from_stats(rows, [c[1:] for c in counts], voxelVolume)
-        vals[status == 0] = np.nan
-        table["firstorder"] = vals
-    texture = tuple(c for c in classes if c != "firstorder")
-    angles = [None] * B
-    if texture:
-        for c in texture:
-            table[c] = np.full((B, _FEATURE_ROW[c]), np.nan)
-        for ng in sorted(set(int(g) for g in Ng[status == 1])):
-            idx = np.flatnonzero((Ng == ng) & (status == 1))
-            if len(idx) == B:
-                sub_l, sub_m = levels, masks
-            else:
-                sub_l = torch.cat([levels[int(off[b]):int(off[b] + nvox[b])] for b in idx])
-                sub_m = torch.cat([masks[int(off[b]):int(off[b] + nvox[b])] for b in idx])
-            sub, st = texture_features_batch(sub_l, sub_m, sizes[idx], ng, texture, distances, gldm_a, symmetricalGLCM,
-                                             mcc and ng <= 64,       # (glcm_mcc declines more than 64 occurring levels)
-                                             mcc_angles=extras and mcc and ng <= 64)
-            routes.append(last_batch_route())
-            for k, b in enumerate(idx):
-                if "glcm_mcc_angles" in sub:
-                    angles[b] = sub["glcm_mcc_angles"][k]
-            for c in texture:
-                table[c][idx] = sub[c]
-            status[idx] &= np.asarray(st, dtype=np.int64)
-    table = {c: table[c] for c in classes}
-    if extras:
-        table["gray_levels"] = np.array([int((np.asarray(c[1:]) > 0).sum()) for c in counts], dtype=np.int64)
-        if "glcm" in classes:
-            table["glcm_mcc_angles"] = angles
-    _cm._set_batch_route(_joined_route(routes))
-    return table, status.tolist()
-
-
-# ---- the boxes of many labels of one label map in the batch layout (prad_batch_gather_dev, csrc/kernels_batch_gather.h) ---------
-def gather_rois_batch(image, labelmap, labels, lo, hi, masks=True, images=True):
-    """The boxes of B labels cut out of one 3-D volume in ONE launch, packed the way _batch_inputs(..., raw=True) takes them.
-    image / labelmap: device tensors of one shape (either may be None when its output is not asked for); labels int [B]; lo / hi
-    int [B, 3]: inclusive (z, y, x) bounds, as label_census returns them (boxes may overlap).  -> (flat image tensor, flat uint8
-    mask tensor, sizes int32 [B, 3]); the mask of ROI b is labelmap == labels[b] inside its box, the image keeps its dtype where
-    it is one of the four the batched kernels read (float32, float64, int32, int16; anything else is widened to float64) and
-    its values bit for bit.  masks=False / images=False leave that output None.  The label map is narrowed as label_census
-    narrows it.  A box that leaves the volume, hi < lo or tensors on two devices raise ValueError before anything is launched.
-    No read-back and no host synchronisation; the table of boxes stays on the device while consecutive calls repeat it."""
-    lib = _lib.load()
-    if not masks and not images:
-        raise ValueError("gather_rois_batch: neither masks nor images asked for")
-    ref = image if images else labelmap
-    if (images and image is None) or (masks and labelmap is None):
-        raise ValueError("gather_rois_batch: the %s is missing" % ("image" if images and image is None else "label map"))
-    if not ref.is_cuda:
-        raise ValueError("engine.gather_rois_batch expects CUDA/HIP tensors")
-    if images and masks and (not labelmap.is_cuda or image.device != labelmap.device):
-        raise ValueError("gather_rois_batch: image on %s, label map on %s" % (image.device, labelmap.device))
-    if ref.dim() != 3 or (images and masks and image.shape != labelmap.shape):
-        raise ValueError("gather_rois_batch takes a 3-D image and a label map of the same shape")
-    lo = np.ascontiguousarray(np.asarray(lo, dtype=np.int64).reshape(-1, 3))
-    hi = np.ascontiguousarray(np.asarray(hi, dtype=np.int64).reshape(-1, 3))
-    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
-    B = int(lo.shape[0])
-    if B < 1 or hi.shape[0] != B or labels.shape[0] != B:
-        raise ValueError("gather_rois_batch: %d lower bounds, %d upper bounds, %d labels" % (B, hi.shape[0], labels.shape[0]))
-    if (hi < lo).any():
-        raise ValueError("gather_rois_batch: ROI %d has hi < lo" % int(np.flatnonzero((hi < lo).any(1))[0]))
-    if (lo < 0).any() or (hi >= np.asarray(ref.shape, dtype=np.int64)).any():
-        raise ValueError("gather_rois_batch: ROI %d leaves the volume %s"
-                         % (int(np.flatnonzero(((lo < 0) | (hi >= np.asarray(ref.shape))).any(1))[0]), tuple(ref.shape)))
-    if (labels > 2**31 - 1).any() or (labels < -2**31).any():
-        raise ValueError("gather_rois_batch: labels outside the int32 range")
-    if images:
-        image = (image if image.dtype in _DTYPE_CODES else image.to(torch.float64)).contiguous()
-    if masks:
-        labelmap = _label_tensor(labelmap, "gather rois batch")
-    sizes = np.ascontiguousarray((hi - lo + 1).astype(np.intc))
-    off, nvox = _roi_offsets(sizes)
-    total = int(nvox.sum())
-    dev = ref.device
-    _lib.raise_for(lib.prad_set_device(dev.index if dev.index is not None else torch.cuda.current_device()), "set_device")
-    out_i = torch.empty(total, dtype=image.dtype, device=dev) if images else None
-    out_m = torch.empty(total, dtype=torch.uint8, device=dev) if masks else None
-    size = np.array(ref.shape, dtype=np.intc)
-    lo32, lab32 = np.ascontiguousarray(lo.astype(np.intc)), np.ascontiguousarray(labels.astype(np.intc))
-    rc = lib.prad_batch_gather_dev(C.c_void_p(image.data_ptr()) if images else None, _DTYPE_CODES[image.dtype] if images else 0,
-                                   C.c_void_p(labelmap.data_ptr()) if masks else None,
-                                   _LABEL_CODES[labelmap.dtype] if masks else 0, _iptr(size), B,
-                                   _iptr(lab32), _iptr(lo32), _iptr(sizes), _lp(off),
-                                   C.c_void_p(out_i.data_ptr()) if images else None,
-                                   C.c_void_p(out_m.data_ptr()) if masks else None, _stream_ptr())
-    _lib.raise_for(rc, "batched ROI gather")
-    return out_i, out_m, sizes
-
-
 NEIGH_GLDM, NEIGH_NGTDM = 0, 1
 
 
@@ -1775,3 +1117,10 @@ def log_image(image: torch.Tensor, spacing_xyz, sigma: float, normalize: bool = 
             1 if normalize else 0, C.c_void_p(out.data_ptr()), _stream_ptr())
     _lib.raise_for(rc, "LoG")
     return out
+
+
+# ---- many small ROIs in a few launches: the batch route lives in roi_batch.py; its public names are bound here too ----------
+from .roi_batch import (FEATURE_FAMILIES, ROI_FEATURE_CLASSES, batch_digitize_max_edges, batch_features_per_angle,  # noqa: E402,F401
+                        batch_firstorder_max_roi, batch_glszm_max_vox, batch_max_vox, bin_batch, firstorder_batch,
+                        gather_rois_batch, glszm_batch, glszm_batch_zones, last_batch_route, roi_features_batch,
+                        texture_features_batch, texture_matrices_batch, texture_matrices_batch_flat)

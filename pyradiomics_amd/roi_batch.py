@@ -1,0 +1,653 @@
+"""Many small ROIs in a few launches: the device-tensor API of the batch route (csrc/prad_batch*.hip, their shared host layer
+csrc/prad_batch_common.h).  A public function turns its arguments into ONE RoiBatch -- flat buffers holding the boxes back to
+back, their sizes and offsets, the library following the tensors' device -- and hands it to the internal function of the same
+name with a leading underscore; internal functions call internal functions, so nothing is normalised or checked twice.  ROIs
+outside a native call's domain go through the single calls of pyradiomics_amd.engine, which re-exports the public names."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import cmatrices as _cm
+from .cmatrices import _iptr
+
+FEATURE_FAMILIES = ("glcm", "glrlm", "gldm", "ngtdm", "glszm")       # bit f of the C `families` argument, row f of its offsets
+ROI_FEATURE_CLASSES = ("firstorder", "glcm", "glrlm", "glszm", "gldm", "ngtdm")
+_FEATURE_ROW = {"glcm": 24, "glrlm": 16, "gldm": 16, "ngtdm": 5, "glszm": 16}
+_NP_DTYPES = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32, torch.int16: np.int16}
+
+
+def _lp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_longlong))
+
+
+def _vp(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _offsets(counts):
+    """int64 [B]: where each of B pieces of `counts` elements starts when they lie back to back"""
+    off = np.zeros(len(counts), dtype=np.int64)
+    off[1:] = np.cumsum(counts)[:-1]
+    return off
+
+
+def _set_device(lib, dev):
+    """the library context is per thread: follow the tensors' device"""
+    _lib.raise_for(lib.prad_set_device(dev.index if dev.index is not None else torch.cuda.current_device()), "set_device")
+
+
+last_batch_route = _cm.last_batch_route
+
+
+def _route(single, total):
+    """how many of `total` ROIs went through the single calls -> the route's name"""
+    return "batch" if not single else ("looped" if single == total else "mixed")
+
+
+def _joined_route(routes):
+    return routes[0] if all(r == routes[0] for r in routes) else "mixed"
+
+
+class RoiBatch(NamedTuple):
+    """B boxes back to back in flat device buffers, as every batched call takes them"""
+    lib: object
+    data: torch.Tensor       # levels (int32) or raw intensities (float32, float64, int32, int16)
+    mask: torch.Tensor       # uint8, non-zero = ROI
+    sizes: np.ndarray        # intc [B, 3]
+    nvox: np.ndarray         # int64 [B]
+    off: np.ndarray          # int64 [B]: first element of every box
+    device: torch.device
+
+    @property
+    def B(self):
+        return int(self.sizes.shape[0])
+
+    def view(self, flat, b):
+        """box b of a flat buffer in the batch layout, in its 3-D shape"""
+        return flat[int(self.off[b]):int(self.off[b] + self.nvox[b])].view(tuple(int(s) for s in self.sizes[b]))
+
+    def boxes(self, idx):
+        """(image, mask) of the ROIs idx, for the single calls"""
+        return ((self.view(self.data, b), self.view(self.mask, b)) for b in idx)
+
+    def to_device(self, array):
+        """a numpy result of the looped routes, put where the native route's results are"""
+        return torch.from_numpy(array).to(self.device)
+
+    def with_data(self, data):
+        """the same masks and geometry over another flat buffer"""
+        return self._replace(data=data)
+
+    def subset(self, idx):
+        """a batch of the ROIs `idx` alone, packed again (the batch itself where idx names every ROI in order)"""
+        if len(idx) == self.B and np.array_equal(idx, np.arange(self.B)):
+            return self
+        sizes, nvox = np.ascontiguousarray(self.sizes[idx]), self.nvox[idx]
+        pick = lambda flat: torch.cat([flat[int(self.off[b]):int(self.off[b] + self.nvox[b])] for b in idx])
+        return self._replace(data=pick(self.data), mask=pick(self.mask), sizes=sizes, nvox=nvox, off=_offsets(nvox))
+
+
+def _roi_batch(data, masks, sizes, raw=False) -> RoiBatch:
+    """levels / masks as the public functions take them: lists of 3-D device tensors (`sizes` is then ignored), or flat device
+    tensors plus sizes int [B, 3].  raw: intensity images instead of levels; they keep their dtype where it is one of the four the
+    kernels read (float32, float64, int32, int16; anything else, or a list of mixed dtypes, becomes float64)"""
+    def image_dtype(dts):
+        if not raw:
+            return torch.int32
+        return dts[0] if dts[0] in _eng._DTYPE_CODES and all(d == dts[0] for d in dts) else torch.float64
+    if isinstance(data, (list, tuple)):
+        if len(data) != len(masks):
+            raise ValueError("levels and masks differ in number")
+        if any(l.dim() != 3 or l.shape != m.shape for l, m in zip(data, masks)):
+            raise ValueError("the batched matrices take 3-D ROIs with masks of the same shape")
+        sizes = np.array([tuple(l.shape) for l in data], dtype=np.intc).reshape(-1, 3)
+        if not len(data):
+            raise ValueError("empty batch")
+        dt = image_dtype([l.dtype for l in data])
+        data = torch.cat([l.reshape(-1).to(dt) for l in data])
+        masks = torch.cat([(m if m.dtype in (torch.bool, torch.uint8) else m != 0).reshape(-1).view(torch.uint8) for m in masks])
+    elif sizes is None:
+        raise ValueError("flat level / mask tensors need `sizes`")
+    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
+    data, masks = data.reshape(-1), masks.reshape(-1)
+    if not data.is_cuda or not masks.is_cuda:
+        raise ValueError("engine.* expects CUDA/HIP tensors; use pyradiomics_amd.cmatrices for numpy input")
+    data, masks = data.to(image_dtype([data.dtype])).contiguous(), _eng._mask_u8(masks)
+    if data.shape != masks.shape:
+        raise ValueError("Dimensions of image and mask do not match.")
+    lib = _lib.load()
+    _set_device(lib, data.device)
+    nvox = sizes.astype(np.int64).prod(1)
+    if int(nvox.sum()) != data.numel():
+        raise ValueError("sizes describe %d voxels, the buffers hold %d" % (int(nvox.sum()), data.numel()))
+    return RoiBatch(lib, data, masks, sizes, nvox, _offsets(nvox), data.device)
+
+
+# ---- GLCM / GLRLM / GLDM / NGTDM (prad_calculate_batch_dev, csrc/kernels_batch.h) --------------------------------------------
+def batch_max_vox() -> int:
+    """voxels of the largest ROI box the batched call takes (PRAD_BATCH_MAX_VOX)"""
+    return int(_lib.load().prad_batch_max_vox())
+
+
+def _matrices_flat(rois, Ng, families, dist, gldm_a, plan=None):
+    covered, offsets, _ = plan if plan is not None else _cm.batch_plan(rois.sizes, Ng, families, dist)
+    if not covered:
+        return None
+    B, dist = rois.B, np.ascontiguousarray(np.asarray(dist, dtype=np.intc).ravel())
+    flat = {f: torch.empty(int(offsets[_cm.BATCH_FAMILIES.index(f), B]), dtype=torch.float64, device=rois.device) for f in families}
+    status = torch.empty(B, dtype=torch.int32, device=rois.device)
+    ptr = [_vp(flat.get(f)) for f in _cm.BATCH_FAMILIES]
+    rc = rois.lib.prad_calculate_batch_dev(_vp(rois.data), _vp(rois.mask), _iptr(rois.sizes), _lp(rois.off), B, int(Ng),
+                                           _cm.batch_family_bits(families), _iptr(dist), int(dist.shape[0]), int(gldm_a),
+                                           ptr[0], ptr[1], ptr[2], ptr[3], _vp(status), _eng._stream_ptr())
+    if rc == _lib.PRAD_E_UNSUPPORTED:
+        return None
+    _lib.raise_for(rc, "batched texture matrices")
+    _cm._set_batch_route("batch")
+    return flat, status.tolist()
+
+
+def texture_matrices_batch_flat(levels, masks, sizes, Ng, families=_cm.BATCH_FAMILIES, distances=(1,), gldm_a=0):
+    """the native call alone: -> ({family: flat float64 device buffer}, status list), or None when it declines the batch"""
+    return _matrices_flat(_roi_batch(levels, masks, sizes), Ng, tuple(families), list(distances), gldm_a)
+
+
+def _matrices(rois, Ng, families, distances, gldm_a):
+    dist = [int(d) for d in distances]
+    plan = _cm.batch_plan(rois.sizes, Ng, families, dist)
+    shapes = _cm.batch_shapes(rois.sizes, int(Ng), plan[2])
+    res = _matrices_flat(rois, Ng, families, dist, gldm_a, plan)
+    if res is not None:
+        flat, status = res
+        mats = {}
+        for f in families:
+            o = plan[1][_cm.BATCH_FAMILIES.index(f)]
+            mats[f] = [flat[f][int(o[b]):int(o[b + 1])].view(shapes[f][b]) for b in range(rois.B)]
+        return mats, status
+    single = {"glcm": lambda i, m: _eng.glcm(i, m, int(Ng), dist)[0],
+              "glrlm": lambda i, m: _eng.glcm_glrlm(i, m, int(Ng), max(i.shape), want_glcm=False)[1],
+              "gldm": lambda i, m: _eng.gldm(i, m, int(Ng), int(gldm_a), dist),
+              "ngtdm": lambda i, m: _eng.ngtdm(i, m, int(Ng), dist)}
+    return _cm._looped_matrices(rois.boxes(range(rois.B)), int(Ng), families, shapes, single, rois.to_device)
+
+
+def texture_matrices_batch(levels, masks, sizes, Ng, families=_cm.BATCH_FAMILIES, distances=(1,), gldm_a=0):
+    """GLCM / GLRLM / GLDM / NGTDM of B small ROIs in ONE launch (segment mode, 3-D).  levels / masks: lists of 3-D device
+    tensors (concatenated here; `sizes` is then ignored), or flat device tensors holding the ROIs back to back plus `sizes`
+    (int [B, 3]).  -> ({family: [B float64 device tensors, views into one flat buffer, in the single calls' layouts:
+    glcm [Ng, Ng, Na], glrlm [Ng, max(size), Na1], gldm [Ng, 2 * Nb + 1] with Nb = 2 * Na, ngtdm [Ng, 3]]}, status [B]: 1,
+    or 0 for a ROI with a masked level outside [1, Ng] -- the single calls' IndexError; its matrices are void).
+    Covered: Ng <= 64, boxes of at most batch_max_vox() voxels, at most 127 angles; otherwise the single calls are looped ROI
+    by ROI (same results, separate tensors) and last_batch_route() says "looped".  GLSZM: glszm_batch."""
+    return _matrices(_roi_batch(levels, masks, sizes), Ng, tuple(families), distances, gldm_a)
+
+
+# ---- GLSZM (prad_batch_glszm_dev / prad_batch_glszm_fill_dev, csrc/kernels_batch_glszm.h) ------------------------------------
+def batch_glszm_max_vox() -> int:
+    """voxels of the largest ROI box the batched GLSZM takes (PRAD_BATCH_GLSZM_MAX_VOX)"""
+    return int(_lib.load().prad_batch_glszm_max_vox())
+
+
+def _glszm_label(rois, sizes, off, Ng):
+    """the labelling launch on the ROIs (sizes[b], off[b]) of the batch's buffers -> (zones int32 device buffer indexed by
+    2 * off[b], summary int32 numpy [B, 3], status int32 numpy [B]); summary and status come back in ONE copy"""
+    B = int(sizes.shape[0])
+    zones = torch.empty(2 * rois.data.numel(), dtype=torch.int32, device=rois.device)
+    meta = torch.empty(4 * B, dtype=torch.int32, device=rois.device)
+    rc = rois.lib.prad_batch_glszm_dev(_vp(rois.data), _vp(rois.mask), _iptr(sizes), _lp(off), B, int(Ng), _vp(zones), _vp(meta),
+                                       C.c_void_p(meta.data_ptr() + 12 * B), _eng._stream_ptr())
+    _lib.raise_for(rc, "batched GLSZM")
+    host = meta.cpu().numpy()
+    return zones, np.ascontiguousarray(host[:3 * B].reshape(B, 3)), host[3 * B:].copy()
+
+
+class GlszmFlat(NamedTuple):
+    """the device buffers the native route's results of glszm_batch are views of"""
+    P: torch.Tensor                      # float64: the matrices of the covered ROIs back to back
+    covered: np.ndarray                  # indices of those ROIs in the batch
+    out_off: np.ndarray                  # int64 [covered]: first double of each matrix
+    cols: np.ndarray                     # int64 [covered]: columns of each matrix
+    sizes: Optional[torch.Tensor]        # int32: the zone sizes of the compact matrices' columns back to back; None: dense
+    s_off: np.ndarray                    # int64 [covered]: first size of each list, -1 without a zone (one zero column)
+
+
+class _GlszmBatch(list):
+    """the result list of glszm_batch; `flat` (a GlszmFlat, or None) describes the buffers of the native route"""
+    flat = None
+
+
+def glszm_batch_zones(levels, masks, sizes, Ng):
+    """the zone lists of B small ROIs from the labelling launch alone -> (list of B int32 device tensors [nzones, 2] of
+    (level, size) in raster order of each zone's first voxel -- views into one buffer --, summary int32 numpy [B, 3]: zones,
+    largest zone, distinct sizes; status int32 numpy [B]).  Raises NotImplementedError outside the native domain (Ng > 64, a box
+    above batch_glszm_max_vox() voxels)."""
+    rois = _roi_batch(levels, masks, sizes)
+    zones, summary, status = _glszm_label(rois, rois.sizes, rois.off, Ng)
+    _cm._set_batch_route("batch")
+    return [zones[2 * int(o):2 * int(o) + 2 * int(n)].view(-1, 2) for o, n in zip(rois.off, summary[:, 0])], summary, status
+
+
+def _glszm(rois, Ng, compact):
+    Ng, B, dev = int(Ng), rois.B, rois.device
+    covered = np.flatnonzero(rois.nvox <= batch_glszm_max_vox()) if Ng <= 64 else np.zeros(0, dtype=np.int64)
+    results, status = _GlszmBatch([None] * B), [_lib.PRAD_OK] * B
+    if len(covered):
+        coff = np.ascontiguousarray(rois.off[covered])
+        zones, summary, st = _glszm_label(rois, np.ascontiguousarray(rois.sizes[covered]), coff, Ng)
+        cols = np.maximum(summary[:, 2 if compact else 1], 1).astype(np.int64)
+        k = summary[:, 2].astype(np.int64)
+        out_off, s_off = np.append(np.int64(0), np.cumsum(Ng * cols)), np.append(np.int64(0), np.cumsum(k))
+        flat = torch.empty(int(out_off[-1]), dtype=torch.float64, device=dev)
+        sizes_dev = torch.empty(max(int(s_off[-1]), 1), dtype=torch.int32, device=dev)
+        rc = rois.lib.prad_batch_glszm_fill_dev(_vp(zones), _iptr(summary), _lp(coff), len(covered), Ng, 1 if compact else 0,
+                                                _vp(flat), _lp(out_off), _vp(sizes_dev), _lp(s_off), _eng._stream_ptr())
+        _lib.raise_for(rc, "batched GLSZM fill")
+        sizes_host = sizes_dev.cpu().numpy() if compact else None
+        for i, b in enumerate(covered):
+            P = flat[int(out_off[i]):int(out_off[i + 1])].view(Ng, int(cols[i]))
+            results[b] = (P[:, :int(k[i])], sizes_host[s_off[i]:s_off[i + 1]].copy()) if compact else P
+            status[b] = int(st[i])
+        # (batch_features_per_angle evaluates the formulas on these buffers, in place)
+        results.flat = GlszmFlat(flat, covered, out_off[:-1], cols, sizes_dev if compact else None, np.where(k > 0, s_off[:-1], -1))
+    rest = sorted(set(range(B)) - set(int(b) for b in covered))
+    single = lambda i, m, Ns: _eng.glszm_compact(i, m, Ng, Ns) if compact else _eng.glszm(i, m, Ng, Ns)
+    for b, one, st in zip(rest, *_cm._looped_glszm(rois.boxes(rest), Ng, compact, single, rois.to_device)):
+        results[b], status[b] = one, st
+    _cm._set_batch_route("looped" if not len(covered) else _route(len(rest), B))
+    return results, status
+
+
+def glszm_batch(levels, masks, sizes, Ng, compact=True):
+    """GLSZM of B small ROIs in two launches (segment mode, 3-D, the full neighbourhood): zones labelled in LDS by one workgroup
+    per ROI, one read-back of the per-ROI summary, one fill.  Inputs as texture_matrices_batch.  -> (list of B results, status
+    [B]: 1, or 0 for a ROI with a masked level outside [1, Ng] -- the single call's IndexError; its result is that of an empty
+    mask).  compact=True: a result is (P float64 [Ng, k] device tensor, sizes int32 numpy [k] ascending) as glszm_compact
+    returns; compact=False: the dense [Ng, max(maxRegion, 1)] tensor as glszm returns.  The results of the native route are
+    views into one flat buffer.  ROIs above batch_glszm_max_vox() voxels, or every ROI when Ng > 64, go through glszm_compact /
+    glszm one by one (Ns = max(1, masked voxels)); last_batch_route() says "batch", "mixed" or "looped"."""
+    return _glszm(_roi_batch(levels, masks, sizes), Ng, compact)
+
+
+# ---- feature formulas (prad_batch_features_dev, csrc/kernels_batch_features.h) -----------------------------------------------
+def _flat_offsets(tensors):
+    """element offsets of the tensors in the ONE storage they all are contiguous views of (-> base pointer, int64 offsets),
+    or None when they are separate tensors (the looped routes' results)"""
+    if not tensors:
+        return None
+    base = tensors[0].untyped_storage().data_ptr()
+    if any((not t.is_cuda) or t.dtype != torch.float64 or not t.is_contiguous() or t.untyped_storage().data_ptr() != base
+           for t in tensors):
+        return None
+    return base, np.array([t.storage_offset() for t in tensors], dtype=np.int64)
+
+
+def _single_glszm_features(item, Ng):
+    """the single call on one glszm_batch result (compact pair or dense tensor); a ROI without zones is an empty matrix"""
+    P, jv = item if isinstance(item, tuple) else (item, np.arange(1, item.shape[1] + 1))
+    if P.shape[1] == 0:
+        return np.full((1, 16), np.nan), np.ones(1, dtype=bool)
+    return _eng.zone_matrix_features(P, jv)
+
+
+def _single_features(f, M, symmetric, mcc):
+    """family f of one ROI through the single calls -> (float64 [rows, nfeat], bool [rows])"""
+    if f == "ngtdm":
+        return _eng.ngtdm_features(M).reshape(1, 5).copy(), np.array([not bool((M[:, 0] > 0).any().item())])
+    if f == "glcm":
+        Na = int(M.shape[2])
+        vals, empty = (_eng.glcm_features(M, symmetric) if Na else (np.empty((0, 23)), np.zeros(0, dtype=bool)))
+        last = _eng.glcm_mcc(M, symmetric) if (mcc and Na) else np.full(Na, np.nan)
+        return np.concatenate([vals, last.reshape(Na, 1)], axis=1), empty
+    if M.dim() == 3 and M.shape[2] == 0:
+        return np.empty((0, 16)), np.zeros(0, dtype=bool)
+    return _eng.zone_matrix_features(M, np.arange(1, M.shape[1] + 1))
+
+
+def batch_features_per_angle(mats, Ng, glszm=None, symmetric=True, mcc=True):
+    """The feature formulas on the matrices of a batch: `mats` is the dict of texture_matrices_batch, `glszm` the result list of
+    glszm_batch (compact or dense) or None.  -> {family: [B pairs (float64 numpy [rows, nfeat], bool numpy [rows] = matrix
+    empty)]}, rows = angles for glcm (24 columns: the 23 of glcm_features, then glcm_mcc; NaN without `mcc`) and glrlm (16),
+    one row for gldm (16), ngtdm (5; its flag says that no level occurs) and glszm (16): the arrays the single calls return,
+    bit for bit.  Matrices that are views of the flat buffers of the batched calls are evaluated in two launches
+    (prad_batch_features_dev: Ng <= 64); anything else goes through the single calls, one by one."""
+    lib = _lib.load()
+    Ng = int(Ng)
+    fams = [f for f in FEATURE_FAMILIES[:4] if f in mats]
+    B = len(mats[fams[0]]) if fams else len(glszm or [])
+    if any(len(mats[f]) != B for f in fams) or (glszm is not None and len(glszm) != B):
+        raise ValueError("the families differ in their number of ROIs")
+    out = {f: [None] * B for f in fams}
+    if glszm is not None:
+        out["glszm"] = [None] * B
+    views = {f: _flat_offsets(list(mats[f])) for f in fams} if Ng <= 64 else {f: None for f in fams}
+    zflat = getattr(glszm, "flat", None) if (glszm is not None and Ng <= 64) else None
+    native = [f for f in fams if views[f] is not None]
+    if (native or zflat is not None) and B:
+        dev = (mats[native[0]][0] if native else zflat.P).device
+        _set_device(lib, dev)
+        # the angle counts and the longest axis as the matrices' shapes give them (the C call takes them as prad_batch_plan does)
+        Na = np.zeros((2, B), dtype=np.intc)
+        sizes = np.ones((B, 3), dtype=np.intc)
+        for b in range(B):
+            if "glcm" in native:
+                Na[0, b] = mats["glcm"][b].shape[2]
+            elif "gldm" in native:
+                Na[0, b] = (mats["gldm"][b].shape[1] - 1) // 4
+            if "glrlm" in native:
+                sizes[b, 0], Na[1, b] = mats["glrlm"][b].shape[1], mats["glrlm"][b].shape[2]
+        offsets = np.zeros((4, B + 1), dtype=np.int64)
+        ptrs = [None] * 4
+        bits = 0
+        for f in native:
+            i = FEATURE_FAMILIES.index(f)
+            ptrs[i], offsets[i, :B] = C.c_void_p(views[f][0]), views[f][1]
+            bits |= 1 << i
+        cols = np.zeros(B, dtype=np.intc)
+        zoff, soff = np.zeros(B, dtype=np.int64), np.full(B, -1, dtype=np.int64)
+        zptr = sptr = None
+        if zflat is not None:
+            bits |= 16
+            cols[zflat.covered] = zflat.cols
+            zoff[zflat.covered] = zflat.out_off
+            zptr, sptr = _vp(zflat.P), _vp(zflat.sizes)
+            if zflat.sizes is not None:
+                soff[zflat.covered] = zflat.s_off
+        lay = np.zeros((2, 5, B + 1), dtype=np.int64)
+        nrec = np.zeros(3, dtype=np.int64)
+        rc = lib.prad_batch_features_plan(_iptr(sizes), B, Ng, bits, _iptr(Na), _iptr(cols), _lp(lay), _lp(nrec))
+        _lib.raise_for(rc, "batched features plan")
+        nout, nrows = int(lay[0, 4, B]), int(lay[1, 4, B])
+        # values and flags in one device block: one read-back
+        block = torch.empty(nout + (nrows + 1) // 2 + 1, dtype=torch.float64, device=dev)
+        flags = block[nout:].view(torch.int32)
+        rc = lib.prad_batch_features_dev(_iptr(sizes), B, Ng, bits, _iptr(Na), _iptr(cols), ptrs[0], ptrs[1], ptrs[2], ptrs[3],
+                                         _lp(offsets), zptr, _lp(zoff), sptr, _lp(soff), 1 if symmetric else 0, 1 if mcc else 0,
+                                         _vp(block), _vp(flags), _eng._stream_ptr())
+        _lib.raise_for(rc, "batched features")
+        host = block.cpu().numpy()
+        vals, empty = host[:nout], host[nout:].view(np.int32)[:nrows] != 0
+        for f in native + (["glszm"] if zflat is not None else []):
+            i, w = FEATURE_FAMILIES.index(f), _FEATURE_ROW[f]
+            for b in (range(B) if f != "glszm" else zflat.covered):
+                e0, e1, r0, r1 = int(lay[0, i, b]), int(lay[0, i, b + 1]), int(lay[1, i, b]), int(lay[1, i, b + 1])
+                out[f][b] = (vals[e0:e1].reshape(r1 - r0, w).copy(), empty[r0:r1].copy())
+    for f in out:      # whatever the native call did not take
+        for b in range(B):
+            if out[f][b] is None:
+                out[f][b] = _single_glszm_features(glszm[b], Ng) if f == "glszm" else _single_features(f, mats[f][b], symmetric, mcc)
+    return out
+
+
+def _texture_features(rois, Ng, classes, distances, gldm_a, symmetricalGLCM, mcc, mcc_angles):
+    B = rois.B
+    fams = tuple(f for f in FEATURE_FAMILIES[:4] if f in classes)
+    status = np.ones(B, dtype=np.int64)
+    routes = []
+    mats, zones = {}, None
+    if fams:
+        mats, st = _matrices(rois, Ng, fams, distances, gldm_a)
+        routes.append(last_batch_route())
+        status &= np.asarray(st, dtype=np.int64) == _lib.PRAD_OK
+    if "glszm" in classes:
+        zones, st = _glszm(rois, Ng, True)
+        routes.append(last_batch_route())
+        status &= np.asarray(st, dtype=np.int64) == _lib.PRAD_OK
+    per = batch_features_per_angle(mats, Ng, zones, symmetricalGLCM, mcc)
+    table = {}
+    for f in classes:
+        rows = np.full((B, _FEATURE_ROW[f]), np.nan)
+        for b in range(B):
+            if status[b]:
+                vals, empty = per[f][b]
+                rows[b] = vals[0] if f == "ngtdm" else _cm._angle_mean(vals, empty)
+        table[f] = rows
+    if mcc_angles and "glcm" in classes:
+        table["glcm_mcc_angles"] = [per["glcm"][b][0][:, 23].copy() if status[b] else None for b in range(B)]
+    _cm._set_batch_route(_joined_route(routes))
+    return table, status.tolist()
+
+
+def texture_features_batch(levels, masks, sizes, Ng, classes=("glcm", "glrlm", "glszm", "gldm", "ngtdm"),
+                           distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True, mcc_angles=False):
+    """The texture FEATURES of B small ROIs (segment mode, 3-D; inputs as texture_matrices_batch): texture_matrices_batch,
+    glszm_batch(compact=True), the formulas of all matrices in two launches (batch_features_per_angle) and, per ROI, the mean
+    over the angles the reference keeps (cmatrices._angle_mean).  -> ({class: float64 numpy [B, nfeat]}, status [B]): glcm 24
+    columns (cmatrices.VOXEL_GLCM_FEATURES, then MCC -- NaN without `mcc`), glrlm / gldm / glszm 16 (the shared zone numbering),
+    ngtdm 5.  status 0: a masked level outside [1, Ng]; that ROI's rows are NaN, the others are not affected.  weightingNorm is
+    not offered.  Outside the native domain (Ng > 64, boxes above the batch caps) the single calls are looped and give the same
+    values; last_batch_route() says "batch", "mixed" or "looped".  mcc_angles=True adds the entry "glcm_mcc_angles": per ROI the
+    MCC of every angle (float64 [Na], NaN for an empty angle; None with status 0) -- what the feature class averages as a flat
+    vector (cmatrices._mcc_angle_mean), in another order of additions than the column mean of the table."""
+    rois, classes = _roi_batch(levels, masks, sizes), tuple(classes)
+    if not classes or any(c not in FEATURE_FAMILIES for c in classes):
+        raise ValueError("classes must be a non-empty subset of %s" % (FEATURE_FAMILIES,))
+    return _texture_features(rois, Ng, classes, distances, gldm_a, symmetricalGLCM, mcc, mcc_angles)
+
+
+# ---- first-order statistics and discretisation (prad_batch_firstorder_dev / prad_batch_digitize_dev, -------------------------
+# ---- csrc/kernels_batch_firstorder.h): raw intensity boxes in, the table of all six feature classes out ----------------------
+def batch_firstorder_max_roi(dtype) -> int:
+    """most ROI voxels (mask != 0) per ROI the batched first-order launch sorts in LDS: 32768, or 16384 for float64"""
+    code = _eng._DTYPE_CODES[dtype] if dtype in _eng._DTYPE_CODES else int(dtype)
+    return int(_lib.load().prad_batch_firstorder_max_roi(code))
+
+
+def batch_digitize_max_edges() -> int:
+    """most bin edges per ROI the batched discretisation stages in LDS (PRAD_BATCH_DIGITIZE_MAX_EDGES)"""
+    return int(_lib.load().prad_batch_digitize_max_edges())
+
+
+def _firstorder(rois, voxelArrayShift):
+    B = rois.B
+    table = torch.empty((B, 16), dtype=torch.float64, device=rois.device)
+    rc = rois.lib.prad_batch_firstorder_dev(_vp(rois.data), _eng._DTYPE_CODES[rois.data.dtype], _vp(rois.mask), _iptr(rois.sizes),
+                                            _lp(rois.off), B, float(voxelArrayShift), _vp(table), _eng._stream_ptr())
+    if rc == _lib.PRAD_E_UNSUPPORTED:          # nothing was launched: every ROI takes the single call
+        tab = np.full((B, 16), np.nan)
+        tab[:, 15] = 8
+    else:
+        _lib.raise_for(rc, "batched first-order statistics")
+        tab = table.cpu().numpy()              # the batch's first read-back
+    status = tab[:, 15].astype(np.int64)
+    rows = np.ascontiguousarray(tab[:, :15])
+    rest = np.flatnonzero((status == 2) | (status == 8))
+    for b in rest:
+        st = _eng.firstorder_stats(rois.view(rois.data, b), rois.view(rois.mask, b), voxelArrayShift)
+        rows[b] = [st[f] for f in _eng.FIRSTORDER_FIELDS]
+    _cm._set_batch_route(_route(len(rest), B))
+    return rows, status
+
+
+def firstorder_batch(images, masks, sizes=None, voxelArrayShift=0.0):
+    """The first-order statistics of B small ROIs in ONE launch (segment mode, 3-D).  images / masks: lists of 3-D device
+    tensors of one dtype (float32, float64, int32, int16; anything else is widened to float64), or flat device tensors holding
+    the boxes back to back plus `sizes` (int [B, 3]); masks bool or integer, non-zero = ROI.  -> (float64 numpy [B, 15] in the
+    order of FIRSTORDER_FIELDS, status int64 [B] = the launch's verdict per ROI: 0 fine; 1 empty ROI, its row is NaN; 2 a
+    non-finite ROI value and 8 more ROI voxels than batch_firstorder_max_roi(): that ROI's row comes from firstorder_stats).
+    last_batch_route() says "batch", "mixed" (some ROIs went through firstorder_stats) or "looped" (all did)."""
+    return _firstorder(_roi_batch(images, masks, sizes, raw=True), voxelArrayShift)
+
+
+def _bin(rois, stats, binning):
+    from . import imageoperations
+    B, dev = rois.B, rois.device
+    rows, status = _firstorder(rois, 0.0) if stats is None else stats
+    rows, status = np.asarray(rows, dtype=np.float64).reshape(B, -1), np.asarray(status).reshape(B)
+    np_dtype = _NP_DTYPES[rois.data.dtype]
+    cap = batch_digitize_max_edges()
+    edges = [np.zeros(0, dtype=np.float64)] * B
+    single = []
+    edge_off = np.zeros(B + 1, dtype=np.int64)
+    count_off = np.full(B, -1, dtype=np.int64)
+    ncounts = 0
+    i_min, i_max = _eng.FIRSTORDER_FIELDS.index("Minimum"), _eng.FIRSTORDER_FIELDS.index("Maximum")
+    for b in range(B):
+        ne = 0
+        if status[b] == 0:
+            e = np.asarray(imageoperations.getBinEdges(np.array([rows[b, i_min], rows[b, i_max]], dtype=np_dtype), **binning),
+                           dtype=np.float64)
+            if len(e) <= cap:
+                edges[b], ne = e, len(e)
+        if status[b] == 1 or ne:
+            count_off[b] = ncounts
+            ncounts += ne + 1
+        else:
+            single.append(b)
+        edge_off[b + 1] = edge_off[b] + ne
+    levels = torch.empty(rois.data.numel(), dtype=torch.int32, device=dev)
+    counts = [None] * B
+    Ng = np.zeros(B, dtype=np.int64)
+    if len(single) < B:
+        flat_edges = np.concatenate(edges) if edge_off[B] else np.zeros(1, dtype=np.float64)
+        d_edges = torch.from_numpy(flat_edges).to(dev)
+        back = torch.empty(ncounts + (B + 1) // 2, dtype=torch.int64, device=dev)      # [counts | top (int32)]: one read-back
+        top = back[ncounts:].view(torch.int32)
+        rc = rois.lib.prad_batch_digitize_dev(_vp(rois.data), _eng._DTYPE_CODES[rois.data.dtype], _vp(rois.mask),
+                                              _iptr(rois.sizes), _lp(rois.off), B, _vp(d_edges), _lp(edge_off), _vp(levels),
+                                              _vp(back), _lp(count_off), _vp(top), _eng._stream_ptr())
+        _lib.raise_for(rc, "batched discretisation")
+        host = back.cpu().numpy()              # the batch's second read-back
+        tops = host[ncounts:].view(np.int32)
+        for b in range(B):
+            if count_off[b] >= 0:
+                Ng[b] = int(tops[b])
+                counts[b] = host[int(count_off[b]):int(count_off[b]) + int(Ng[b]) + 1].copy()
+    for b in single:
+        lv, ng, e, c = _eng.bin_image(rois.view(rois.data, b), rois.view(rois.mask, b), with_counts=True, **binning)
+        rois.view(levels, b).reshape(-1).copy_(lv.reshape(-1))
+        Ng[b], edges[b], counts[b] = ng, e, c
+    _cm._set_batch_route(_route(len(single), B))
+    return levels, Ng, edges, counts
+
+
+def bin_batch(images, masks, sizes=None, stats=None, **binning):
+    """The discretisation of B small ROIs in ONE launch: every ROI gets its own bin edges -- imageoperations.getBinEdges on its
+    (Minimum, Maximum), as bin_image builds them; binWidth and binCount both work -- and is digitised against them by its own
+    workgroup.  Inputs as firstorder_batch; stats: the (rows, status) pair of firstorder_batch on the same batch (computed here
+    when None).  -> (flat int32 level tensor in the batch layout, Ng int64 [B], list of B float64 edge arrays, list of B int64
+    count arrays [Ng + 1]), ROI by ROI what bin_image(..., with_counts=True) returns.  An empty ROI has Ng 0, no edges, counts
+    [0] and levels 0.  ROIs whose statistics came from the single call (status 2 / 8) or with more than
+    batch_digitize_max_edges() edges go through bin_image; last_batch_route() says "batch", "mixed" or "looped"."""
+    return _bin(_roi_batch(images, masks, sizes, raw=True), stats, binning)
+
+
+def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, binWidth=None, binCount=None, voxelArrayShift=0,
+                       voxelVolume=1.0, distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True, extras=False):
+    """The feature table of B small ROIs from their raw intensity boxes and masks (inputs as firstorder_batch): firstorder_batch
+    and bin_batch -- two launches and two read-backs for the whole batch (binWidth, default 25, or binCount) -- then
+    texture_features_batch once per distinct Ng of the batch on the ROIs that share it.  -> ({class: float64 numpy [B, nfeat]},
+    status [B]): "firstorder" has the 19 columns of cmatrices.FIRSTORDER_FEATURES (firstorder.features_from_stats on the
+    statistics, the level counts and voxelVolume, a number or [B]); the texture classes the columns of texture_features_batch.
+    status 0: an empty ROI; its rows are NaN, the others are not affected.  last_batch_route() says "batch", "mixed" or
+    "looped" (texture_features_batch loops the single calls above 64 levels; MCC is not evaluated there -- its column is NaN
+    for a ROI with more than 64 levels, as without `mcc`).  extras=True adds two entries the label route of the feature extractor
+    needs to report what the feature classes report: "gray_levels" int64 [B], the number of grey levels that occur in the ROI, and
+    (with glcm) "glcm_mcc_angles", see texture_features_batch."""
+    from . import firstorder as _fo
+    rois = _roi_batch(images, masks, sizes, raw=True)
+    classes = tuple(classes)
+    if not classes or any(c not in ROI_FEATURE_CLASSES for c in classes):
+        raise ValueError("classes must be a non-empty subset of %s" % (ROI_FEATURE_CLASSES,))
+    binning = {"binCount": binCount} if binCount is not None else {"binWidth": 25 if binWidth is None else binWidth}
+    B = rois.B
+    routes = []
+    rows, verdict = _firstorder(rois, voxelArrayShift)
+    routes.append(last_batch_route())
+    levels, Ng, _, counts = _bin(rois, (rows, verdict), binning)
+    routes.append(last_batch_route())
+    binned = rois.with_data(levels)
+    status = (verdict != 1).astype(np.int64)
+    table = {}
+    if "firstorder" in classes:
+        vals = _fo.features_from_stats(rows, [c[1:] for c in counts], voxelVolume)
+        vals[status == 0] = np.nan
+        table["firstorder"] = vals
+    texture = tuple(c for c in classes if c != "firstorder")
+    angles = [None] * B
+    if texture:
+        for c in texture:
+            table[c] = np.full((B, _FEATURE_ROW[c]), np.nan)
+        for ng in sorted(set(int(g) for g in Ng[status == 1])):
+            idx = np.flatnonzero((Ng == ng) & (status == 1))
+            sub, st = _texture_features(binned.subset(idx), ng, texture, distances, gldm_a, symmetricalGLCM,
+                                        mcc and ng <= 64,       # (glcm_mcc declines more than 64 occurring levels)
+                                        extras and mcc and ng <= 64)
+            routes.append(last_batch_route())
+            for k, b in enumerate(idx):
+                if "glcm_mcc_angles" in sub:
+                    angles[b] = sub["glcm_mcc_angles"][k]
+            for c in texture:
+                table[c][idx] = sub[c]
+            status[idx] &= np.asarray(st, dtype=np.int64)
+    table = {c: table[c] for c in classes}
+    if extras:
+        table["gray_levels"] = np.array([int((np.asarray(c[1:]) > 0).sum()) for c in counts], dtype=np.int64)
+        if "glcm" in classes:
+            table["glcm_mcc_angles"] = angles
+    _cm._set_batch_route(_joined_route(routes))
+    return table, status.tolist()
+
+
+# ---- the boxes of many labels of one label map in the batch layout (prad_batch_gather_dev, csrc/kernels_batch_gather.h) -------
+def gather_rois_batch(image, labelmap, labels, lo, hi, masks=True, images=True):
+    """The boxes of B labels cut out of one 3-D volume in ONE launch, packed the way the *_batch functions take raw images.
+    image / labelmap: device tensors of one shape (either may be None when its output is not asked for); labels int [B]; lo / hi
+    int [B, 3]: inclusive (z, y, x) bounds, as label_census returns them (boxes may overlap).  -> (flat image tensor, flat uint8
+    mask tensor, sizes int32 [B, 3]); the mask of ROI b is labelmap == labels[b] inside its box, the image keeps its dtype where
+    it is one of the four the batched kernels read (float32, float64, int32, int16; anything else is widened to float64) and
+    its values bit for bit.  masks=False / images=False leave that output None.  The label map is narrowed as label_census
+    narrows it.  A box that leaves the volume, hi < lo or tensors on two devices raise ValueError before anything is launched.
+    No read-back and no host synchronisation; the table of boxes stays on the device while consecutive calls repeat it."""
+    lib = _lib.load()
+    if not masks and not images:
+        raise ValueError("gather_rois_batch: neither masks nor images asked for")
+    ref = image if images else labelmap
+    if (images and image is None) or (masks and labelmap is None):
+        raise ValueError("gather_rois_batch: the %s is missing" % ("image" if images and image is None else "label map"))
+    if not ref.is_cuda:
+        raise ValueError("engine.gather_rois_batch expects CUDA/HIP tensors")
+    if images and masks and (not labelmap.is_cuda or image.device != labelmap.device):
+        raise ValueError("gather_rois_batch: image on %s, label map on %s" % (image.device, labelmap.device))
+    if ref.dim() != 3 or (images and masks and image.shape != labelmap.shape):
+        raise ValueError("gather_rois_batch takes a 3-D image and a label map of the same shape")
+    lo = np.ascontiguousarray(np.asarray(lo, dtype=np.int64).reshape(-1, 3))
+    hi = np.ascontiguousarray(np.asarray(hi, dtype=np.int64).reshape(-1, 3))
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    B = int(lo.shape[0])
+    if B < 1 or hi.shape[0] != B or labels.shape[0] != B:
+        raise ValueError("gather_rois_batch: %d lower bounds, %d upper bounds, %d labels" % (B, hi.shape[0], labels.shape[0]))
+    if (hi < lo).any():
+        raise ValueError("gather_rois_batch: ROI %d has hi < lo" % int(np.flatnonzero((hi < lo).any(1))[0]))
+    if (lo < 0).any() or (hi >= np.asarray(ref.shape, dtype=np.int64)).any():
+        raise ValueError("gather_rois_batch: ROI %d leaves the volume %s"
+                         % (int(np.flatnonzero(((lo < 0) | (hi >= np.asarray(ref.shape))).any(1))[0]), tuple(ref.shape)))
+    if (labels > 2**31 - 1).any() or (labels < -2**31).any():
+        raise ValueError("gather_rois_batch: labels outside the int32 range")
+    if images:
+        image = (image if image.dtype in _eng._DTYPE_CODES else image.to(torch.float64)).contiguous()
+    if masks:
+        labelmap = _eng._label_tensor(labelmap, "gather rois batch")
+    sizes = np.ascontiguousarray((hi - lo + 1).astype(np.intc))
+    nvox = sizes.astype(np.int64).prod(1)
+    total = int(nvox.sum())
+    dev = ref.device
+    _set_device(lib, dev)
+    out_i = torch.empty(total, dtype=image.dtype, device=dev) if images else None
+    out_m = torch.empty(total, dtype=torch.uint8, device=dev) if masks else None
+    size = np.array(ref.shape, dtype=np.intc)
+    lo32, lab32 = np.ascontiguousarray(lo.astype(np.intc)), np.ascontiguousarray(labels.astype(np.intc))
+    rc = lib.prad_batch_gather_dev(_vp(image) if images else None, _eng._DTYPE_CODES[image.dtype] if images else 0,
+                                   _vp(labelmap) if masks else None, _eng._LABEL_CODES[labelmap.dtype] if masks else 0,
+                                   _iptr(size), B, _iptr(lab32), _iptr(lo32), _iptr(sizes), _lp(_offsets(nvox)), _vp(out_i),
+                                   _vp(out_m), _eng._stream_ptr())
+    _lib.raise_for(rc, "batched ROI gather")
+    return out_i, out_m, sizes
+
+
+# (last: engine binds the public names above at its own end, so either module may be the first to be imported)
+from . import engine as _eng  # noqa: E402  the single calls the looped routes use

@@ -400,6 +400,76 @@ def test_host_lists_through_cmatrices():
         assert np.array_equal(fo["firstorder"][name], got["firstorder"][name]), name
 
 
+def _same_bits(a, b, what):
+    """bit for bit, NaNs equal to one another"""
+    if a is None or b is None:
+        assert a is None and b is None, what
+        return
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.shape == b.shape and a.dtype == b.dtype, what
+    if a.dtype.kind == "f":
+        nan = np.isnan(a)
+        assert np.array_equal(nan, np.isnan(b)), what
+        a, b = a[~nan], b[~nan]
+    assert a.tobytes() == b.tobytes(), what
+
+
+def _same_tables(got, want, what):
+    (tg, sg), (tw, sw) = got, want
+    assert sg == sw and list(tg) == list(tw), what
+    for key in tw:
+        if key == "glcm_mcc_angles":
+            assert len(tg[key]) == len(tw[key]), what
+            for b, (x, y) in enumerate(zip(tg[key], tw[key])):
+                _same_bits(x, y, (what, key, b))
+        else:
+            _same_bits(tg[key], tw[key], (what, key))
+
+
+def test_three_ways_to_hand_over_a_batch():
+    """the same three boxes as lists of non-contiguous views with int64 masks, as lists of contiguous tensors with bool masks and
+    as flat tensors plus `sizes`: roi_features_batch (all six classes, extras) and texture_features_batch (int64 levels, Ng = 8)
+    answer the three bit for bit -- tables, gray_levels, glcm_mcc_angles and status"""
+    import torch
+    from pyradiomics_amd import engine
+    rng = np.random.default_rng(4242)
+    shapes = [(2, 3, 5), (7, 4, 3), (1, 1, 4)]
+    imgs = [rng.uniform(0.0, 199.0, s).astype(np.float32) for s in shapes]         # about eight bins of width 25
+    masks = [rng.random(s) < 0.8 for s in shapes]
+    for i, m in zip(imgs, masks):
+        m.flat[0], m.flat[1], m.flat[-1] = True, True, False                       # at least two voxels in, at least one out
+        i.flat[0], i.flat[1] = 1.0, 198.0
+    lvls = [(np.floor(i / 25.0) + 1).astype(np.int64) for i in imgs]
+    assert all(l.min() >= 1 and l.max() <= 8 for l in lvls)
+    sizes = np.array(shapes)
+
+    def strided(a):
+        wide = np.zeros(a.shape[:2] + (2 * a.shape[2],), dtype=a.dtype)
+        wide[:, :, ::2] = a
+        view = torch.from_numpy(wide).cuda()[:, :, ::2]
+        assert not view.is_contiguous() and np.array_equal(view.cpu().numpy(), a)
+        return view
+
+    def ways(arrays):
+        cont = [torch.from_numpy(a).cuda() for a in arrays]
+        return [strided(a) for a in arrays], cont, torch.cat([c.reshape(-1) for c in cont])
+    m64 = [torch.from_numpy(m.astype(np.int64) * 5).cuda() for m in masks]
+    mbool = [torch.from_numpy(m).cuda() for m in masks]
+    mflat = torch.cat([m.reshape(-1) for m in mbool]).view(torch.uint8)
+    a, b, c = ways(imgs)
+    kw = dict(binWidth=25, voxelArrayShift=2.0, voxelVolume=0.5, extras=True)
+    want = engine.roi_features_batch(b, mbool, **kw)
+    assert list(want[0]) == list(engine.ROI_FEATURE_CLASSES) + ["gray_levels", "glcm_mcc_angles"] and want[1] == [1, 1, 1]
+    _same_tables(engine.roi_features_batch(a, m64, **kw), want, "strided views, int64 masks")
+    _same_tables(engine.roi_features_batch(c, mflat, sizes, **kw), want, "flat tensors")
+    a, b, c = ways(lvls)
+    assert a[0].dtype == torch.int64
+    want = engine.texture_features_batch(b, mbool, None, 8, mcc_angles=True)
+    assert want[1] == [1, 1, 1] and "glcm_mcc_angles" in want[0]
+    _same_tables(engine.texture_features_batch(a, m64, None, 8, mcc_angles=True), want, "strided levels, int64 masks")
+    _same_tables(engine.texture_features_batch(c, mflat, sizes, 8, mcc_angles=True), want, "flat levels")
+
+
 def test_zz_report():
     print()
     mine = {k: r for k, r in lim.RATIOS.items() if k[0] in (ROUTE, ROUTE_SINGLE, ROUTE_CLASS)}
