@@ -971,7 +971,103 @@ __device__ void lines_hold_two(const T *__restrict__ L, int Nz, int Ny, int Nx, 
   }
 }
 
-// T / pitch: as multi_check_kernel.  flags / sticky (deferred calls, sticky may be null): the levels verdict of the call
+// scratch of one angle workgroup, per level i of the angle (Ng <= 255): sum (len-1) * runs, runs of length >= 2, voxels N_i
+// (SKIP1), GLRLM_a[i][1]; then the two verdict words.  finalize_volume_kernel keeps it in a __shared__ array of its own, the
+// riding job of sweep_fw_kernel (kernels_sweepfw.h FinJob) carves it from the front of that kernel's dynamic array.
+struct FinScratch {
+  u64 pairs[256], longer[256], nvox[256];
+  u32 run1[256];
+  int found, hit;
+};
+
+// The work of ONE angle workgroup of the finalize, by all threads of the calling workgroup: GLCM diagonal, SKIP1 restore,
+// multi[a] (cheap verdict, else the exact test), column r == 0 of the GLRLM output and, for angle 0, the levels verdict
+// (flags / sticky: deferred calls, sticky may be null).  T / pitch: as multi_check_kernel.  The caller puts a barrier behind it
+// before it touches the scratch again.
+// The tables are read FLAT, up to 40 independent loads per thread in flight (a wave per level with a lane per 64th length is a
+// chain of dependent round trips: 8 per row at Nr = 512, once per level the wave owns); the few non-zero counts go to
+// per-level LDS sums.  Integer sums: the order does not matter.
+template <typename T, int U>
+__device__ __forceinline__ void finalize_angle_work(FinScratch *S, int a, int dz, int dy, int dx, const T *__restrict__ L, int Nz, int Ny,
+                                                    int Nx, int pitch, const u32 *__restrict__ glcm_acc, u32 *glrlm_acc, int Ng, int Nr,
+                                                    int Na, double *__restrict__ glcm_out, double *__restrict__ glrlm_out,
+                                                    int *__restrict__ multi, int restore_from, const int *__restrict__ flags,
+                                                    int *__restrict__ sticky) {
+  const int tid = threadIdx.x, lane = tid & 63, nt = (int)blockDim.x;
+  const int nrun = Ng * Nr, npair = Ng * Ng;   // (the host keeps Ng * Nr below 2^31)
+  const bool restore = restore_from >= 0 && a != restore_from;
+  // (a round of loads costs a memory round trip whatever its size: the first pair rows go out in front of the barrier, both run
+  //  tables together behind it)
+  const u32 *gtab = glcm_acc + (size_t)a * npair;
+  u32 g[U / 2];
+#pragma unroll
+  for (int u = 0; u < U / 2; u++) g[u] = (u * nt + tid < npair) ? gtab[u * nt + tid] : 0u;
+  for (int i = tid; i < 256; i += nt) {
+    S->pairs[i] = 0;
+    S->longer[i] = 0;
+    S->nvox[i] = 0;
+    S->run1[i] = 0;
+  }
+  if (tid == 0) {
+    S->found = multi[a] != 0;   // (a rows kernel of an earlier launch may have set it)
+    S->hit = 0;
+    if (sticky && a == 0 && (flags[0] || flags[2])) sticky[0] = 1;
+  }
+  __syncthreads();
+  int found = 0;
+  u32 *tab = glrlm_acc + (size_t)a * nrun;
+  const u32 *xtab = glrlm_acc + (size_t)(restore ? restore_from : a) * nrun;   // N_i comes from the x angle's complete run table
+  for (int e0 = 0; e0 < nrun; e0 += U * nt) {
+    u32 v[U], x[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) v[u] = (e0 + u * nt + tid < nrun) ? tab[e0 + u * nt + tid] : 0u;
+#pragma unroll
+    for (int u = 0; u < U; u++) x[u] = (restore && e0 + u * nt + tid < nrun) ? xtab[e0 + u * nt + tid] : 0u;
+#pragma unroll
+    for (int u = 0; u < U; u++)
+      if (v[u] | x[u]) {
+        const int e = e0 + u * nt + tid, i = e / Nr, r = e - i * Nr;
+        if (x[u]) atomicAdd(&S->nvox[i], (u64)(r + 1) * x[u]);
+        if (v[u] && r == 0) {
+          S->run1[i] = v[u];
+        } else if (v[u]) {   // a run longer than 1: the angle has a line of two voxels
+          found = 1;
+          atomicAdd(&S->pairs[i], (u64)r * v[u]);
+          atomicAdd(&S->longer[i], (u64)v[u]);
+        }
+      }
+  }
+  // a non-empty off-diagonal row: two adjacent voxels of different levels
+#pragma unroll
+  for (int u = 0; u < U / 2; u++) found |= (g[u] != 0);
+  for (int e0 = (U / 2) * nt; e0 < npair; e0 += (U / 2) * nt) {
+#pragma unroll
+    for (int u = 0; u < U / 2; u++) g[u] = (e0 + u * nt + tid < npair) ? gtab[e0 + u * nt + tid] : 0u;
+#pragma unroll
+    for (int u = 0; u < U / 2; u++) found |= (g[u] != 0);
+  }
+  if (__ballot(found) != 0 && lane == 0) S->found = 1;
+  __syncthreads();
+  int m = S->found;   // uniform: nobody writes it behind the barrier
+  if (!m) {   // every masked voxel isolated along the angle (rare): the exact test of multi_check_kernel
+    lines_hold_two<T>(L, Nz, Ny, Nx, pitch, dz, dy, dx, &S->hit);
+    __syncthreads();
+    m = S->hit;
+  }
+  for (int i = tid; i < Ng; i += nt) {
+    const u64 pairs = S->pairs[i];
+    glcm_out[((size_t)i * Ng + i) * Na + a] = (double)pairs;   // GLCM diagonal: the pairs inside the runs
+    u32 run1 = S->run1[i];
+    if (restore) {   // SKIP1: GLRLM_a[i][1] = N_i - sum_{len >= 2} len * GLRLM_a[i][len]
+      run1 = (u32)(S->nvox[i] - (pairs + S->longer[i]));
+      tab[(size_t)i * Nr] = run1;   // the accumulators hold what the three launches left in them
+    }
+    // cmatrices.c:524-534: an angle without any line of >= 2 masked voxels loses its run-length-1 column
+    glrlm_out[(size_t)i * Nr * Na + a] = m ? (double)run1 : 0.0;
+  }
+  if (tid == 0) multi[a] = m;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(1024) finalize_volume_kernel(AngleSet A, const T *__restrict__ L, int Nz, int Ny, int Nx, int pitch,
                                                                const u32 *__restrict__ glcm_acc, u32 *glrlm_acc,
@@ -979,10 +1075,7 @@ __global__ void __launch_bounds__(1024) finalize_volume_kernel(AngleSet A, const
                                                                double *__restrict__ glrlm_out, int *__restrict__ multi,
                                                                int restore_from, const int *__restrict__ flags,
                                                                int *__restrict__ sticky) {
-  // per level i of the angle (Ng <= 255): sum (len-1) * runs, runs of length >= 2, voxels N_i (SKIP1), GLRLM_a[i][1]
-  __shared__ u64 s_pairs[256], s_longer[256], s_nvox[256];
-  __shared__ u32 s_run1[256];
-  __shared__ int s_found, s_hit;
+  __shared__ FinScratch scratch;
   const int b = blockIdx.x, tid = threadIdx.x;
   if (b >= Na + nbR) {   // off-diagonal GLCM counts -> float64
     const long long idx = (long long)(b - Na - nbR) * blockDim.x + tid;
@@ -1003,82 +1096,8 @@ __global__ void __launch_bounds__(1024) finalize_volume_kernel(AngleSet A, const
     glrlm_out[idx] = (double)glrlm_acc[(size_t)a * Ng * Nr + gr];
     return;
   }
-  // Angle workgroup.  The tables are read FLAT, up to 40 independent loads per thread in flight (a wave per level with a lane per
-  // 64th length is a chain of dependent round trips: 8 per row at Nr = 512, once per level the wave owns); the few non-zero
-  // counts go to per-level LDS sums.  Integer sums: the order does not matter.
-  const int a = b, lane = tid & 63, nt = (int)blockDim.x;
-  const int nrun = Ng * Nr, npair = Ng * Ng;   // (the host keeps Ng * Nr below 2^31)
-  const bool restore = restore_from >= 0 && a != restore_from;
-  // (a round of loads costs a memory round trip whatever its size: the first pair rows go out in front of the barrier, both run
-  //  tables together behind it)
-  const u32 *gtab = glcm_acc + (size_t)a * npair;
-  u32 g[8];
-#pragma unroll
-  for (int u = 0; u < 8; u++) g[u] = (u * nt + tid < npair) ? gtab[u * nt + tid] : 0u;
-  for (int i = tid; i < 256; i += nt) {
-    s_pairs[i] = 0;
-    s_longer[i] = 0;
-    s_nvox[i] = 0;
-    s_run1[i] = 0;
-  }
-  if (tid == 0) {
-    s_found = multi[a] != 0;   // (a rows kernel of an earlier launch may have set it)
-    s_hit = 0;
-    if (sticky && a == 0 && (flags[0] || flags[2])) sticky[0] = 1;
-  }
-  __syncthreads();
-  int found = 0;
-  u32 *tab = glrlm_acc + (size_t)a * nrun;
-  const u32 *xtab = glrlm_acc + (size_t)(restore ? restore_from : a) * nrun;   // N_i comes from the x angle's complete run table
-  for (int e0 = 0; e0 < nrun; e0 += 16 * nt) {
-    u32 v[16], x[16];
-#pragma unroll
-    for (int u = 0; u < 16; u++) v[u] = (e0 + u * nt + tid < nrun) ? tab[e0 + u * nt + tid] : 0u;
-#pragma unroll
-    for (int u = 0; u < 16; u++) x[u] = (restore && e0 + u * nt + tid < nrun) ? xtab[e0 + u * nt + tid] : 0u;
-#pragma unroll
-    for (int u = 0; u < 16; u++)
-      if (v[u] | x[u]) {
-        const int e = e0 + u * nt + tid, i = e / Nr, r = e - i * Nr;
-        if (x[u]) atomicAdd(&s_nvox[i], (u64)(r + 1) * x[u]);
-        if (v[u] && r == 0) {
-          s_run1[i] = v[u];
-        } else if (v[u]) {   // a run longer than 1: the angle has a line of two voxels
-          found = 1;
-          atomicAdd(&s_pairs[i], (u64)r * v[u]);
-          atomicAdd(&s_longer[i], (u64)v[u]);
-        }
-      }
-  }
-  // a non-empty off-diagonal row: two adjacent voxels of different levels
-#pragma unroll
-  for (int u = 0; u < 8; u++) found |= (g[u] != 0);
-  for (int e0 = 8 * nt; e0 < npair; e0 += 8 * nt) {
-#pragma unroll
-    for (int u = 0; u < 8; u++) g[u] = (e0 + u * nt + tid < npair) ? gtab[e0 + u * nt + tid] : 0u;
-#pragma unroll
-    for (int u = 0; u < 8; u++) found |= (g[u] != 0);
-  }
-  if (__ballot(found) != 0 && lane == 0) s_found = 1;
-  __syncthreads();
-  int m = s_found;   // uniform: nobody writes s_found behind the barrier
-  if (!m) {   // every masked voxel isolated along the angle (rare): the exact test of multi_check_kernel
-    lines_hold_two<T>(L, Nz, Ny, Nx, pitch, A.off[a][0], A.off[a][1], A.off[a][2], &s_hit);
-    __syncthreads();
-    m = s_hit;
-  }
-  for (int i = tid; i < Ng; i += nt) {
-    const u64 pairs = s_pairs[i];
-    glcm_out[((size_t)i * Ng + i) * Na + a] = (double)pairs;   // GLCM diagonal: the pairs inside the runs
-    u32 run1 = s_run1[i];
-    if (restore) {   // SKIP1: GLRLM_a[i][1] = N_i - sum_{len >= 2} len * GLRLM_a[i][len]
-      run1 = (u32)(s_nvox[i] - (pairs + s_longer[i]));
-      tab[(size_t)i * Nr] = run1;   // the accumulators hold what the three launches left in them
-    }
-    // cmatrices.c:524-534: an angle without any line of >= 2 masked voxels loses its run-length-1 column
-    glrlm_out[(size_t)i * Nr * Na + a] = m ? (double)run1 : 0.0;
-  }
-  if (tid == 0) multi[a] = m;
+  finalize_angle_work<T, 16>(&scratch, b, A.off[b][0], A.off[b][1], A.off[b][2], L, Nz, Ny, Nx, pitch, glcm_acc, glrlm_acc, Ng, Nr, Na,
+                         glcm_out, glrlm_out, multi, restore_from, flags, sticky);
 }
 
 }  // namespace prad

@@ -21,6 +21,8 @@
 //     recorded exactly once and no stitching pass is needed.
 //   * rows of an angle with dy != 0 are walked wrapped ((u0 + t*dy) mod NU) as in kernels_sweep.h: the wrap is
 //     wave-uniform (all lines of the window end, new ones begin).
+//   * side jobs of the launch: the pack of the NEXT volume (PackJob, interleaved with the walk) and, in front of the walk, the
+//     finalize of the volume BEFORE and the zeroing for the volumes to come (FinJob) -- a steady deferred step is this one launch.
 #pragma once
 #include "kernels_sweep.h"
 
@@ -117,6 +119,39 @@ struct PackJob {
   int NX, Ng;
   int every;          // a wave loads one of its units in front of every `every`-th plain group of its walk
 };
+
+// What else rides in the launch that walks volume N-1 and packs volume N: the FINALIZE of volume N-2 and the ZEROING that
+// volume N (and the pack of N+1) need, so that a steady deferred step is this one launch.  Carried by the line roles'
+// workgroups, with or without a pack job (a volume whose pack cannot ride -- a row length that is no multiple of 16 -- still
+// walks in the pipeline); an empty job (no zero words, Na == 0) costs a few scalar compares.  Three parts,
+// none of which reads anything another workgroup of the same launch writes:
+//   zero     up to three word ranges, stores only, dealt over all threads of the line workgroups.  The host names only words
+//            that no workgroup of THIS launch reads or writes otherwise (prad_api.hip, "workspace sets").
+//   convert  the element-wise part of finalize_volume_kernel for volume N-2 (run counts without column r == 0, off-diagonal
+//            pair counts -> float64), dealt over the same threads; a thread's first load goes out in front of the LDS
+//            zero-init of its workgroup and is stored behind it.
+//   angles   finalize_angle_work (kernels_sweep.h) for angle a of N-2 by the workgroup blockIdx.x == ablock[a], before that
+//            workgroup zeroes its table: the scratch is the front of the dynamic LDS array.  By stream order the accumulators
+//            of N-2 were complete before this launch began.
+struct FinJob {
+  u32 *z[3];            // word ranges to zero
+  unsigned zn[3];
+  int Na;               // angles of volume N-2 (0: no finalize rides)
+  int Ng, Nr, Nz, Ny, Nx, pitch;   // ITS geometry, not the launch's
+  const uint8_t *L;     // its packed levels (the rare exact test reads them)
+  const u32 *glcm_acc;
+  u32 *glrlm_acc;
+  double *glcm_out, *glrlm_out;
+  int *multi;
+  const int *flags;     // its flag words
+  int *sticky;
+  signed char off[PRAD_MAX_SWEEP][3];
+  short ablock[PRAD_MAX_SWEEP];   // workgroup (blockIdx.x, a line workgroup) that does the angle work of angle a
+};
+#define PRAD_FIN_SCRATCH_BYTES ((int)sizeof(FinScratch))
+#ifndef PRAD_FIN_RIDE_U
+#define PRAD_FIN_RIDE_U 8   // run-table loads in flight per thread of a riding angle workgroup
+#endif
 
 #define PRAD_FW_U 8
 #ifndef PRAD_FW_MAXG
@@ -1146,8 +1181,26 @@ __global__ void __launch_bounds__(1024) sweep_fw_rows_kernel(const uint8_t *__re
 // the pack of the NEXT volume as a side job of the walking waves (PackJob; the instantiation without it spares the walk
 // the side job's registers: 0.39 instead of 0.405 ms per 512^3 volume).  A volume whose pack found irregular levels
 // (flags[0]) is skipped -- the generic kernels redo that call -- but the side job still runs.
+// The line roles' workgroups also carry the riding job `fj` (FinJob, above): the finalize of the volume walked one launch
+// earlier and the zeroing for the next volumes, done before the walk so that none of its registers is live in the walk's loops.
+// element e of the riding job's conversion (run counts first, then pair counts; the output index, angle fastest): false for the
+// elements the angle work writes (column r == 0, the diagonal)
+__device__ __forceinline__ bool fin_convert_element(const FinJob &fj, unsigned e, unsigned totR, const u32 *&src, double *&dst) {
+  if (e < totR) {
+    const unsigned gr = e / (unsigned)fj.Na, a = e - gr * (unsigned)fj.Na;
+    src = fj.glrlm_acc + ((size_t)a * fj.Ng * fj.Nr + gr);
+    dst = fj.glrlm_out + e;
+    return gr % (unsigned)fj.Nr != 0;
+  }
+  e -= totR;
+  const unsigned ij = e / (unsigned)fj.Na, a = e - ij * (unsigned)fj.Na, i = ij / (unsigned)fj.Ng, j = ij - i * (unsigned)fj.Ng;
+  src = fj.glcm_acc + ((size_t)a * fj.Ng * fj.Ng + ij);
+  dst = fj.glcm_out + e;
+  return i != j;
+}
+
 template <bool LONG, int K, bool HASPAD, bool PACK>
-__global__ void __launch_bounds__(1024) sweep_fw_kernel(FwSet set, PackJob pj, const uint8_t *__restrict__ L,
+__global__ void __launch_bounds__(1024) sweep_fw_kernel(FwSet set, PackJob pj, FinJob fj, const uint8_t *__restrict__ L,
                                                         const uint8_t *__restrict__ rowzero, int Ng, int Nr, int RS,
                                                         u32 *__restrict__ glcm_acc, u32 *__restrict__ glrlm_acc,
                                                         int *__restrict__ work, int *__restrict__ flags) {
@@ -1194,15 +1247,54 @@ __global__ void __launch_bounds__(1024) sweep_fw_kernel(FwSet set, PackJob pj, c
 #ifdef PRAD_FW_SETPRIO   // experiment: issue priority over co-resident waves of another launch
   __builtin_amdgcn_s_setprio(PRAD_FW_SETPRIO);
 #endif
-  if (flags[0] == 0) {     // (else: irregular levels, nothing to walk)
+  // the riding job (FinJob), in front of everything that belongs to the walk: nothing of it is live once the walk begins
+  u32 cval = 0;
+  double *cdst = nullptr;
+  unsigned gt = 0, nthr = 0, totR = 0, tot = 0;
+  {
+    gt = blockIdx.x * blockDim.x + threadIdx.x;
+    nthr = (unsigned)set.first_block[set.count] * blockDim.x;
+    if (fj.Na > 0) {   // the conversion's first load: it returns under the angle work and the zero-init below
+      totR = (unsigned)fj.Ng * fj.Nr * fj.Na;
+      tot = totR + (unsigned)fj.Ng * fj.Ng * fj.Na;
+      const u32 *src;
+      if (gt < tot && fin_convert_element(fj, gt, totR, src, cdst)) cval = *src;
+      else cdst = nullptr;
+    }
+    const unsigned z01 = fj.zn[0] + fj.zn[1], zt = z01 + fj.zn[2];
+    for (unsigned w = gt; w < zt; w += nthr) {
+      if (w < fj.zn[0]) fj.z[0][w] = 0;
+      else if (w < z01) fj.z[1][w - fj.zn[0]] = 0;
+      else fj.z[2][w - z01] = 0;
+    }
+    for (int a = 0; a < fj.Na; a++)
+      if ((int)fj.ablock[a] == (int)blockIdx.x) {
+        finalize_angle_work<uint8_t, PRAD_FIN_RIDE_U>(reinterpret_cast<FinScratch *>(lds), a, fj.off[a][0], fj.off[a][1], fj.off[a][2], fj.L, fj.Nz, fj.Ny,
+                                     fj.Nx, fj.pitch, fj.glcm_acc, fj.glrlm_acc, fj.Ng, fj.Nr, fj.Na, fj.glcm_out, fj.glrlm_out,
+                                     fj.multi, -1, fj.flags, fj.sticky);
+        __syncthreads();   // (the scratch is the front of the table that is zeroed next)
+      }
+  }
+  const bool walk = flags[0] == 0;     // (else: irregular levels, nothing to walk)
+  const bool lds_at_0 = (unsigned)(size_t)((lds_u32 *)lds) == 0u;   // table offsets are used as LDS addresses
+  const HistLayout h = hist_layout(true, true, true, Ng, RS);
+  if (walk && lds_at_0) {
+    for (int i = threadIdx.x; i < h.words + Ng + 1; i += blockDim.x) lds[i] = 0;
+    __syncthreads();
+    clk.lap<FP_INIT>();
+  }
+  {
+    if (cdst) *cdst = (double)cval;
+    for (unsigned e = gt + nthr; e < tot; e += nthr) {   // (a job larger than the launch: the rest, a round trip each)
+      const u32 *src;
+      if (fin_convert_element(fj, e, totR, src, cdst)) *cdst = (double)*src;
+    }
+  }
+  if (walk) {
     const bool anyzero = flags[3] != 0;   // the pack saw a voxel outside the ROI (else the row flags are not read)
-    const HistLayout h = hist_layout(true, true, true, Ng, RS);
-    if ((unsigned)(size_t)((lds_u32 *)lds) != 0u) {  // table offsets are used as LDS addresses
+    if (!lds_at_0) {
       if (threadIdx.x == 0) atomicExch(flags + 2, 1);
     } else {
-      for (int i = threadIdx.x; i < h.words + Ng + 1; i += blockDim.x) lds[i] = 0;
-      __syncthreads();
-      clk.lap<FP_INIT>();
       const FwDesc &D = set.d[role];
       FwTab T;
       T.init(h, Nr, glrlm_acc + (size_t)D.slot * Ng * Nr);

@@ -648,38 +648,39 @@ int launch_lines(Call &k, const SweepPlan &p, const uint8_t *levels, int Ng, int
 }
 
 template <bool LNG, int K, bool HASPAD, bool PACK>
-int launch_fw_kpp(Call &k, const SweepPlan &p, const PackJob &pj, const uint8_t *levels, const uint8_t *rowzero, int Ng, int Nr,
+int launch_fw_kpp(Call &k, const SweepPlan &p, const PackJob &pj, const FinJob &fj, const uint8_t *levels, const uint8_t *rowzero, int Ng, int Nr,
                   u32 *glcm_acc, u32 *glrlm_acc, int *multi, int *flags_d) {
   // one block size and one LDS size per grid: the x angle's trailing workgroups (table + staging tiles) may need more than the walk's
   const size_t lds = p.fw_xblocks > 0 ? std::max(p.lds_fw, p.lds_fw_rows) : p.lds_fw;
   PRAD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_fw_kernel<LNG, K, HASPAD, PACK>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((sweep_fw_kernel<LNG, K, HASPAD, PACK>), dim3(p.fw_blocks + p.fw_xblocks), dim3(p.fw_threads), lds, k.s, p.fwset, pj,
+  hipLaunchKernelGGL((sweep_fw_kernel<LNG, K, HASPAD, PACK>), dim3(p.fw_blocks + p.fw_xblocks), dim3(p.fw_threads), lds, k.s, p.fwset, pj, fj,
                      levels, rowzero, Ng, Nr, p.RSfw, glcm_acc, glrlm_acc, multi + 2 * PRAD_MAX_SWEEP + PRAD_FW_WORK_STRIDE, flags_d);
   return check_launch("sweep_fw_kernel");
 }
 template <bool LNG, int K, bool HASPAD>
-int launch_fw_kp(Call &k, const SweepPlan &p, const PackJob &pj, const uint8_t *levels, const uint8_t *rowzero, int Ng, int Nr,
+int launch_fw_kp(Call &k, const SweepPlan &p, const PackJob &pj, const FinJob &fj, const uint8_t *levels, const uint8_t *rowzero, int Ng, int Nr,
                  u32 *glcm_acc, u32 *glrlm_acc, int *multi, int *flags_d) {
-  if (pj.n16 > 0) return launch_fw_kpp<LNG, K, HASPAD, true>(k, p, pj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
-  return launch_fw_kpp<LNG, K, HASPAD, false>(k, p, pj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
+  if (pj.n16 > 0) return launch_fw_kpp<LNG, K, HASPAD, true>(k, p, pj, fj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
+  return launch_fw_kpp<LNG, K, HASPAD, false>(k, p, pj, fj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
 }
 template <bool LNG, int K>
-int launch_fw_k(Call &k, const SweepPlan &p, const PackJob &pj, const uint8_t *levels, const uint8_t *rowzero, int Ng, int Nr,
+int launch_fw_k(Call &k, const SweepPlan &p, const PackJob &pj, const FinJob &fj, const uint8_t *levels, const uint8_t *rowzero, int Ng, int Nr,
                 u32 *glcm_acc, u32 *glrlm_acc, int *multi, int *flags_d) {
-  if (p.Nx != 64 * K) return launch_fw_kp<LNG, K, true>(k, p, pj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
-  return launch_fw_kp<LNG, K, false>(k, p, pj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
+  if (p.Nx != 64 * K) return launch_fw_kp<LNG, K, true>(k, p, pj, fj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
+  return launch_fw_kp<LNG, K, false>(k, p, pj, fj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
 }
-// the fixed-window launch of one volume: every line angle and, optionally, the pack of the NEXT volume as a side job
-int launch_fw(Call &k, const SweepPlan &p, const PackJob &pj, const uint8_t *levels, const uint8_t *rowzero, int Ng, int Nr,
+// the fixed-window launch of one volume: every line angle and, optionally, the pack of the NEXT volume as a side job; with a pack,
+// `fj` may carry the finalize of the volume BEFORE and the zeroing for the next ones (FinJob)
+int launch_fw(Call &k, const SweepPlan &p, const PackJob &pj, const FinJob &fj, const uint8_t *levels, const uint8_t *rowzero, int Ng, int Nr,
               u32 *glcm_acc, u32 *glrlm_acc, int *multi, int *flags_d) {
   if (p.fwK == 16)   // rows of 513 .. 1024 voxels: 16 columns per lane
-    return p.LONGfw ? launch_fw_k<true, 16>(k, p, pj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d)
-                    : launch_fw_k<false, 16>(k, p, pj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
-  if (p.LONGfw) return p.fwK == 4 ? launch_fw_k<true, 4>(k, p, pj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d)
-                                : launch_fw_k<true, 8>(k, p, pj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
-  return p.fwK == 4 ? launch_fw_k<false, 4>(k, p, pj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d)
-                    : launch_fw_k<false, 8>(k, p, pj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
+    return p.LONGfw ? launch_fw_k<true, 16>(k, p, pj, fj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d)
+                    : launch_fw_k<false, 16>(k, p, pj, fj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
+  if (p.LONGfw) return p.fwK == 4 ? launch_fw_k<true, 4>(k, p, pj, fj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d)
+                                : launch_fw_k<true, 8>(k, p, pj, fj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
+  return p.fwK == 4 ? launch_fw_k<false, 4>(k, p, pj, fj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d)
+                    : launch_fw_k<false, 8>(k, p, pj, fj, levels, rowzero, Ng, Nr, glcm_acc, glrlm_acc, multi, flags_d);
 }
 
 template <bool LNG, int K, bool HASPAD, bool SKIP1, bool PACK>
@@ -788,8 +789,47 @@ bool fin_side() {
 }
 int fin_wait_for_lane(hipStream_t s, int lane);      // `s` waits for the side-stream finalize that last read workspace set `lane`
 
-// workspace of a volume + the memsets that must precede its pack and its sweeps
-int vol_prepare(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm, VolState &v) {
+// PRAD_FIN_RIDE=0: the finalize of a pipeline volume as a launch of its own behind its walk launch, and zero3_kernel in front of
+// every pack (A/B, and the checker of the riding job); read on every call so that a test can flip it
+bool fin_ride() {
+  const char *e = getenv("PRAD_FIN_RIDE");
+  return !(e && atoi(e) == 0 && e[0] != '\0');
+}
+
+// What a volume needs zeroed: accumulators + control words (before its WALKS), row flags and flag words (before its PACK).
+struct ZeroNeed {
+  u32 *acc = nullptr, *rz = nullptr, *fl = nullptr;
+  size_t acc_w = 0, rz_w = 0, fl_w = 0;
+};
+// What is known about the row flags and the flag words of one of the pipeline's workspace sets.  A walk launch that carries a
+// FinJob re-zeroes what the set's last occupant used; the next occupant then launches no zero3_kernel if it needs no more than
+// that and the buffers are still the same allocations.
+struct SetZero {
+  u32 *rz = nullptr, *fl = nullptr;
+  size_t rz_cap = 0;       // capacity of the row-flag allocation the record describes (a reallocation always grows it)
+  size_t rz_used = 0;      // words the last occupant's pack may have written
+  size_t rz_zero = 0;      // leading words known to be zero
+  bool fl_zero = false;
+};
+constexpr int kPipeSets = 4;   // workspace sets of the pipeline: packed, walked, being finalized, and one that is re-zeroed
+SetZero *set_zero_book() {
+  static thread_local SetZero book[kPipeSets];
+  return book;
+}
+void set_zero_forget() {
+  for (int i = 0; i < kPipeSets; i++) set_zero_book()[i] = SetZero();
+}
+int launch_zero3(hipStream_t s, const ZeroNeed &z) {
+  const size_t total_w = z.acc_w + z.rz_w + z.fl_w;
+  if (total_w == 0) return PRAD_OK;
+  const unsigned gx = (unsigned)std::max<size_t>(1, std::min<size_t>((total_w / 4 + 255) / 256, 1024));
+  hipLaunchKernelGGL(zero3_kernel, dim3(gx), dim3(256), 0, s, z.acc, z.acc_w, z.rz, z.rz_w, z.fl, z.fl_w);
+  return check_launch("zero3_kernel");
+}
+
+// workspace of a volume + the zeroing that must precede its pack and its sweeps.  `defer`: the caller launches (or lets a walk
+// launch carry) what *defer names; without it the volume's zero3_kernel is launched here.
+int vol_prepare(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm, VolState &v, ZeroNeed *defer = nullptr) {
   Context &c = *k.c;
   if (fin_side() && c.lane >= 0) PRAD_TRY(fin_wait_for_lane(k.s, c.lane));
   v.lane = c.lane;
@@ -824,12 +864,32 @@ int vol_prepare(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, doubl
   if (p.fw) PRAD_TRY(c.get<uint8_t>("rowzero", (size_t)nrows + 64, &v.rowzero));
   // accumulators + control words, row flags and the volume's flag words start from zero: ONE launch
   // (three hipMemsetAsync calls are three launches, each with its dependent-launch gap on the stream)
-  const size_t acc_w = nglcm + nglrlm + nctl, rz_w = v.rowzero ? ((size_t)nrows + 3) / 4 : 0;
-  const size_t total_w = acc_w + rz_w + 4;
-  const unsigned gx = (unsigned)std::max<size_t>(1, std::min<size_t>((total_w / 4 + 255) / 256, 1024));
-  hipLaunchKernelGGL(zero3_kernel, dim3(gx), dim3(256), 0, k.s, v.acc, acc_w, reinterpret_cast<u32 *>(v.rowzero), rz_w,
-                     reinterpret_cast<u32 *>(v.flags_d), (size_t)4);
-  return check_launch("zero3_kernel");
+  ZeroNeed z;
+  z.acc = v.acc;
+  z.acc_w = nglcm + nglrlm + nctl;
+  z.rz = reinterpret_cast<u32 *>(v.rowzero);
+  z.rz_w = v.rowzero ? ((size_t)nrows + 3) / 4 : 0;
+  z.fl = reinterpret_cast<u32 *>(v.flags_d);
+  z.fl_w = 4;
+  if (c.lane >= 0 && c.lane < kPipeSets) {   // a set of the pipeline: what an earlier walk launch re-zeroed need not be zeroed again
+    SetZero &S = set_zero_book()[c.lane];
+    const size_t cap = v.rowzero ? c.bufs[c.key("rowzero")].cap : 0;
+    if (fin_ride()) {
+      if (S.rz == z.rz && S.rz_cap == cap && z.rz_w <= S.rz_zero) z.rz_w = 0;
+      if (S.fl == z.fl && S.fl_zero) z.fl_w = 0;
+    }
+    S.rz = z.rz;       // the set is this volume's now: its pack dirties both
+    S.rz_cap = cap;
+    S.rz_used = v.rowzero ? ((size_t)nrows + 3) / 4 : 0;
+    S.rz_zero = 0;
+    S.fl = z.fl;
+    S.fl_zero = false;
+  }
+  if (defer) {
+    *defer = z;
+    return PRAD_OK;
+  }
+  return launch_zero3(k.s, z);
 }
 
 // can this volume's pack ride in another volume's sweep launch?  (linear layout, vector loads)
@@ -896,12 +956,12 @@ int vol_pack_standalone(Call &k, VolState &v) {
 }
 
 template <bool G, bool R, bool F>
-int launch_sweeps(Call &k, const VolState &v, const PackJob &pj) {
+int launch_sweeps(Call &k, const VolState &v, const PackJob &pj, const FinJob &fj) {
   const SweepPlan &p = v.p;
   if (p.lines.count > 0 && p.fw && G && R && F) {
     {
       Timed t(*k.c, "sweep", k.s);
-      PRAD_TRY(launch_fw(k, p, pj, v.levels, v.rowzero, v.Ng, v.Nr, v.glcm_acc, v.glrlm_acc, v.multi, v.flags_d));
+      PRAD_TRY(launch_fw(k, p, pj, fj, v.levels, v.rowzero, v.Ng, v.Nr, v.glcm_acc, v.glrlm_acc, v.multi, v.flags_d));
     }
     if (p.row_slot >= 0 && p.fw_xblocks == 0) {   // (else the x angle ran as the trailing role of that launch)
       Timed t(*k.c, "rows", k.s);
@@ -941,15 +1001,23 @@ int launch_sweeps(Call &k, const VolState &v, const PackJob &pj) {
 }
 
 // the sweeps of volume v; `pj` (n16 > 0) = the pack of another volume as a side job of the fixed-window launch
-int vol_sweep(Call &k, const VolState &v, const PackJob &pj) {
+bool fin_job_empty(const FinJob &fj);
+int vol_sweep(Call &k, const VolState &v, const PackJob &pj, const FinJob &fj) {
   if (pj.n16 > 0 && !pipeline_volume(v.p, v.glcm != nullptr, v.glrlm != nullptr))
     return fail(PRAD_E_ARG, "internal: a pack job needs a fixed-window host launch");
   if (pj.n16 > 0 && (pj.levels16 != nullptr) != v.p.fw2)
     return fail(PRAD_E_ARG, "internal: the pack job's layout is not the host launch's");
-  if (v.glcm && v.glrlm && v.p.fused) return launch_sweeps<true, true, true>(k, v, pj);
-  if (v.glcm && v.glrlm) return launch_sweeps<true, true, false>(k, v, pj);
-  if (v.glcm) return launch_sweeps<true, false, false>(k, v, pj);
-  return launch_sweeps<false, true, false>(k, v, pj);
+  if (!fin_job_empty(fj) && !(v.glcm && v.glrlm && v.p.fused && v.p.fw && v.p.lines.count > 0))
+    return fail(PRAD_E_ARG, "internal: a finalize job needs a fused-table host launch");
+  if (v.glcm && v.glrlm && v.p.fused) return launch_sweeps<true, true, true>(k, v, pj, fj);
+  if (v.glcm && v.glrlm) return launch_sweeps<true, true, false>(k, v, pj, fj);
+  if (v.glcm) return launch_sweeps<true, false, false>(k, v, pj, fj);
+  return launch_sweeps<false, true, false>(k, v, pj, fj);
+}
+int vol_sweep(Call &k, const VolState &v, const PackJob &pj) {
+  FinJob none;
+  memset(&none, 0, sizeof(none));
+  return vol_sweep(k, v, pj, none);
 }
 
 __global__ void latch_flags_kernel(const int *__restrict__ flags, int *__restrict__ sticky) {
@@ -1065,13 +1133,33 @@ int sweep_glcm_glrlm(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, 
   return PRAD_OK;
 }
 
-// ---- deferred calls as a two-stage pipeline (the default deferred mode; PRAD_DEFERRED_MODE=lanes selects the lanes) -------
+// ---- deferred calls as a pipeline (the default deferred mode; PRAD_DEFERRED_MODE=lanes selects the lanes) ----------------
 // A deferred whole-volume call N launches { walks of volume N-1 + pack of volume N } as ONE fixed-window launch (the pack
-// is a side job of the walking waves: kernels_sweepfw.h PackJob), then the x angle and the finalize of volume N-1.  Volume
-// N itself stays PENDING (packed, not yet walked) until the next deferred call or until prad_deferred_status /
-// prad_deferred_join flush it.  Two workspace sets alternate (Context::lane selects the set; the stream is the caller's).
+// is a side job of the walking waves: kernels_sweepfw.h PackJob).  Volume N itself stays PENDING (packed, not yet walked) until
+// the next deferred call or until prad_deferred_status / prad_deferred_join / prad_deferred_mark flush it.
+//
+// Fused-table volumes (<= 44 levels) go one stage further: volume N-1 is not finalized behind its walk launch but stays WALKED,
+// and the NEXT walk launch -- the one of call N+1, which walks N and packs N+1 -- carries its finalize and the zeroing for the
+// volumes to come as a riding job (FinJob), so a steady step is ONE launch: no zero3_kernel, no finalize_volume_kernel.  The
+// job rides only in a fused-table launch on the same stream; otherwise (a two-table volume, another stream,
+// PRAD_FW_XROLE=0, PRAD_FINALIZE_ONE=0, PRAD_FIN_RIDE=0, any flush) the stand-alone finalize of the walked volume is launched
+// FIRST, as before.  Every path that drains the pipeline (pipeline_flush) finishes the walked volume too, so the contract is
+// unchanged: outputs are valid after prad_deferred_status, prad_deferred_join or a mark.  The two-table route (45 - 160 levels)
+// is untouched: its volumes are finalized behind their walk launch.
+//
+// Workspace sets.  Three volumes are in flight -- packed, walked, being finalized (whose LEVELS the rare exact test reads) -- so
+// FOUR sets alternate (Context::lane = seq % 4; the stream is the caller's).  Launch N walks N-1 (set N-1), packs N (set N),
+// finalizes N-2 (set N-2) and zeroes
+//   * the accumulators and control words of set N: used by the walks of N in launch N+1, last read by the finalize of N-4;
+//   * the row flags and the four flag words of set N+1 = set N-3: written by the pack of N+1 in launch N+1, last read in
+//     launches N-2 (row flags, walks of N-3) and N-1 (flag words, finalize of N-3).
+// INVARIANT: no launch contains a word that one workgroup zeroes and any other workgroup of that launch reads or writes.
+// It holds by construction: make_fin_job names a range only after comparing its SET with the sets of the three volumes the
+// launch works on, and everything earlier is ordered by the stream.  A set remembers what is known to be zero (SetZero):
+// vol_prepare launches zero3_kernel only for the rest (the first volumes of a run, a grown buffer, more rows than were re-zeroed).
 struct PipeState {
   VolState pending;
+  VolState walked;              // walked, not finalized: its finalize rides in the next walk launch or runs stand-alone first
   hipStream_t s = nullptr;      // stream the pending volume's pack was enqueued on
   unsigned long long seq = 0;
   hipEvent_t ev = nullptr;
@@ -1095,9 +1183,113 @@ bool pipeline_mode() {
 }
 int pipeline_sticky(Context &c, int **sticky) { return c.get<int>("deferred_sticky", 16, sticky); }
 
-// walks + finalize of the pending volume on stream s (pj: the next volume's pack as a side job, or n16 == 0)
-int pipeline_retire(Context &c, hipStream_t s, const PackJob &pj) {
+bool fin_job_empty(const FinJob &fj) { return fj.Na == 0 && fj.zn[0] + fj.zn[1] + fj.zn[2] == 0; }
+
+// can the finalize of v ride in a walk launch?  (the conditions of the one-launch finalize, a walk launch that is the volume's
+// last, and the job's 32-bit element indices)
+bool fin_can_ride(const VolState &v) {
+  const SweepPlan &p = v.p;
+  if (!(v.glcm && v.glrlm && p.fw && p.fused && p.lines.count > 0 && v.levels && v.lane >= 0 && v.lane < kPipeSets)) return false;
+  if (p.row_slot >= 0 && p.fw_xblocks == 0) return false;   // (PRAD_FW_XROLE=0: the x angle is a launch behind the walk launch)
+  if (!finalize_one() || (long long)v.Ng * v.Nr >= (1LL << 30) || v.Ng > 255 || v.Na > PRAD_MAX_SWEEP || v.Na != p.aset.count) return false;
+  return ((long long)v.Ng * v.Nr + (long long)v.Ng * v.Ng) * v.Na < (1LL << 31);
+}
+// can the walk launch of `host` on stream s carry a FinJob?  (with or without a pack job pj)
+bool fin_host_ok(const PipeState &ps, const VolState &host, const PackJob &pj, hipStream_t s) {
+  const SweepPlan &p = host.p;
+  if (!(fin_ride() && !fin_side() && ps.s == s && host.glcm && host.glrlm && p.fw && p.fused && p.lines.count > 0)) return false;
+  const size_t lds = p.fw_xblocks > 0 ? std::max(p.lds_fw, p.lds_fw_rows) : p.lds_fw;   // (as launch_fw_kpp)
+  return lds >= (size_t)PRAD_FIN_SCRATCH_BYTES && p.fw_blocks >= 1 && p.fw_blocks < 32768;
+}
+
+// The riding job of the launch that walks `host` and packs the volume of set `new_lane`: the finalize of `walked` (or none) and
+// the zeroing of `need` (the new volume's accumulators; or none) and of the NEXT set's row flags and flag words.  Each range is
+// named only if its set is none of the sets this launch works on (see the invariant above).
+FinJob make_fin_job(const VolState &host, const VolState *walked, const ZeroNeed *need, int new_lane) {
+  FinJob j;
+  memset(&j, 0, sizeof(j));
+  const int nline = host.p.fw_blocks;
+  if (walked) {
+    const VolState &w = *walked;
+    j.Na = w.Na;
+    j.Ng = w.Ng;
+    j.Nr = w.Nr;
+    j.Nz = w.p.Nz;
+    j.Ny = w.p.Ny;
+    j.Nx = w.p.Nx;
+    j.pitch = w.p.pitch;
+    j.L = w.levels;
+    j.glcm_acc = w.glcm_acc;
+    j.glrlm_acc = w.glrlm_acc;
+    j.glcm_out = w.glcm;
+    j.glrlm_out = w.glrlm;
+    j.multi = w.multi;
+    j.flags = w.flags_d;
+    // Placement of the 13 angle workgroups (each starts its walk ~7 us late; the role's chunk hand-out makes up for it).
+    // 0: angle a on workgroup a / count of role a % count.  1: all on the roles whose waves finish first.  2: evenly over the grid.
+    static const int place = getenv("PRAD_FIN_PLACE") ? atoi(getenv("PRAD_FIN_PLACE")) : 0;
+    const FwSet &fs = host.p.fwset;
+    static const int early[4] = {1, 4, 3, 10};   // (profiles/r05_fw_phases.md, wave life by role)
+    for (int a = 0; a < w.Na; a++) {
+      for (int d = 0; d < 3; d++) j.off[a][d] = (signed char)w.p.aset.off[a][d];
+      int role = a % fs.count, idx = a / fs.count;
+      if (place == 1 && fs.count > 10) {
+        role = early[a % 4];
+        idx = a / 4;
+      }
+      int b = (fs.first_block[role] + idx < fs.first_block[role + 1]) ? fs.first_block[role] + idx : a % nline;
+      if (place == 2) b = (int)((long long)a * nline / w.Na);
+      j.ablock[a] = (short)b;
+    }
+  }
+  const int wl = walked ? walked->lane : -1;
+  size_t words = 0;
+  if (need && need->acc_w > 0 && new_lane >= 0 && new_lane < kPipeSets && new_lane != host.lane && new_lane != wl) {
+    j.z[0] = need->acc;
+    j.zn[0] = (unsigned)need->acc_w;
+    words += need->acc_w;
+  }
+  if (new_lane >= 0 && new_lane < kPipeSets) {
+    const int t = (new_lane + 1) % kPipeSets;
+    SetZero &S = set_zero_book()[t];
+    if (t != host.lane && t != wl && t != new_lane && S.rz_zero < S.rz_used && S.rz) {
+      j.z[1] = S.rz;
+      j.zn[1] = (unsigned)S.rz_used;
+      words += S.rz_used;
+      S.rz_zero = S.rz_used;
+    }
+    if (t != host.lane && t != wl && t != new_lane && S.fl && !S.fl_zero) {
+      j.z[2] = S.fl;
+      j.zn[2] = 4;
+      S.fl_zero = true;
+    }
+  }
+  (void)words;
+  return j;
+}
+
+// the stand-alone finalize of the walked volume on stream s (ordered behind its walk launch by the caller)
+int pipeline_finish_walked(Context &c, hipStream_t s) {
   PipeState &ps = pipe_state();
+  if (!ps.walked.valid) return PRAD_OK;
+  Call k;
+  k.c = &c;
+  k.s = s;
+  k.Na = ps.walked.Na;
+  k.flags_d = ps.walked.flags_d;
+  int *sticky = nullptr;
+  PRAD_TRY(pipeline_sticky(c, &sticky));
+  PRAD_TRY(vol_finalize(k, ps.walked, sticky));
+  ps.walked.valid = false;
+  return PRAD_OK;
+}
+
+// walks of the pending volume on stream s (pj: the next volume's pack as a side job, or n16 == 0) and its finalize -- at once, or,
+// with `keep`, left to the next walk launch (the volume becomes `walked`).  The finalize of the volume walked BEFORE rides in
+// this launch if it can, else it is launched first.  need / new_lane: the zeroing the next volume still asks for and its set.
+int pipeline_retire(Context &c, hipStream_t s, const PackJob &pj, bool keep = false, const ZeroNeed *need = nullptr, int new_lane = -1) {
+  PipeState &ps = pipe_state();
+  const bool host_ok = fin_host_ok(ps, ps.pending, pj, s);   // (before ps.s moves)
   if (ps.s != s) {   // the pack ran on another stream: order the two on the device
     if (!ps.ev) PRAD_HIP(hipEventCreateWithFlags(&ps.ev, hipEventDisableTiming));
     PRAD_HIP(hipEventRecord(ps.ev, ps.s));
@@ -1110,11 +1302,33 @@ int pipeline_retire(Context &c, hipStream_t s, const PackJob &pj) {
   k.flags_d = ps.pending.flags_d;
   int *sticky = nullptr;
   PRAD_TRY(pipeline_sticky(c, &sticky));
-  PRAD_TRY(vol_sweep(k, ps.pending, pj));
+  FinJob fj;
+  memset(&fj, 0, sizeof(fj));
+  if (host_ok) {
+    const bool rides = ps.walked.valid && fin_can_ride(ps.walked) && ps.walked.lane != ps.pending.lane && ps.walked.lane != new_lane;
+    if (ps.walked.valid && !rides) PRAD_TRY(pipeline_finish_walked(c, s));
+    fj = make_fin_job(ps.pending, rides ? &ps.walked : nullptr, need, new_lane);
+    fj.sticky = sticky;
+    ps.walked.valid = false;   // (enqueued with the launch below)
+  } else {
+    PRAD_TRY(pipeline_finish_walked(c, s));
+  }
+  if (need && need->acc_w > 0 && fj.zn[0] == 0) {   // (the job did not take the accumulators: their set is one the launch works on)
+    ZeroNeed acc;
+    acc.acc = need->acc;
+    acc.acc_w = need->acc_w;
+    PRAD_TRY(launch_zero3(s, acc));
+  }
+  PRAD_TRY(vol_sweep(k, ps.pending, pj, fj));
+  if (keep && fin_ride() && !fin_side() && fin_can_ride(ps.pending)) {
+    ps.walked = ps.pending;
+    ps.pending.valid = false;
+    return PRAD_OK;
+  }
   if (fin_side() && ps.pending.lane >= 0 && ps.pending.lane < 4) {
     // The three finalize launches (13 us + their launch gaps per 512^3 volume) need a handful of workgroups and no LDS: on a
     // side stream they run under the next volume's walk launch instead of in front of it.  The accumulators they read belong to
-    // workspace set `lane`: with THREE alternating sets the next volume that zeroes this set is two steps away.
+    // workspace set `lane`: with more than two alternating sets the next volume that zeroes this set is two steps away.
     if (!ps.fin) {
       PRAD_HIP(hipStreamCreateWithFlags(&ps.fin, hipStreamNonBlocking));
       PRAD_HIP(hipEventCreateWithFlags(&ps.fin_in, hipEventDisableTiming));
@@ -1154,14 +1368,15 @@ int fin_join(hipStream_t s, bool host) {
   return PRAD_OK;
 }
 
-// nothing pending afterwards (kernels enqueued on the pending volume's own stream; no host synchronisation)
+// nothing pending or walked afterwards (kernels enqueued on the pending volume's own stream; no host synchronisation)
 int pipeline_flush(Context &c) {
   PipeState &ps = pipe_state();
-  if (!ps.pending.valid) return PRAD_OK;
+  if (!ps.pending.valid && !ps.walked.valid) return PRAD_OK;
   PackJob none;
   memset(&none, 0, sizeof(none));
   const size_t before = c.times.size();
-  PRAD_TRY(pipeline_retire(c, ps.s, none));
+  if (ps.pending.valid) PRAD_TRY(pipeline_retire(c, ps.s, none));
+  else PRAD_TRY(pipeline_finish_walked(c, ps.s));
   if (c.timing_accumulate) c.all_times.insert(c.all_times.end(), c.times.begin() + (long)before, c.times.end());
   return PRAD_OK;
 }
@@ -1174,7 +1389,8 @@ int pipeline_step(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, dou
   *handled = false;
   if (!pipeline_volume(p, glcm != nullptr, glrlm != nullptr)) return pipeline_flush(c);
   VolState v;
-  PRAD_TRY(vol_prepare(k, p, Ng, Nr, glcm, glrlm, v));
+  ZeroNeed need;
+  PRAD_TRY(vol_prepare(k, p, Ng, Nr, glcm, glrlm, v, &need));
   PackJob pj;
   memset(&pj, 0, sizeof(pj));
   bool inl = false;
@@ -1182,7 +1398,18 @@ int pipeline_step(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, dou
     // (the side job writes the layout of the launch it rides in: fused-table and two-table volumes do not mix)
     inl = pack_inline_ok(k, v) && ps.pending.p.fw2 == v.p.fw2 && !getenv("PRAD_NO_INLINE_PACK");
     if (inl) pj = make_pack_job(k, v, &ps.pending);
-    PRAD_TRY(pipeline_retire(c, k.s, pj));
+    // the walk launch zeroes the accumulators of this volume itself if it carries a job; what the pack needs zeroed goes first
+    const bool ride = fin_host_ok(ps, ps.pending, pj, k.s) && need.acc_w + need.rz_w + need.fl_w < ((size_t)1 << 30);
+    ZeroNeed now = need;
+    if (ride) {
+      now.acc_w = 0;
+      need.rz_w = need.fl_w = 0;
+    }
+    PRAD_TRY(launch_zero3(k.s, now));
+    PRAD_TRY(pipeline_retire(c, k.s, pj, true, ride ? &need : nullptr, v.lane));
+  } else {
+    PRAD_TRY(pipeline_finish_walked(c, ps.s));   // (a walked volume without a pending one: only after a failed call)
+    PRAD_TRY(launch_zero3(k.s, need));
   }
   if (!inl) PRAD_TRY(vol_pack_standalone(k, v));
   v.packed_inline = inl;
@@ -1315,8 +1542,11 @@ int texture_pairs_runs(const int32_t *image, const uint8_t *mask, const int *siz
     ~LaneGuard() { c.lane = -1; }
   } lane_guard{c};
   bool pipe = c.deferred && !voxels && pipeline_mode();
-  if (c.deferred && !voxels && !pipe) PRAD_TRY(c.lane_begin(s, &s));   // lanes mode: whole-volume deferred calls alternate between lanes
-  if (pipe) c.lane = (int)(pipe_state().seq++ % (fin_side() ? 3u : 2u));   // pipeline mode: the workspace sets alternate (three with the finalize side stream), the stream is the caller's
+  if (c.deferred && !voxels && !pipe) {   // lanes mode: whole-volume deferred calls alternate between lanes
+    PRAD_TRY(c.lane_begin(s, &s));
+    if (c.lane >= 0) c.lane += kPipeSets;   // (workspace sets of their own: #0 .. #3 belong to the pipeline)
+  }
+  if (pipe) c.lane = (int)(pipe_state().seq++ % (unsigned)kPipeSets);   // pipeline mode: four workspace sets alternate (see the pipeline's header), the stream is the caller's
   Call k;
   PRAD_TRY(setup_call(k, image, mask, size, Nd, angles, Na, Nvox, voxels, kernelRadius, force2Ddim, s, false));
   SweepPlan p = plan_sweep(k, Ng, Nr, glcm != nullptr, glrlm != nullptr);
@@ -1329,7 +1559,7 @@ int texture_pairs_runs(const int32_t *image, const uint8_t *mask, const int *siz
     pipe = false;
     c.lane = -1;
     PRAD_TRY(c.lane_begin(user, &s));
-    if (c.lane >= 0) c.lane += fin_side() ? 3 : 2;      // (workspace sets of their own: #0 / #1 (/ #2) belong to the pipeline's alternating volumes)
+    if (c.lane >= 0) c.lane += kPipeSets;      // (workspace sets of their own: #0 .. #3 belong to the pipeline's alternating volumes)
     PRAD_TRY(setup_call(k, image, mask, size, Nd, angles, Na, Nvox, voxels, kernelRadius, force2Ddim, s, false));
     p = plan_sweep(k, Ng, Nr, glcm != nullptr, glrlm != nullptr);
   }
@@ -1898,12 +2128,14 @@ int prad_set_device(int device) {
   if (device < 0 || device >= n) return fail(PRAD_E_ARG, "device %d not in [0,%d)", device, n);
   Context &c = ctx();
   if (c.device != device) {
-    if (pipe_state().pending.valid && c.device_set && hipSetDevice(c.device) == hipSuccess) {
-      (void)pipeline_flush(c);   // a volume still pending on the old device: retire it there
+    if ((pipe_state().pending.valid || pipe_state().walked.valid) && c.device_set && hipSetDevice(c.device) == hipSuccess) {
+      (void)pipeline_flush(c);   // a volume still pending or walked on the old device: retire it there
       if (pipe_state().s) (void)hipStreamSynchronize(pipe_state().s);
       (void)fin_join(nullptr, true);
     }
     pipe_state().pending.valid = false;
+    pipe_state().walked.valid = false;
+    set_zero_forget();
     pipe_state().s = nullptr;
     pipe_state().ev = nullptr;
     pipe_state().fin = nullptr;      // (the side stream and its events belonged to the old device)
@@ -1934,12 +2166,14 @@ void release_image_queues();     // (prad_image_enqueue_dev's streams and events
 }
 int prad_release_workspace(void) {
   Context &c = ctx();
-  if (pipe_state().pending.valid) {        // the pending volume's buffers are about to go away: retire it first
+  if (pipe_state().pending.valid || pipe_state().walked.valid) {   // their buffers are about to go away: retire them first
     (void)pipeline_flush(c);
     if (pipe_state().s) (void)hipStreamSynchronize(pipe_state().s);
     (void)fin_join(nullptr, true);
     pipe_state().pending.valid = false;
+    pipe_state().walked.valid = false;
   }
+  set_zero_forget();                      // (what was known to be zero lived in the workspace)
   glszm_state().valid = false;            // its zone list lives in the workspace
   for (auto &kv : c.bufs) {
     if (kv.second.p) (void)hipFree(kv.second.p);
