@@ -187,6 +187,25 @@ int prad_get_angle_count(const int *size, const int *distances, int Nd, int Ndis
 int prad_build_angles(const int *size, const int *distances, int Nd, int Ndist, int force2Ddim, int Na,
                       int *angles);
 
+/* ---- debug: the sweep plan of a segment-mode GLCM / GLRLM call (no device call, no launch) ----------------------------
+ * Plans for a volume of `size` ([Nd], Nd <= 3 for a plan), the HOST angle list `angles` ([Na][Nd]), Ng levels and Nr run
+ * lengths as a real call does -- the environment's switches included -- with `cus` compute units (<= 0: the device's count,
+ * 256 without a device).  Writes the plan to out[0 .. cap) as ints and returns how many it wrote; -(the count needed) when
+ * cap is too small; 0 for arguments no call accepts.  The record:
+ *   ok                                   0: the call takes another route, and the record ends here
+ *   Nz Ny Nx  fused fw fw2 fw2_rows
+ *   RS RSr RSfw RSfw_rows RS2 RS2r  LONG LONGr LONGfw LONGfw2 LONGfw2r
+ *   lds_bytes lds_bytes_rows lds_fw lds_fw_rows lds_fw2 lds_fw2_rows
+ *   threads fw_threads fw_rows_threads fwK fw_blocks fw2_copies fw2r_copies fw2r_waves
+ *   LPL pitch padw pitch16 vec_rows  skip1 row_slot fw_xblocks
+ *   lines.count, then per line angle:    slot NM NU NX du dx sM sU LXc chunks
+ *   aset.count, then per angle:          its offset (z, y, x)
+ *   has_fwset (fw or fw2), and if 1:     count NX pitch nrows xcd  first_block[17]  xslot xRS xwaves xgpd,
+ *                                        then per line angle: slot NM NU du dx sM sU CL pieces chunks dom_kind
+ * (64-bit strides and chunk counts are narrowed to int.)  tests/test_sweep_plan.py pins these records. */
+int prad_debug_sweep_plan(const int *size, int Nd, const int *angles, int Na, int Ng, int Nr, int want_glcm, int want_glrlm,
+                          int cus, int *out, int cap);
+
 /* ---- GLCM: calculate_glcm (cmatrices.c:4-92) ---------------------------------------------------- */
 /* glcm: float64 [Nvox][Ng][Ng][Na] */
 int prad_calculate_glcm(const int32_t *image, const uint8_t *mask, const int *size, int Nd,

@@ -55,6 +55,7 @@ SYMBOLS = {
     "prad_deferred_mark": (C.c_int, [C.POINTER(C.c_int), C.c_void_p]),
     "prad_get_angle_count": (C.c_int, [_ip, _ip, C.c_int, C.c_int, C.c_int, C.c_int]),
     "prad_build_angles": (C.c_int, [_ip, _ip, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
+    "prad_debug_sweep_plan": (C.c_int, [_ip, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_int]),
     "prad_calculate_glcm": (C.c_int, _COMMON + [C.c_int] + _VOX + [_vp]),
     "prad_calculate_glcm_dev": (C.c_int, _COMMON + [C.c_int] + _VOX + [_vp, _vp]),
     "prad_calculate_glrlm": (C.c_int, _COMMON + [C.c_int, C.c_int] + _VOX + [_vp]),

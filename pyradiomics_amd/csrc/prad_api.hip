@@ -20,7 +20,8 @@
 #include "kernels_voxslide.h"
 #include "kernels_mcc.h"
 #include "kernels_voxtex.h"
-#include "kernels_binning.h"
+#include "prad_sweep_plan.h"
+#include "prad_internal.h"
 
 #include <algorithm>
 #include <atomic>
@@ -36,9 +37,10 @@
 using namespace prad;
 
 namespace {
-
 const char *kVersion = "pyradiomics_amd 0.1.0 (gfx950)";
+}  // namespace
 
+namespace prad {   // (prad_internal.h: prad_image.hip enumerates the angles of an image too)
 // ------------------------------------------------------------------------------------------------
 // angle enumeration (cmatrices.c:756-892), host side: tiny, integer, runs once per call
 // ------------------------------------------------------------------------------------------------
@@ -100,6 +102,10 @@ int angle_build(const int *size, const int *distances, int Nd, int Ndist, int f2
   }
   return got == Na ? 0 : 1;
 }
+static_assert(kMaxSweepAngles == PRAD_MAX_SWEEP, "prad_internal.h: kMaxSweepAngles");
+}  // namespace prad
+
+namespace {
 
 // ------------------------------------------------------------------------------------------------
 // call setup shared by all matrices
@@ -247,58 +253,6 @@ int generic_ngtdm(Call &k, int Ng, double *out) {
 // ------------------------------------------------------------------------------------------------
 // sweep path (segment mode GLCM / GLRLM)
 // ------------------------------------------------------------------------------------------------
-struct SweepPlan {
-  bool ok = false;
-  int Nz = 1, Ny = 1, Nx = 1;  // volume embedded in 3-D
-  SweepSet lines;              // angles marching along z or y
-  int row_slot = -1;           // slot of the angle along x, or -1
-  bool skip1 = false;          // two-table walk: runs of length 1 are not recorded, finalize restores them from the x angle's runs
-  bool fused = false;          // one [prev][len][cur] table instead of separate GLCM / GLRLM tables
-  int LPL = 1;                 // lines per lane of the lines kernel (1, 2, 4)
-  int pitch = 0, padw = 0;     // row pitch / periodic pad of the packed level volume
-  bool vec_rows = false;       // Nx multiple of 16: vector pack and vector row staging
-  AngleSet aset;               // all angles embedded in 3-D (for multi_check_kernel)
-  // lines kernel configuration
-  int RS = 0;                  // GLRLM run lengths kept in LDS (>= Nr: every length, no long-run path)
-  bool LONG = false;
-  int threads = 256;
-  size_t lds_bytes = 0;
-  // rows kernel configuration (512 threads, 8 staging tiles behind the histograms)
-  int RSr = 0;
-  bool LONGr = false;
-  size_t lds_bytes_rows = 0;
-  // fixed-window lines kernel (kernels_sweepfw.h): rows of 65..512 voxels, fused table
-  bool fw = false;
-  int fwK = 8;                 // window columns per lane (4: rows up to 256, 8: up to 512)
-  int fw_blocks = 1;           // workgroups per angle
-  int fw_threads = 1024;       // threads per workgroup of the fixed-window launch
-  int fw_rows_threads = 512;   // ... and of the x angle's launch (sweep_fw_rows_kernel: one staging tile per wave)
-  int RSfw = 0;                // run-length slots of its table (one workgroup per CU: most of the 160 KB)
-  bool LONGfw = false;
-  size_t lds_fw = 0;
-  int RSfw_rows = 0;           // length slots of the rows role's table (it shares the LDS with 16 staging tiles)
-  size_t lds_fw_rows = 0;      // the x angle as a launch of its own (sweep_fw_rows_kernel)
-  int fw_xblocks = 0;          // > 0: the x angle is the trailing role of the fixed-window launch, this many workgroups behind fw_blocks
-  // two-table fixed-window kernel (kernels_sweepfw2.h): 45+ grey levels
-  bool fw2 = false;
-  int RS2 = 0;                 // run-length slots per level row
-  int fw2_copies = 1;          // copies of the run-length slots in a row (lane l uses copy l mod copies)
-  bool LONGfw2 = false;
-  size_t lds_fw2 = 0;
-  int pitch16 = 0;             // bytes per row of the 16-bit level volume
-  // the x angle of a two-table volume on the 16-bit levels (sweep_fw2_rows_kernel): table + one staging tile per wave
-  bool fw2_rows = false;
-  int RS2r = 0, fw2r_copies = 1, fw2r_waves = 16;
-  bool LONGfw2r = false;
-  size_t lds_fw2_rows = 0;
-  FwSet fwset;
-};
-
-constexpr size_t kHistBudget = 72 * 1024;      // LDS bytes a lines workgroup may spend on histograms
-constexpr size_t kHistBudgetRows = 36 * 1024;  // same for a rows workgroup (which also holds staging tiles)
-constexpr int kRowsThreads = 512;
-constexpr size_t kHistBudgetFw = 146 * 1024;   // fixed-window kernel: one 16-wave workgroup per CU (+ its dead zone)
-
 int cu_count() {
   static thread_local int cus = 0;
   if (!cus) {
@@ -310,313 +264,26 @@ int cu_count() {
   return cus;
 }
 
-// largest RS (<= Nr) whose table fits `budget` bytes; -1 if not even RS = 1 fits
-int fit_rs(bool glcm, bool glrlm, bool fused, int Ng, int Nr, size_t budget) {
-  int lo = 0, hi = Nr;
-  if (sizeof(u32) * (size_t)hist_layout(glcm, glrlm, fused, Ng, 1).words > budget) return -1;
-  lo = 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (sizeof(u32) * (size_t)hist_layout(glcm, glrlm, fused, Ng, mid).words <= budget) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// Can this call run on the sweep kernels?  (see the dispatch policy at the top of this file)
-SweepPlan plan_sweep(const Call &k, int Ng, int Nr, bool want_glcm, bool want_glrlm) {
-  SweepPlan p;
-  if (k.vm.voxels || k.g.nd > 3 || Ng < 1 || Ng > 255 || k.Na > PRAD_MAX_SWEEP) return p;
-  int dims[3] = {1, 1, 1};
-  for (int d = 0; d < k.g.nd; d++) dims[3 - k.g.nd + d] = k.g.size[d];
-  p.Nz = dims[0]; p.Ny = dims[1]; p.Nx = dims[2];
-  const int longest = std::max(dims[0], std::max(dims[1], dims[2]));
-  if (want_glrlm && Nr < longest) return p;  // a run could overflow Nr
-  if (!want_glrlm) Nr = 1;
-  // fused table when both matrices are wanted and it holds run lengths up to at least min(Nr, 8)
-  if (want_glcm && want_glrlm) {
-    const int rs = fit_rs(true, true, true, Ng, Nr, kHistBudget);
-    const int rsr = fit_rs(true, true, true, Ng, Nr, kHistBudgetRows);
-    if (Ng <= (255 >> PRAD_FUSED_SHIFT) && rs >= std::min(Nr, 8) && rsr >= std::min(Nr, 4)) {
-      p.fused = true;
-      p.RS = rs;
-      p.RSr = rsr;
-    }
-  }
-  // Two-table fixed-window kernel for the line angles when the fused table does not fit (45+ levels): rows that one wave
-  // window covers, a level row [Ng + 1 pairs | RS2 lengths] table within the LDS, and the rows kernel (separate tables, here
-  // with up to 100 KB for them) for the angle along x
-  const bool force_fw2 = getenv("PRAD_FORCE_FW2") != nullptr && Ng >= 8;   // experiment: the two-table kernel at any level count
-  if (force_fw2 && want_glcm && want_glrlm && p.Nx > 64 && p.Nx <= 512) p.fused = false;
-  if (want_glcm && want_glrlm && !p.fused && (Ng >= 40 || force_fw2) && p.Nx > 64 && p.Nx <= 512 && !getenv("PRAD_NO_FW2")) {
-    // run-length slots per level row and copies of them (lane l adds to copy l mod C): as many copies as leave >= 32 slots
-    // (or every length), slots capped at 64 -- longer runs take the checked path, and empty slots cost zeroing and flushing
-    const long long maxwords = (158 * 1024) / 4;
-    const long long room = maxwords / (Ng + 1) - (Ng + 1);
-    int copies = 1;
-    long long rs2 = std::min<long long>(room, Nr);
-    for (int cc = 8; cc >= 2; cc >>= 1)
-      if (room / cc >= std::min<long long>(32, Nr)) {
-        copies = cc;
-        rs2 = std::min<long long>(std::min<long long>(room / cc, 64), Nr);
-        break;
-      }
-    if (const char *e = getenv("PRAD_FW2_COPIES")) {   // tuning override
-      copies = std::max(1, std::min(8, atoi(e)));
-      rs2 = std::min<long long>(std::min<long long>(room / copies, copies > 1 ? 64 : Nr), Nr);
-    }
-    if (const char *e = getenv("PRAD_FW2_RS")) rs2 = std::min<long long>(rs2, atoll(e));   // tuning override
-    if (rs2 < Nr && ((Ng + 1 + copies * rs2) & 1) == 0) rs2--;      // odd row stride: consecutive levels on different banks
-    const int rsr = fit_rs(true, true, false, Ng, Nr, 116 * 1024);   // (+ 40 KB of staging tiles: within the 160 KB)
-    if ((rs2 >= 24 || rs2 >= Nr) && rs2 >= 1 && rsr >= std::min(Nr, 4)) {
-      p.fw2 = true;
-      p.skip1 = getenv("PRAD_FW2_NOSKIP1") == nullptr;   // (needs the x angle in the call: cleared below when it is not)
-      p.RS2 = (int)rs2;
-      p.LONGfw2 = rs2 < Nr;
-      p.fw2_copies = copies;
-      p.lds_fw2 = 4 * fw2_table_words(Ng, p.RS2, copies);
-      p.RS = 0;
-      p.RSr = rsr;
-      // the x angle with the same two tables (round 5): as many waves (16, 8, 4 -- the walk is a serial chain per lane) as
-      // leave the table next to their 5 KB staging tiles >= 32 length slots (4 waves: >= 24); else the rows kernel of
-      // kernels_sweep.h on the 8-bit copy as before
-      for (int waves = 16; waves >= 4 && !p.fw2_rows && !getenv("PRAD_NO_FW2_ROWS"); waves >>= 1) {
-        if (const char *e = getenv("PRAD_FW2_ROWS_WAVES")) {   // tuning override
-          if (atoi(e) != waves) continue;
-        }
-        const long long mw = ((158 * 1024) - (long long)waves * 64 * PRAD_ROW16_PITCH) / 4;
-        const long long rm = mw / (Ng + 1) - (Ng + 1);
-        if (rm < std::min<long long>(waves > 4 ? 32 : 24, Nr)) continue;
-        int cc = 1;
-        long long r2 = std::min<long long>(std::min<long long>(rm, 64), Nr);
-        for (int c2 = 4; c2 >= 2; c2 >>= 1)
-          if (rm / c2 >= std::min<long long>(32, Nr)) {
-            cc = c2;
-            r2 = std::min<long long>(std::min<long long>(rm / c2, 64), Nr);
-            break;
-          }
-        if (r2 < Nr && ((Ng + 1 + cc * r2) & 1) == 0) r2--;      // odd row stride, as above
-        if (r2 < 1) continue;
-        p.fw2_rows = true;
-        p.RS2r = (int)r2;
-        p.fw2r_copies = cc;
-        p.fw2r_waves = waves;
-        p.LONGfw2r = r2 < Nr;
-        p.lds_fw2_rows = ((4 * fw2_table_words(Ng, p.RS2r, cc) + 15) & ~(size_t)15) + (size_t)waves * 64 * PRAD_ROW16_PITCH;
-      }
-    }
-  }
-  if (!p.fused && !p.fw2) {
-    p.RS = want_glrlm ? fit_rs(want_glcm, true, false, Ng, Nr, kHistBudget) : 0;
-    p.RSr = want_glrlm ? fit_rs(want_glcm, true, false, Ng, Nr, kHistBudgetRows) : 0;
-    if (p.RS < 0 || p.RSr < 0) return p;
-    if (!want_glrlm && sizeof(u32) * (size_t)hist_layout(true, false, false, Ng, 0).words > kHistBudgetRows) return p;
-  }
-  p.LONG = want_glrlm && p.RS < Nr;
-  p.LONGr = want_glrlm && p.RSr < Nr;
-  p.lds_bytes = sizeof(u32) * (size_t)hist_layout(want_glcm, want_glrlm, p.fused, Ng, p.RS).words;
-  p.threads = p.lds_bytes <= 20 * 1024 ? 256 : (p.lds_bytes <= 40 * 1024 ? 512 : 1024);
-  if (const char *e = getenv("PRAD_THREADS")) {  // tuning/ablation override
-    const int v = atoi(e);
-    if (v == 256 || v == 512 || v == 1024) p.threads = v;
-  }
-  const size_t hw = (size_t)hist_layout(want_glcm, want_glrlm, p.fused, Ng, p.RSr).words;
-  p.lds_bytes_rows = sizeof(u32) * ((hw + 3) & ~(size_t)3) + (kRowsThreads / 64) * 64 * PRAD_ROW_PITCH;
-  // packed layout: each lane of the lines kernel owns LPL adjacent lines; rows get a periodic pad of one wave width
-  // Lines per lane: more lines amortise the per-step overhead (a chunk of 256 / 128 / 64 lines costs about
-  // 1.0 / 0.575 / 0.33 per step), fewer lines waste less of a partial last chunk and give the dynamic hand-out more,
-  // smaller chunks.  Estimate the walk time of one angle as (chunks per wave + half a chunk of tail) x chunk cost.
-  {
-    const double waves = std::max(1.0, (double)(cu_count() / std::max(1, std::min(k.Na, 12))) * 16.0);
-    const double cost[3] = {1.0, 0.575, 0.33};
-    const int cand[3] = {4, 2, 1};
-    double best = 1e300;
-    p.LPL = 1;
-    for (int i = 0; i < 3; i++) {
-      if (cand[i] > 1 && p.Nx < 48 * cand[i]) continue;        // lanes would mostly idle
-      const double chunks = (double)std::max(p.Ny, 1) * ((p.Nx + 64 * cand[i] - 1) / (64 * cand[i]));
-      const double t = (chunks <= waves ? 1.0 : chunks / waves + 0.5) * cost[i];
-      if (t < best) {
-        best = t;
-        p.LPL = cand[i];
-      }
-    }
-  }
-  if (const char *e = getenv("PRAD_LPL")) {  // tuning/ablation override
-    const int v = atoi(e);
-    if (v == 1 || v == 2 || v == 4) p.LPL = v;
-  }
-  p.vec_rows = (p.Nx % 16) == 0;
-  // fixed-window kernel: needs the fused table and rows that one wave window (64 lanes x 4 or 8 columns) covers
-  p.fw = p.fused && p.Nx > 64 && p.Nx <= 1024 && !getenv("PRAD_NO_FW");
-  if (p.Nx > 512 && getenv("PRAD_NO_FW16")) p.fw = false;
-  if (const char *e = getenv("PRAD_FW_MINVOX")) p.fw = p.fw && k.g.n >= atoll(e);
-  p.fwK = p.Nx <= 256 ? 4 : (p.Nx <= 512 ? 8 : 16);
-  if (p.fw2) p.fwK = p.Nx <= 256 ? 4 : 8;
-  p.padw = (p.fw || p.fw2) ? 0 : std::min(64 * p.LPL, p.Nx);
-  p.pitch16 = 2 * ((p.Nx + 7) & ~7);
-  p.pitch = (p.Nx + p.padw + 15) & ~15;   // 16-byte aligned rows: vector staging in the rows kernel for any Nx
-  p.lines.count = 0;
-  p.aset.count = k.Na;
-  for (int a = 0; a < k.Na; a++) {
-    int o[3] = {0, 0, 0};
-    for (int d = 0; d < k.g.nd; d++) o[3 - k.g.nd + d] = k.angles_h[a * k.g.nd + d];
-    int first = 0;
-    for (int d = 0; d < 3; d++) {
-      if (o[d] < -1 || o[d] > 1) return p;
-      if (!first && o[d]) first = o[d];
-      p.aset.off[a][d] = o[d];
-    }
-    if (first != 1) return p;  // sweeps assume the first moving component is +1 (unidirectional list)
-    if (o[0] == 0 && o[1] == 0) {
-      if (p.row_slot >= 0) return p;
-      p.row_slot = a;
-      continue;
-    }
-    SweepDesc &D = p.lines.d[p.lines.count++];
-    D.slot = a;
-    D.NX = p.Nx;
-    D.dx = o[2];
-    if (o[0] == 1) {  // march z, rows = y
-      D.NM = p.Nz; D.NU = p.Ny; D.du = o[1];
-      D.sM = (long long)p.Ny * p.pitch; D.sU = p.pitch;
-    } else {          // march y, rows = z (never moves)
-      D.NM = p.Ny; D.NU = p.Nz; D.du = 0;
-      D.sM = p.pitch; D.sU = (long long)p.Ny * p.pitch;
-    }
-    D.LXc = (p.Nx + 64 * p.LPL - 1) / (64 * p.LPL);
-    D.chunks = (long long)D.NU * D.LXc;
-  }
-  if ((p.fw || p.fw2) && p.lines.count > 0) {
-    size_t budget = kHistBudgetFw;
-    if (const char *e = getenv("PRAD_FW_BUDGET_KB")) budget = (size_t)std::max(8, atoi(e)) * 1024;   // tuning override
-    p.RSfw = fit_rs(true, true, true, Ng, Nr, budget);
-    // LDS bank of a bin = (row stride * prev + len + cur) mod 32 with row stride = (RS+1)(Ng+1) words.  On smooth images
-    // cur ~ prev +- 1, so the banks of one ds_add spread like (stride+1) * prev: give up a few length slots for a stride
-    // whose (stride+1) is odd and 5..11 banks away from 0 (512^3 smooth levels: 0.74 ms at stride = 0 mod 32, 0.57 ms at 22)
-    if (p.RSfw < Nr) {
-      for (int rs = p.RSfw; rs >= std::max(16, p.RSfw - 12); rs--) {
-        const int d = (((rs + 1) * (Ng + 1)) % 32 + 1) % 32, dist = std::min(d, 32 - d);
-        if ((d & 1) && dist >= 5 && dist <= 11) {
-          p.RSfw = rs;
-          break;
-        }
-      }
-    }
-    if (const char *e = getenv("PRAD_FW_RS")) p.RSfw = std::max(1, std::min(p.RSfw, atoi(e)));   // tuning override
-    p.LONGfw = p.RSfw < Nr;
-    p.lds_fw = fw_lds_bytes(hist_layout(true, true, true, Ng, p.RSfw));
-    if (p.row_slot >= 0 && p.fw) {   // the x angle: a launch of its own, 8 waves + their staging tiles (sweep_fw_rows_kernel)
-      if (const char *e = getenv("PRAD_FW_ROWS_THREADS")) p.fw_rows_threads = std::max(64, std::min(1024, atoi(e) & ~63));   // tuning override
-      const size_t tiles = (size_t)(p.fw_rows_threads / 64) * 64 * PRAD_ROW_PITCH;
-      int rs = fit_rs(true, true, true, Ng, Nr, std::min<size_t>(100 * 1024, (size_t)160 * 1024 - 2048 - tiles));
-      for (int r = rs; rs < Nr && r >= std::max(16, rs - 12); r--) {   // same bank-stride rule as above
-        const int d = (((r + 1) * (Ng + 1)) % 32 + 1) % 32, dist = std::min(d, 32 - d);
-        if ((d & 1) && dist >= 5 && dist <= 11) { rs = r; break; }
-      }
-      p.RSfw_rows = rs;
-      p.lds_fw_rows = ((fw_lds_bytes(hist_layout(true, true, true, Ng, rs)) + 15) & ~(size_t)15) + tiles;
-    }
-    int nroles_x = 0;
-    {
-      // Roles of the one launch (kernels_sweepfw.h sweep_fw_kernel): one per line angle, one 16-wave workgroup per CU over
-      // all of them (1-D grid; the remainder of the division goes to the first roles)
-      const int nroles = p.lines.count;
-      nroles_x = nroles;
-      int total = cu_count();
-      if (const char *e = getenv("PRAD_FW_BLOCKS")) total = std::max(nroles, atoi(e));   // tuning override: workgroups of the launch
-      if (const char *e = getenv("PRAD_FW_THREADS")) p.fw_threads = std::max(64, std::min(1024, atoi(e) & ~63));   // ... and their size
-      // The remainder of the division goes to the roles that cost most per line (round 5b): the wave life by role of
-      // profiles/r05_fw_phases.md x the workgroups each role had gives 19.5 - 19.6 (lines that drift in x AND wrap in the row
-      // dimension), 18.8 - 19.2 (one of the two), 18.1 - 18.5 (neither); until then the first `total % nroles` roles of the
-      // angle list took it -- two of the light ones among them -- and the launch waited for role 6 (PRAD_FW_EXTRA_FIRST=1: as then)
-      int bonus[PRAD_MAX_SWEEP] = {0};
-      {
-        int left = total % nroles;
-        const bool as_listed = getenv("PRAD_FW_EXTRA_FIRST") != nullptr;
-        for (int cls = as_listed ? 0 : 2; cls >= 0 && left > 0; cls--)
-          for (int r = 0; r < nroles && left > 0; r++) {
-            const SweepDesc &S = p.lines.d[r];
-            const int c = (S.dx != 0 ? 1 : 0) + (S.du != 0 ? 1 : 0);
-            if ((as_listed || c == cls) && !bonus[r]) {
-              bonus[r] = 1;
-              left--;
-            }
-          }
-      }
-      p.fwset.first_block[0] = 0;
-      for (int r = 0; r < nroles; r++) p.fwset.first_block[r + 1] = p.fwset.first_block[r] + total / nroles + bonus[r];
-      for (int r = nroles + 1; r < PRAD_MAX_SWEEP + 1; r++) p.fwset.first_block[r] = p.fwset.first_block[nroles];
-      p.fw_blocks = p.fwset.first_block[nroles];
-    }
-    // The x angle of a fused-table GLCM + GLRLM call: trailing workgroups of the same launch (kernels_sweepfw.h sweep_fw_kernel),
-    // as many as its own launch would have, shaped like that launch's (fw_rows_threads / 64 walking waves, one staging tile each,
-    // behind a table of RSfw_rows length slots).  PRAD_FW_XROLE=0: the two launches, as before.
-    p.fwset.xslot = -1;
-    p.fwset.xRS = 0;
-    p.fwset.xwaves = 0;
-    p.fwset.xgpd = 1;
-    {
-      const char *e = getenv("PRAD_FW_XROLE");
-      if (p.fw && p.fused && p.row_slot >= 0 && p.fw_threads == 1024 && !(e && atoi(e) == 0)) {
-        const long long groups = fw_row_groups((long long)p.Nz * p.Ny);
-        const int wpb = p.fw_rows_threads / 64;
-        long long xb = std::min<long long>((groups + wpb - 1) / wpb, (long long)cu_count());
-        if (const char *b = getenv("PRAD_FW_XBLOCKS")) xb = std::min<long long>(atoll(b), 4096);   // tuning override
-        p.fw_xblocks = (int)std::max<long long>(1, xb);
-        p.fwset.first_block[nroles_x + 1] = p.fw_blocks + p.fw_xblocks;
-        p.fwset.xslot = p.row_slot;
-        p.fwset.xRS = p.RSfw_rows;
-        p.fwset.xwaves = wpb;
-        p.fwset.xgpd = 1;   // (groups per pull: more only coarsens the hand-out, see fw_rows_role)
-        if (const char *g = getenv("PRAD_FW_XGPD")) p.fwset.xgpd = std::max(1, std::min(64, atoi(g)));   // tuning override
-      }
-    }
-    int per_wave = 6;
-    if (const char *e = getenv("PRAD_FW_PER_WAVE")) per_wave = std::max(1, atoi(e));
-    p.fwset.count = p.lines.count;
-    p.fwset.NX = p.Nx;
-    // XCD-aware chunk hand-out (kernels_sweepfw.h): opt-in -- it takes the fabric reads of the level volume from 10.2 to 3.9
-    // per volume at 512^3 but its 8 shorter pieces cost 4 % of time (profiles/r03_probes.md), and time is the metric
-    p.fwset.xcd = 0;
-    if (const char *e = getenv("PRAD_FW_XCD")) p.fwset.xcd = ((p.fw || p.fw2) && p.Nz >= 64 && atoi(e) != 0) ? 1 : 0;
-    for (int i = 0; i < p.lines.count; i++) {
-      const SweepDesc &S = p.lines.d[i];
-      FwDesc &D = p.fwset.d[i];
-      D.slot = S.slot; D.NM = S.NM; D.NU = S.NU; D.du = S.du; D.dx = S.dx; D.sM = S.sM; D.sU = S.sU;
-      p.fwset.pitch = p.pitch;
-      if (p.fw2) {   // byte strides of the 16-bit level volume
-        const bool march_z = S.sM >= S.sU;
-        D.sM = march_z ? (long long)p.Ny * p.pitch16 : p.pitch16;
-        D.sU = march_z ? p.pitch16 : (long long)p.Ny * p.pitch16;
-        p.fwset.pitch = p.pitch16;
-      }
-      p.fwset.nrows = p.Nz * p.Ny;
-      const long long want = (long long)per_wave * (p.fwset.first_block[i + 1] - p.fwset.first_block[i]) * (p.fw_threads / 64);
-      int pieces = (int)std::max<long long>(1, (want + D.NU - 1) / D.NU);
-      int CL = ((D.NM + pieces - 1) / pieces + 7) & ~7;
-      CL = std::max(CL, D.NM >= 128 ? 64 : 16);   // (shorter pieces only multiply the piece start / tail overhead)
-      const bool march_z_role = S.sM >= S.sU && p.Nz > 1;
-      D.dom_kind = march_z_role ? 0 : 1;
-      if (p.fwset.xcd && march_z_role) CL = std::max(32, ((D.NM + PRAD_FW_DOMAINS - 1) / PRAD_FW_DOMAINS + 7) & ~7);   // a piece = an XCD's z-slab
-      if (const char *e = getenv("PRAD_FW_CL")) CL = std::max(8, atoi(e) & ~7);
-      D.CL = CL;
-      D.pieces = (D.NM + CL - 1) / CL;
-      const long long chunks = (long long)D.NU * D.pieces;
-      if (chunks > 2000000000LL) return p;   // (cannot happen below 2^31 voxels) -> generic path
-      D.chunks = (int)chunks;
-    }
-  } else {
-    p.fw = false;
-    if (p.fw2) return SweepPlan();   // (only the x angle was asked for: not worth a plan of its own) -> generic path
-  }
-  if (p.row_slot < 0) p.skip1 = false;   // no x angle in this call: nothing to restore the runs of length 1 from
-  p.ok = true;
-  return p;
+// The switches of the GLCM / GLRLM route (prad_sweep_plan.h SweepKnobs) are an argument `kn` of everything below that depends on
+// one.  Every GLCM / GLRLM call (texture_pairs_runs) and every other entry point that finds a volume to flush (join, mark,
+// status, ...: pipeline_flush(c)) reads the environment afresh -- once -- and passes the record down, so that a test can flip a
+// checker switch (PRAD_FIN_RIDE, PRAD_FINALIZE_ONE, PRAD_FW_XROLE, ...) inside one process.
+SweepPlan plan_sweep(const Call &k, const SweepKnobs &kn, int Ng, int Nr, bool want_glcm, bool want_glrlm) {
+  PlanInput in;
+  in.nd = k.g.nd;
+  in.size = k.g.size;
+  in.angles = k.angles_h;
+  in.Na = k.Na;
+  in.Ng = Ng;
+  in.Nr = Nr;
+  in.want_glcm = want_glcm;
+  in.want_glrlm = want_glrlm;
+  in.voxel_mode = k.vm.voxels != nullptr;
+  return plan_sweep(in, kn, cu_count());
 }
 
 template <bool G, bool R, bool LNG, bool F, int LPL>
-int launch_lines_lpl(Call &k, const SweepPlan &p, const uint8_t *levels, int Ng, int Nr, u32 *glcm_acc,
+int launch_lines_lpl(Call &k, const SweepKnobs &kn, const SweepPlan &p, const uint8_t *levels, int Ng, int Nr, u32 *glcm_acc,
                      u32 *glrlm_acc, int *multi) {
   long long maxchunks = 0;
   for (int i = 0; i < p.lines.count; i++) maxchunks = std::max(maxchunks, p.lines.d[i].chunks);
@@ -627,10 +294,7 @@ int launch_lines_lpl(Call &k, const SweepPlan &p, const uint8_t *levels, int Ng,
   // tail is short, and a lone workgroup has the CU's LDS bandwidth to itself.
   const long long blocks_avail = std::max<long long>(1, (long long)cu_count() / p.lines.count);
   unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>(blocks_avail, (maxchunks + wpb - 1) / wpb));
-  if (const char *e = getenv("PRAD_LINES_BLOCKS")) {  // tuning override: workgroups per angle
-    const int v = atoi(e);
-    if (v >= 1) gx = (unsigned)v;
-  }
+  if (kn.lines_blocks.set && kn.lines_blocks.v >= 1) gx = (unsigned)kn.lines_blocks.v;  // tuning override: workgroups per angle
   PRAD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&sweep_lines_kernel<G, R, LNG, F, LPL>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
   hipLaunchKernelGGL((sweep_lines_kernel<G, R, LNG, F, LPL>), dim3(gx, p.lines.count), dim3(p.threads), p.lds_bytes,
@@ -640,11 +304,11 @@ int launch_lines_lpl(Call &k, const SweepPlan &p, const uint8_t *levels, int Ng,
 }
 
 template <bool G, bool R, bool LNG, bool F>
-int launch_lines(Call &k, const SweepPlan &p, const uint8_t *levels, int Ng, int Nr, u32 *glcm_acc, u32 *glrlm_acc,
+int launch_lines(Call &k, const SweepKnobs &kn, const SweepPlan &p, const uint8_t *levels, int Ng, int Nr, u32 *glcm_acc, u32 *glrlm_acc,
                  int *multi) {
-  if (p.LPL == 4) return launch_lines_lpl<G, R, LNG, F, 4>(k, p, levels, Ng, Nr, glcm_acc, glrlm_acc, multi);
-  if (p.LPL == 2) return launch_lines_lpl<G, R, LNG, F, 2>(k, p, levels, Ng, Nr, glcm_acc, glrlm_acc, multi);
-  return launch_lines_lpl<G, R, LNG, F, 1>(k, p, levels, Ng, Nr, glcm_acc, glrlm_acc, multi);
+  if (p.LPL == 4) return launch_lines_lpl<G, R, LNG, F, 4>(k, kn, p, levels, Ng, Nr, glcm_acc, glrlm_acc, multi);
+  if (p.LPL == 2) return launch_lines_lpl<G, R, LNG, F, 2>(k, kn, p, levels, Ng, Nr, glcm_acc, glrlm_acc, multi);
+  return launch_lines_lpl<G, R, LNG, F, 1>(k, kn, p, levels, Ng, Nr, glcm_acc, glrlm_acc, multi);
 }
 
 template <bool LNG, int K, bool HASPAD, bool PACK>
@@ -782,19 +446,10 @@ struct VolState {
   int lane = -1;                // workspace set of the volume (pipeline mode)
 };
 
-// PRAD_FINALIZE_STREAM=1 (round-6 experiment): the finalize launches of a pipeline volume on a side stream, see pipeline_retire
-bool fin_side() {
-  static const bool on = getenv("PRAD_FINALIZE_STREAM") != nullptr && atoi(getenv("PRAD_FINALIZE_STREAM")) != 0;
-  return on;
-}
-int fin_wait_for_lane(hipStream_t s, int lane);      // `s` waits for the side-stream finalize that last read workspace set `lane`
-
 // PRAD_FIN_RIDE=0: the finalize of a pipeline volume as a launch of its own behind its walk launch, and zero3_kernel in front of
-// every pack (A/B, and the checker of the riding job); read on every call so that a test can flip it
-bool fin_ride() {
-  const char *e = getenv("PRAD_FIN_RIDE");
-  return !(e && atoi(e) == 0 && e[0] != '\0');
-}
+// every pack (A/B, and the checker of the riding job); the knob record is read afresh on every call and every flush so that a
+// test can flip it
+bool fin_ride(const SweepKnobs &kn) { return kn.fin_ride; }
 
 // What a volume needs zeroed: accumulators + control words (before its WALKS), row flags and flag words (before its PACK).
 struct ZeroNeed {
@@ -829,9 +484,9 @@ int launch_zero3(hipStream_t s, const ZeroNeed &z) {
 
 // workspace of a volume + the zeroing that must precede its pack and its sweeps.  `defer`: the caller launches (or lets a walk
 // launch carry) what *defer names; without it the volume's zero3_kernel is launched here.
-int vol_prepare(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm, VolState &v, ZeroNeed *defer = nullptr) {
+int vol_prepare(Call &k, const SweepKnobs &kn, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm, VolState &v,
+                ZeroNeed *defer = nullptr) {
   Context &c = *k.c;
-  if (fin_side() && c.lane >= 0) PRAD_TRY(fin_wait_for_lane(k.s, c.lane));
   v.lane = c.lane;
   v.valid = true;
   v.p = p;
@@ -844,7 +499,7 @@ int vol_prepare(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, doubl
   const long long nrows = (long long)p.Nz * p.Ny;
   // (a two-table volume whose x angle walks the 16-bit elements keeps no byte copy: round 5b)
   v.levels = nullptr;
-  if (!(p.fw2 && p.fw2_rows && p.lines.count > 0 && p.row_slot >= 0) || getenv("PRAD_FW2_KEEP8")) {
+  if (!(p.fw2 && p.fw2_rows && p.lines.count > 0 && p.row_slot >= 0)) {
     PRAD_TRY(c.get<uint8_t>("levels", (size_t)nrows * p.pitch + 1024, &v.levels));
     v.levels += 512;   // the fixed-window kernel reads (and masks) up to one window before the first and behind the last row
   }
@@ -874,7 +529,7 @@ int vol_prepare(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, doubl
   if (c.lane >= 0 && c.lane < kPipeSets) {   // a set of the pipeline: what an earlier walk launch re-zeroed need not be zeroed again
     SetZero &S = set_zero_book()[c.lane];
     const size_t cap = v.rowzero ? c.bufs[c.key("rowzero")].cap : 0;
-    if (fin_ride()) {
+    if (fin_ride(kn)) {
       if (S.rz == z.rz && S.rz_cap == cap && z.rz_w <= S.rz_zero) z.rz_w = 0;
       if (S.fl == z.fl && S.fl_zero) z.fl_w = 0;
     }
@@ -895,7 +550,7 @@ int vol_prepare(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, doubl
 // can this volume's pack ride in another volume's sweep launch?  (linear layout, vector loads)
 bool pipeline_volume(const SweepPlan &p, bool glcm, bool glrlm) {   // a volume the two-stage deferred pipeline takes
   if (!(p.ok && p.lines.count > 0 && glcm && glrlm)) return false;
-  return (p.fw && p.fused) || (p.fw2 && !getenv("PRAD_FW2_LANES"));
+  return (p.fw && p.fused) || p.fw2;
 }
 bool pack_inline_ok(const Call &k, const VolState &v) {
   if (!(v.glcm && v.glrlm && v.p.pitch == v.p.Nx && v.p.padw == 0 && (k.g.n % 16) == 0 &&
@@ -908,7 +563,7 @@ bool pack_inline_ok(const Call &k, const VolState &v) {
   return v.p.fw && v.p.fused;
 }
 
-PackJob make_pack_job(const Call &k, const VolState &v, const VolState *host) {
+PackJob make_pack_job(const Call &k, const SweepKnobs &kn, const VolState &v, const VolState *host) {
   PackJob j;
   memset(&j, 0, sizeof(j));
   j.image = k.image;
@@ -921,18 +576,15 @@ PackJob make_pack_job(const Call &k, const VolState &v, const VolState *host) {
   j.NX = v.p.Nx;
   j.Ng = v.Ng;
   // cadence: spread a wave's units over the plain groups of its walk (both per wave); what is left drains behind the walk
-  double groups = 0, waves = 16.0;
-  if (host) {
+  double groups = 0;
+  if (host)
     for (int i = 0; i < host->p.fwset.count; i++) groups += (double)host->p.fwset.d[i].NM * host->p.fwset.d[i].NU / PRAD_FW_U;
-    waves = 16.0 * std::max(1, host->p.fw_blocks);
-  }
   const double units = (double)j.n16 / 64.0;
   // (two-table walk: a unit every 3rd group instead of every 2nd at 512^3 -- 0.707 -> 0.698 ms per volume, smooth inside its run-to-run spread of 0.75 - 0.78;
   //  the fused-table walk measures best at 2: 0.490 against 0.496 at 3, profiles/r05b_probes.md)
   const double slack = v.p.fw2 ? 1.05 : 0.92;
   j.every = (int)std::max(1.0, std::min(64.0, std::floor(slack * groups / std::max(1.0, units))));
-  (void)waves;
-  if (const char *e = getenv("PRAD_PACK_EVERY")) j.every = std::max(1, atoi(e));
+  if (kn.pack_every.set) j.every = std::max(1, (int)kn.pack_every.v);
   return j;
 }
 
@@ -956,7 +608,7 @@ int vol_pack_standalone(Call &k, VolState &v) {
 }
 
 template <bool G, bool R, bool F>
-int launch_sweeps(Call &k, const VolState &v, const PackJob &pj, const FinJob &fj) {
+int launch_sweeps(Call &k, const SweepKnobs &kn, const VolState &v, const PackJob &pj, const FinJob &fj) {
   const SweepPlan &p = v.p;
   if (p.lines.count > 0 && p.fw && G && R && F) {
     {
@@ -990,8 +642,8 @@ int launch_sweeps(Call &k, const VolState &v, const PackJob &pj, const FinJob &f
   }
   Timed t(*k.c, "sweep", k.s);
   if (p.lines.count > 0) {
-    if (R && p.LONG) PRAD_TRY((launch_lines<G, R, true, F>(k, p, v.levels, v.Ng, v.Nr, v.glcm_acc, v.glrlm_acc, v.multi)));
-    else PRAD_TRY((launch_lines<G, R, false, F>(k, p, v.levels, v.Ng, v.Nr, v.glcm_acc, v.glrlm_acc, v.multi)));
+    if (R && p.LONG) PRAD_TRY((launch_lines<G, R, true, F>(k, kn, p, v.levels, v.Ng, v.Nr, v.glcm_acc, v.glrlm_acc, v.multi)));
+    else PRAD_TRY((launch_lines<G, R, false, F>(k, kn, p, v.levels, v.Ng, v.Nr, v.glcm_acc, v.glrlm_acc, v.multi)));
   }
   if (p.row_slot >= 0) {
     if (R && p.LONGr) PRAD_TRY((launch_rows<G, R, true, F>(k, p, v.levels, v.Ng, v.Nr, v.glcm_acc, v.glrlm_acc, v.multi)));
@@ -1002,22 +654,22 @@ int launch_sweeps(Call &k, const VolState &v, const PackJob &pj, const FinJob &f
 
 // the sweeps of volume v; `pj` (n16 > 0) = the pack of another volume as a side job of the fixed-window launch
 bool fin_job_empty(const FinJob &fj);
-int vol_sweep(Call &k, const VolState &v, const PackJob &pj, const FinJob &fj) {
+int vol_sweep(Call &k, const SweepKnobs &kn, const VolState &v, const PackJob &pj, const FinJob &fj) {
   if (pj.n16 > 0 && !pipeline_volume(v.p, v.glcm != nullptr, v.glrlm != nullptr))
     return fail(PRAD_E_ARG, "internal: a pack job needs a fixed-window host launch");
   if (pj.n16 > 0 && (pj.levels16 != nullptr) != v.p.fw2)
     return fail(PRAD_E_ARG, "internal: the pack job's layout is not the host launch's");
   if (!fin_job_empty(fj) && !(v.glcm && v.glrlm && v.p.fused && v.p.fw && v.p.lines.count > 0))
     return fail(PRAD_E_ARG, "internal: a finalize job needs a fused-table host launch");
-  if (v.glcm && v.glrlm && v.p.fused) return launch_sweeps<true, true, true>(k, v, pj, fj);
-  if (v.glcm && v.glrlm) return launch_sweeps<true, true, false>(k, v, pj, fj);
-  if (v.glcm) return launch_sweeps<true, false, false>(k, v, pj, fj);
-  return launch_sweeps<false, true, false>(k, v, pj, fj);
+  if (v.glcm && v.glrlm && v.p.fused) return launch_sweeps<true, true, true>(k, kn, v, pj, fj);
+  if (v.glcm && v.glrlm) return launch_sweeps<true, true, false>(k, kn, v, pj, fj);
+  if (v.glcm) return launch_sweeps<true, false, false>(k, kn, v, pj, fj);
+  return launch_sweeps<false, true, false>(k, kn, v, pj, fj);
 }
-int vol_sweep(Call &k, const VolState &v, const PackJob &pj) {
+int vol_sweep(Call &k, const SweepKnobs &kn, const VolState &v, const PackJob &pj) {
   FinJob none;
   memset(&none, 0, sizeof(none));
-  return vol_sweep(k, v, pj, none);
+  return vol_sweep(k, kn, v, pj, none);
 }
 
 __global__ void latch_flags_kernel(const int *__restrict__ flags, int *__restrict__ sticky) {
@@ -1036,14 +688,11 @@ int latch_neigh(Context &c, Call &k) {
 }
 
 // PRAD_FINALIZE_ONE=0: the three finalize launches of a GLCM + GLRLM volume instead of finalize_volume_kernel (A/B, and the
-// checker of that kernel); read on every call so that a test can flip it
-bool finalize_one() {
-  const char *e = getenv("PRAD_FINALIZE_ONE");
-  return !(e && atoi(e) == 0 && e[0] != '\0');
-}
+// checker of that kernel); like fin_ride(), from the knob record that every call and every flush reads afresh
+bool finalize_one(const SweepKnobs &kn) { return kn.finalize_one; }
 
 // u32 accumulators -> float64 matrices in the reference layouts; `sticky` (deferred calls): latch the levels verdict
-int vol_finalize(Call &k, const VolState &v, int *sticky) {
+int vol_finalize(Call &k, const SweepKnobs &kn, const VolState &v, int *sticky) {
   Context &c = *k.c;
   const SweepPlan &p = v.p;
   const int Ng = v.Ng, Nr = v.Nr, Na = v.Na;
@@ -1056,7 +705,7 @@ int vol_finalize(Call &k, const VolState &v, int *sticky) {
     // matrices and the x angle's complete run table (plans with skip1 always carry them: plan_sweep clears the flag otherwise)
     if (p.fw2 && p.skip1 && p.lines.count > 0 && !(glcm && glrlm && p.row_slot >= 0))
       return fail(PRAD_E_UNSUPPORTED, "sweep plan derives runs of length 1 but the call cannot restore them");
-    if (glcm && glrlm && runs_diag && finalize_one() && (long long)Ng * Nr < (1LL << 30)) {
+    if (glcm && glrlm && runs_diag && finalize_one(kn) && (long long)Ng * Nr < (1LL << 30)) {
       // ONE launch (finalize_volume_kernel): Na angle workgroups, then the two element-wise conversions
       const int nbR = (int)blocks_for((long long)Ng * Nr * Na, 1024), nbG = (int)blocks_for((long long)Ng * Ng * Na, 1024);
       const int restore_from = (p.fw2 && p.skip1 && p.lines.count > 0) ? p.row_slot : -1;
@@ -1111,17 +760,17 @@ int vol_finalize(Call &k, const VolState &v, int *sticky) {
 }
 
 // returns PRAD_OK with *used=false if the device found irregular levels (caller then runs generic)
-int sweep_glcm_glrlm(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm, bool *used) {
+int sweep_glcm_glrlm(Call &k, const SweepKnobs &kn, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm, bool *used) {
   Context &c = *k.c;
   VolState v;
-  PRAD_TRY(vol_prepare(k, p, Ng, Nr, glcm, glrlm, v));
+  PRAD_TRY(vol_prepare(k, kn, p, Ng, Nr, glcm, glrlm, v));
   PRAD_TRY(vol_pack_standalone(k, v));
   PackJob pj;
   memset(&pj, 0, sizeof(pj));
-  PRAD_TRY(vol_sweep(k, v, pj));
+  PRAD_TRY(vol_sweep(k, kn, v, pj));
   int *sticky = nullptr;       // deferred calls latch their levels verdict
   if (c.deferred) PRAD_TRY(c.get<int>("deferred_sticky", 16, &sticky));
-  PRAD_TRY(vol_finalize(k, v, sticky));
+  PRAD_TRY(vol_finalize(k, kn, v, sticky));
   if (c.deferred) {   // enqueue only: the verdict on the levels is latched for prad_deferred_status()
     *used = true;
     return PRAD_OK;
@@ -1164,21 +813,14 @@ struct PipeState {
   unsigned long long seq = 0;
   hipEvent_t ev = nullptr;
   int mode = -1;                // 1 pipeline, 0 lanes
-  // side stream of the finalize launches (fin_side()): fin_done[l] is recorded behind the finalize that read workspace set l
-  hipStream_t fin = nullptr;
-  hipEvent_t fin_in = nullptr, fin_all = nullptr, fin_done[4] = {};
-  bool fin_used[4] = {};
 };
 PipeState &pipe_state() {
   static thread_local PipeState p;
   return p;
 }
-bool pipeline_mode() {
+bool pipeline_mode(const SweepKnobs &kn) {
   PipeState &ps = pipe_state();
-  if (ps.mode < 0) {
-    const char *e = getenv("PRAD_DEFERRED_MODE");
-    ps.mode = (e && strcmp(e, "lanes") == 0) ? 0 : 1;
-  }
+  if (ps.mode < 0) ps.mode = kn.lanes_mode ? 0 : 1;
   return ps.mode == 1;
 }
 int pipeline_sticky(Context &c, int **sticky) { return c.get<int>("deferred_sticky", 16, sticky); }
@@ -1187,17 +829,17 @@ bool fin_job_empty(const FinJob &fj) { return fj.Na == 0 && fj.zn[0] + fj.zn[1] 
 
 // can the finalize of v ride in a walk launch?  (the conditions of the one-launch finalize, a walk launch that is the volume's
 // last, and the job's 32-bit element indices)
-bool fin_can_ride(const VolState &v) {
+bool fin_can_ride(const SweepKnobs &kn, const VolState &v) {
   const SweepPlan &p = v.p;
   if (!(v.glcm && v.glrlm && p.fw && p.fused && p.lines.count > 0 && v.levels && v.lane >= 0 && v.lane < kPipeSets)) return false;
   if (p.row_slot >= 0 && p.fw_xblocks == 0) return false;   // (PRAD_FW_XROLE=0: the x angle is a launch behind the walk launch)
-  if (!finalize_one() || (long long)v.Ng * v.Nr >= (1LL << 30) || v.Ng > 255 || v.Na > PRAD_MAX_SWEEP || v.Na != p.aset.count) return false;
+  if (!finalize_one(kn) || (long long)v.Ng * v.Nr >= (1LL << 30) || v.Ng > 255 || v.Na > PRAD_MAX_SWEEP || v.Na != p.aset.count) return false;
   return ((long long)v.Ng * v.Nr + (long long)v.Ng * v.Ng) * v.Na < (1LL << 31);
 }
 // can the walk launch of `host` on stream s carry a FinJob?  (with or without a pack job pj)
-bool fin_host_ok(const PipeState &ps, const VolState &host, const PackJob &pj, hipStream_t s) {
+bool fin_host_ok(const SweepKnobs &kn, const PipeState &ps, const VolState &host, const PackJob &pj, hipStream_t s) {
   const SweepPlan &p = host.p;
-  if (!(fin_ride() && !fin_side() && ps.s == s && host.glcm && host.glrlm && p.fw && p.fused && p.lines.count > 0)) return false;
+  if (!(fin_ride(kn) && ps.s == s && host.glcm && host.glrlm && p.fw && p.fused && p.lines.count > 0)) return false;
   const size_t lds = p.fw_xblocks > 0 ? std::max(p.lds_fw, p.lds_fw_rows) : p.lds_fw;   // (as launch_fw_kpp)
   return lds >= (size_t)PRAD_FIN_SCRATCH_BYTES && p.fw_blocks >= 1 && p.fw_blocks < 32768;
 }
@@ -1225,29 +867,20 @@ FinJob make_fin_job(const VolState &host, const VolState *walked, const ZeroNeed
     j.glrlm_out = w.glrlm;
     j.multi = w.multi;
     j.flags = w.flags_d;
-    // Placement of the 13 angle workgroups (each starts its walk ~7 us late; the role's chunk hand-out makes up for it).
-    // 0: angle a on workgroup a / count of role a % count.  1: all on the roles whose waves finish first.  2: evenly over the grid.
-    static const int place = getenv("PRAD_FIN_PLACE") ? atoi(getenv("PRAD_FIN_PLACE")) : 0;
+    // Placement of the 13 angle workgroups (each starts its walk ~7 us late; the role's chunk hand-out makes up for it):
+    // angle a on workgroup a / count of role a % count
     const FwSet &fs = host.p.fwset;
-    static const int early[4] = {1, 4, 3, 10};   // (profiles/r05_fw_phases.md, wave life by role)
     for (int a = 0; a < w.Na; a++) {
       for (int d = 0; d < 3; d++) j.off[a][d] = (signed char)w.p.aset.off[a][d];
-      int role = a % fs.count, idx = a / fs.count;
-      if (place == 1 && fs.count > 10) {
-        role = early[a % 4];
-        idx = a / 4;
-      }
-      int b = (fs.first_block[role] + idx < fs.first_block[role + 1]) ? fs.first_block[role] + idx : a % nline;
-      if (place == 2) b = (int)((long long)a * nline / w.Na);
+      const int role = a % fs.count, idx = a / fs.count;
+      const int b = (fs.first_block[role] + idx < fs.first_block[role + 1]) ? fs.first_block[role] + idx : a % nline;
       j.ablock[a] = (short)b;
     }
   }
   const int wl = walked ? walked->lane : -1;
-  size_t words = 0;
   if (need && need->acc_w > 0 && new_lane >= 0 && new_lane < kPipeSets && new_lane != host.lane && new_lane != wl) {
     j.z[0] = need->acc;
     j.zn[0] = (unsigned)need->acc_w;
-    words += need->acc_w;
   }
   if (new_lane >= 0 && new_lane < kPipeSets) {
     const int t = (new_lane + 1) % kPipeSets;
@@ -1255,7 +888,6 @@ FinJob make_fin_job(const VolState &host, const VolState *walked, const ZeroNeed
     if (t != host.lane && t != wl && t != new_lane && S.rz_zero < S.rz_used && S.rz) {
       j.z[1] = S.rz;
       j.zn[1] = (unsigned)S.rz_used;
-      words += S.rz_used;
       S.rz_zero = S.rz_used;
     }
     if (t != host.lane && t != wl && t != new_lane && S.fl && !S.fl_zero) {
@@ -1264,12 +896,11 @@ FinJob make_fin_job(const VolState &host, const VolState *walked, const ZeroNeed
       S.fl_zero = true;
     }
   }
-  (void)words;
   return j;
 }
 
 // the stand-alone finalize of the walked volume on stream s (ordered behind its walk launch by the caller)
-int pipeline_finish_walked(Context &c, hipStream_t s) {
+int pipeline_finish_walked(Context &c, const SweepKnobs &kn, hipStream_t s) {
   PipeState &ps = pipe_state();
   if (!ps.walked.valid) return PRAD_OK;
   Call k;
@@ -1279,7 +910,7 @@ int pipeline_finish_walked(Context &c, hipStream_t s) {
   k.flags_d = ps.walked.flags_d;
   int *sticky = nullptr;
   PRAD_TRY(pipeline_sticky(c, &sticky));
-  PRAD_TRY(vol_finalize(k, ps.walked, sticky));
+  PRAD_TRY(vol_finalize(k, kn, ps.walked, sticky));
   ps.walked.valid = false;
   return PRAD_OK;
 }
@@ -1287,9 +918,10 @@ int pipeline_finish_walked(Context &c, hipStream_t s) {
 // walks of the pending volume on stream s (pj: the next volume's pack as a side job, or n16 == 0) and its finalize -- at once, or,
 // with `keep`, left to the next walk launch (the volume becomes `walked`).  The finalize of the volume walked BEFORE rides in
 // this launch if it can, else it is launched first.  need / new_lane: the zeroing the next volume still asks for and its set.
-int pipeline_retire(Context &c, hipStream_t s, const PackJob &pj, bool keep = false, const ZeroNeed *need = nullptr, int new_lane = -1) {
+int pipeline_retire(Context &c, const SweepKnobs &kn, hipStream_t s, const PackJob &pj, bool keep = false, const ZeroNeed *need = nullptr,
+                    int new_lane = -1) {
   PipeState &ps = pipe_state();
-  const bool host_ok = fin_host_ok(ps, ps.pending, pj, s);   // (before ps.s moves)
+  const bool host_ok = fin_host_ok(kn, ps, ps.pending, pj, s);   // (before ps.s moves)
   if (ps.s != s) {   // the pack ran on another stream: order the two on the device
     if (!ps.ev) PRAD_HIP(hipEventCreateWithFlags(&ps.ev, hipEventDisableTiming));
     PRAD_HIP(hipEventRecord(ps.ev, ps.s));
@@ -1305,13 +937,13 @@ int pipeline_retire(Context &c, hipStream_t s, const PackJob &pj, bool keep = fa
   FinJob fj;
   memset(&fj, 0, sizeof(fj));
   if (host_ok) {
-    const bool rides = ps.walked.valid && fin_can_ride(ps.walked) && ps.walked.lane != ps.pending.lane && ps.walked.lane != new_lane;
-    if (ps.walked.valid && !rides) PRAD_TRY(pipeline_finish_walked(c, s));
+    const bool rides = ps.walked.valid && fin_can_ride(kn, ps.walked) && ps.walked.lane != ps.pending.lane && ps.walked.lane != new_lane;
+    if (ps.walked.valid && !rides) PRAD_TRY(pipeline_finish_walked(c, kn, s));
     fj = make_fin_job(ps.pending, rides ? &ps.walked : nullptr, need, new_lane);
     fj.sticky = sticky;
     ps.walked.valid = false;   // (enqueued with the launch below)
   } else {
-    PRAD_TRY(pipeline_finish_walked(c, s));
+    PRAD_TRY(pipeline_finish_walked(c, kn, s));
   }
   if (need && need->acc_w > 0 && fj.zn[0] == 0) {   // (the job did not take the accumulators: their set is one the launch works on)
     ZeroNeed acc;
@@ -1319,96 +951,65 @@ int pipeline_retire(Context &c, hipStream_t s, const PackJob &pj, bool keep = fa
     acc.acc_w = need->acc_w;
     PRAD_TRY(launch_zero3(s, acc));
   }
-  PRAD_TRY(vol_sweep(k, ps.pending, pj, fj));
-  if (keep && fin_ride() && !fin_side() && fin_can_ride(ps.pending)) {
+  PRAD_TRY(vol_sweep(k, kn, ps.pending, pj, fj));
+  if (keep && fin_ride(kn) && fin_can_ride(kn, ps.pending)) {
     ps.walked = ps.pending;
     ps.pending.valid = false;
     return PRAD_OK;
   }
-  if (fin_side() && ps.pending.lane >= 0 && ps.pending.lane < 4) {
-    // The three finalize launches (13 us + their launch gaps per 512^3 volume) need a handful of workgroups and no LDS: on a
-    // side stream they run under the next volume's walk launch instead of in front of it.  The accumulators they read belong to
-    // workspace set `lane`: with more than two alternating sets the next volume that zeroes this set is two steps away.
-    if (!ps.fin) {
-      PRAD_HIP(hipStreamCreateWithFlags(&ps.fin, hipStreamNonBlocking));
-      PRAD_HIP(hipEventCreateWithFlags(&ps.fin_in, hipEventDisableTiming));
-      PRAD_HIP(hipEventCreateWithFlags(&ps.fin_all, hipEventDisableTiming));
-      for (int l = 0; l < 4; l++) PRAD_HIP(hipEventCreateWithFlags(&ps.fin_done[l], hipEventDisableTiming));
-    }
-    PRAD_HIP(hipEventRecord(ps.fin_in, s));
-    PRAD_HIP(hipStreamWaitEvent(ps.fin, ps.fin_in, 0));
-    Call k2 = k;
-    k2.s = ps.fin;
-    PRAD_TRY(vol_finalize(k2, ps.pending, sticky));
-    PRAD_HIP(hipEventRecord(ps.fin_done[ps.pending.lane], ps.fin));
-    ps.fin_used[ps.pending.lane] = true;
-  } else {
-    PRAD_TRY(vol_finalize(k, ps.pending, sticky));
-  }
+  PRAD_TRY(vol_finalize(k, kn, ps.pending, sticky));
   ps.pending.valid = false;
   return PRAD_OK;
 }
 
-int fin_wait_for_lane(hipStream_t s, int lane) {
-  PipeState &ps = pipe_state();
-  if (lane < 0 || lane >= 4 || !ps.fin || !ps.fin_used[lane]) return PRAD_OK;
-  PRAD_HIP(hipStreamWaitEvent(s, ps.fin_done[lane], 0));
-  return PRAD_OK;
-}
-// everything queued on the finalize side stream so far: `s` waits for it (s != nullptr) or the host does
-int fin_join(hipStream_t s, bool host) {
-  PipeState &ps = pipe_state();
-  if (!ps.fin) return PRAD_OK;
-  if (host) {
-    PRAD_HIP(hipStreamSynchronize(ps.fin));
-    return PRAD_OK;
-  }
-  PRAD_HIP(hipEventRecord(ps.fin_all, ps.fin));
-  PRAD_HIP(hipStreamWaitEvent(s, ps.fin_all, 0));
-  return PRAD_OK;
-}
-
-// nothing pending or walked afterwards (kernels enqueued on the pending volume's own stream; no host synchronisation)
-int pipeline_flush(Context &c) {
+// nothing pending or walked afterwards (kernels enqueued on the pending volume's own stream; no host synchronisation).
+int pipeline_flush(Context &c, const SweepKnobs &kn) {
   PipeState &ps = pipe_state();
   if (!ps.pending.valid && !ps.walked.valid) return PRAD_OK;
   PackJob none;
   memset(&none, 0, sizeof(none));
   const size_t before = c.times.size();
-  if (ps.pending.valid) PRAD_TRY(pipeline_retire(c, ps.s, none));
-  else PRAD_TRY(pipeline_finish_walked(c, ps.s));
+  if (ps.pending.valid) PRAD_TRY(pipeline_retire(c, kn, ps.s, none));
+  else PRAD_TRY(pipeline_finish_walked(c, kn, ps.s));
   if (c.timing_accumulate) c.all_times.insert(c.all_times.end(), c.times.begin() + (long)before, c.times.end());
   return PRAD_OK;
+}
+// ... from an entry point that is no GLCM / GLRLM call (join, mark, status, set_device, ...): it reads the switches itself, and
+// only when there is a volume to flush
+int pipeline_flush(Context &c) {
+  PipeState &ps = pipe_state();
+  if (!ps.pending.valid && !ps.walked.valid) return PRAD_OK;
+  return pipeline_flush(c, sweep_knobs_from_env());
 }
 
 // one deferred call in pipeline mode; *handled = false: the volume is not a fixed-window one, the caller takes the
 // ordinary deferred route (the pipeline has been drained)
-int pipeline_step(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm, bool *handled) {
+int pipeline_step(Call &k, const SweepKnobs &kn, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm, bool *handled) {
   Context &c = *k.c;
   PipeState &ps = pipe_state();
   *handled = false;
-  if (!pipeline_volume(p, glcm != nullptr, glrlm != nullptr)) return pipeline_flush(c);
+  if (!pipeline_volume(p, glcm != nullptr, glrlm != nullptr)) return pipeline_flush(c, kn);
   VolState v;
   ZeroNeed need;
-  PRAD_TRY(vol_prepare(k, p, Ng, Nr, glcm, glrlm, v, &need));
+  PRAD_TRY(vol_prepare(k, kn, p, Ng, Nr, glcm, glrlm, v, &need));
   PackJob pj;
   memset(&pj, 0, sizeof(pj));
   bool inl = false;
   if (ps.pending.valid) {
     // (the side job writes the layout of the launch it rides in: fused-table and two-table volumes do not mix)
-    inl = pack_inline_ok(k, v) && ps.pending.p.fw2 == v.p.fw2 && !getenv("PRAD_NO_INLINE_PACK");
-    if (inl) pj = make_pack_job(k, v, &ps.pending);
+    inl = pack_inline_ok(k, v) && ps.pending.p.fw2 == v.p.fw2 && !kn.no_inline_pack;
+    if (inl) pj = make_pack_job(k, kn, v, &ps.pending);
     // the walk launch zeroes the accumulators of this volume itself if it carries a job; what the pack needs zeroed goes first
-    const bool ride = fin_host_ok(ps, ps.pending, pj, k.s) && need.acc_w + need.rz_w + need.fl_w < ((size_t)1 << 30);
+    const bool ride = fin_host_ok(kn, ps, ps.pending, pj, k.s) && need.acc_w + need.rz_w + need.fl_w < ((size_t)1 << 30);
     ZeroNeed now = need;
     if (ride) {
       now.acc_w = 0;
       need.rz_w = need.fl_w = 0;
     }
     PRAD_TRY(launch_zero3(k.s, now));
-    PRAD_TRY(pipeline_retire(c, k.s, pj, true, ride ? &need : nullptr, v.lane));
+    PRAD_TRY(pipeline_retire(c, kn, k.s, pj, true, ride ? &need : nullptr, v.lane));
   } else {
-    PRAD_TRY(pipeline_finish_walked(c, ps.s));   // (a walked volume without a pending one: only after a failed call)
+    PRAD_TRY(pipeline_finish_walked(c, kn, ps.s));   // (a walked volume without a pending one: only after a failed call)
     PRAD_TRY(launch_zero3(k.s, need));
   }
   if (!inl) PRAD_TRY(vol_pack_standalone(k, v));
@@ -1423,11 +1024,11 @@ int pipeline_step(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, dou
 // The tier between the sweeps and the exact kernels (kernels_pairs.h): segment mode, Nd <= 3, any offset list of up to 128
 // angles, up to 38 400 grey levels.  *used = false when the call is not for it or the pack found a level outside 1..Ng
 // (the outputs are then untouched zeros and the exact kernels redo the call).
-int pairs_glcm_glrlm(Call &k, int Ng, int Nr, double *glcm, double *glrlm, bool *used) {
+int pairs_glcm_glrlm(Call &k, const SweepKnobs &kn, int Ng, int Nr, double *glcm, double *glrlm, bool *used) {
   *used = false;
   Context &c = *k.c;
   if (k.vm.voxels || k.g.nd > 3 || Ng < 1 || Ng > PRAD_PAIR_LDS_WORDS || k.Na > PRAD_PAIR_MAXA || k.g.n >= 0x7fffffffLL ||
-      getenv("PRAD_NO_PAIRS"))
+      kn.no_pairs)
     return PRAD_OK;
   int dims[3] = {1, 1, 1};
   for (int d = 0; d < k.g.nd; d++) dims[3 - k.g.nd + d] = k.g.size[d];
@@ -1530,6 +1131,8 @@ int pairs_glcm_glrlm(Call &k, int Ng, int Nr, double *glcm, double *glrlm, bool 
   return PRAD_OK;
 }
 
+}  // namespace
+namespace prad {   // (prad_internal.h)
 int texture_pairs_runs(const int32_t *image, const uint8_t *mask, const int *size, int Nd, const int *angles,
                        int Na, int Ng, int Nr, int Nvox, const int *voxels, int kernelRadius, int force2Ddim,
                        double *glcm, double *glrlm, hipStream_t s) {
@@ -1537,11 +1140,12 @@ int texture_pairs_runs(const int32_t *image, const uint8_t *mask, const int *siz
   if (Ng < 1 || (glrlm && Nr < 1)) return fail(PRAD_E_ARG, "Ng/Nr must be >= 1");
   Context &c = ctx();
   PRAD_TRY(c.ensure_device());
+  const SweepKnobs kn = sweep_knobs_from_env();   // once per call
   struct LaneGuard {
     Context &c;
     ~LaneGuard() { c.lane = -1; }
   } lane_guard{c};
-  bool pipe = c.deferred && !voxels && pipeline_mode();
+  bool pipe = c.deferred && !voxels && pipeline_mode(kn);
   if (c.deferred && !voxels && !pipe) {   // lanes mode: whole-volume deferred calls alternate between lanes
     PRAD_TRY(c.lane_begin(s, &s));
     if (c.lane >= 0) c.lane += kPipeSets;   // (workspace sets of their own: #0 .. #3 belong to the pipeline)
@@ -1549,34 +1153,33 @@ int texture_pairs_runs(const int32_t *image, const uint8_t *mask, const int *siz
   if (pipe) c.lane = (int)(pipe_state().seq++ % (unsigned)kPipeSets);   // pipeline mode: four workspace sets alternate (see the pipeline's header), the stream is the caller's
   Call k;
   PRAD_TRY(setup_call(k, image, mask, size, Nd, angles, Na, Nvox, voxels, kernelRadius, force2Ddim, s, false));
-  SweepPlan p = plan_sweep(k, Ng, Nr, glcm != nullptr, glrlm != nullptr);
+  SweepPlan p = plan_sweep(k, kn, Ng, Nr, glcm != nullptr, glrlm != nullptr);
   if (pipe && !pipeline_volume(p, glcm != nullptr, glrlm != nullptr)) {
-    // Not a volume for the two-stage pipeline (the wrapped-lines kernels; PRAD_FW2_LANES: the two-table kernel of 45+ grey
-    // levels as until round 5): its pack is a launch of its own, so deal the call onto the lanes, where the pack of one
-    // volume runs under the walk of the previous one
+    // Not a volume for the two-stage pipeline (the wrapped-lines kernels): its pack is a launch of its own, so deal the call
+    // onto the lanes, where the pack of one volume runs under the walk of the previous one
     const hipStream_t user = s;
-    PRAD_TRY(pipeline_flush(c));
+    PRAD_TRY(pipeline_flush(c, kn));
     pipe = false;
     c.lane = -1;
     PRAD_TRY(c.lane_begin(user, &s));
     if (c.lane >= 0) c.lane += kPipeSets;      // (workspace sets of their own: #0 .. #3 belong to the pipeline's alternating volumes)
     PRAD_TRY(setup_call(k, image, mask, size, Nd, angles, Na, Nvox, voxels, kernelRadius, force2Ddim, s, false));
-    p = plan_sweep(k, Ng, Nr, glcm != nullptr, glrlm != nullptr);
+    p = plan_sweep(k, kn, Ng, Nr, glcm != nullptr, glrlm != nullptr);
   }
   PRAD_TRY(c.begin_call(s));
   if (!p.ok) PRAD_HIP(hipMemsetAsync(k.flags_d, 0, sizeof(int) * 4, s));   // (vol_prepare does it on the sweep path)
   bool done = false;
   c.last_variant = !p.ok ? "none" : (p.fw2 ? "fw2" : (p.fw && glcm && glrlm ? "fw" : "lines"));
   if (pipe) {
-    PRAD_TRY(pipeline_step(k, p, Ng, Nr, glcm, glrlm, &done));
+    PRAD_TRY(pipeline_step(k, kn, p, Ng, Nr, glcm, glrlm, &done));
     if (done) c.last_path = "sweep";
   }
   if (!done && p.ok) {
-    PRAD_TRY(sweep_glcm_glrlm(k, p, Ng, Nr, glcm, glrlm, &done));
+    PRAD_TRY(sweep_glcm_glrlm(k, kn, p, Ng, Nr, glcm, glrlm, &done));
     if (done) c.last_path = "sweep";
   }
   if (!done && !c.deferred) {      // (synchronous calls: the tier reads its levels verdict back)
-    PRAD_TRY(pairs_glcm_glrlm(k, Ng, Nr, glcm, glrlm, &done));
+    PRAD_TRY(pairs_glcm_glrlm(k, kn, Ng, Nr, glcm, glrlm, &done));
     if (done) {
       c.last_path = "pairs";
       c.last_variant = "pairs";
@@ -1593,6 +1196,8 @@ int texture_pairs_runs(const int32_t *image, const uint8_t *mask, const int *siz
   PRAD_HIP(hipStreamSynchronize(s));
   return k.flags_h[1] ? PRAD_INDEX_ERROR : PRAD_OK;
 }
+}  // namespace prad
+namespace {
 
 // GLDM / NGTDM on the 16-bit level volume (kernels_pairs.h): what kernels_neigh.h does not take -- more than 255 levels, bin
 // tables beyond its LDS budget.  Synchronous calls only; *used = false: not for this tier, or a level outside 1..Ng.
@@ -1828,6 +1433,8 @@ int texture_ngtdm(const int32_t *image, const uint8_t *mask, const int *size, in
   return k.flags_h[1] ? PRAD_INDEX_ERROR : PRAD_OK;
 }
 
+}  // namespace
+namespace prad {   // (prad_internal.h)
 // GLDM and NGTDM of a segment from one pass over the neighbourhoods (segment mode; prad_calculate_gldm_ngtdm_dev)
 int texture_gldm_ngtdm(const int32_t *image, const uint8_t *mask, const int *size, int Nd, const int *angles, int Na,
                        int Ng, int alpha, double *gldm, double *ngtdm, hipStream_t s) {
@@ -1860,6 +1467,29 @@ int texture_gldm_ngtdm(const int32_t *image, const uint8_t *mask, const int *siz
   PRAD_TRY(texture_gldm(image, mask, size, Nd, angles, Na, Ng, alpha, 1, nullptr, 0, -1, gldm, s));
   return texture_ngtdm(image, mask, size, Nd, angles, Na, Ng, 1, nullptr, 0, -1, ngtdm, s);
 }
+
+// ONE byte-packed copy of a derived image for its neighbourhood pass and its GLSZM (kernels_neigh.h SharedPack), made on `s`
+// in front of the image's fork; a buffer per ticket: up to four images are in flight
+int image_shared_pack(Context &c, const int32_t *levels, const uint8_t *mask, long long n, int NX, int Ng, int ticket, hipStream_t s) {
+  char name[32];
+  snprintf(name, sizeof(name), "img_pack%d", ticket);
+  uint8_t *pk = nullptr;
+  int *pf = nullptr;
+  c.workspace = 0;
+  PRAD_TRY(c.get<uint8_t>(name, (size_t)n + 64 + 16, &pk));
+  pf = (int *)(pk + (((size_t)n + 64 + 3) & ~(size_t)3));
+  PRAD_HIP(hipMemsetAsync(pf, 0, sizeof(int) * 2, s));
+  const int vec_ok = ((((uintptr_t)levels) | ((uintptr_t)mask) | ((uintptr_t)pk)) & 15) == 0;
+  const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((n / 16 + 255) / 256, 4096));
+  hipLaunchKernelGGL(pack_levels_kernel, dim3(gx), dim3(256), 0, s, levels, mask, n, NX, NX, 0, Ng, pk, pf, vec_ok, 0);
+  PRAD_TRY(check_launch("pack_levels_kernel"));
+  SharedPack &sp = shared_pack();
+  sp.image = levels; sp.mask = mask; sp.n = n; sp.Ng = Ng; sp.levels = pk; sp.flags = pf;
+  return PRAD_OK;
+}
+void image_shared_pack_clear() { shared_pack() = SharedPack(); }
+}  // namespace prad
+namespace {
 
 // z-slab split of one large segment over several GPUs: integer accumulators of a plane range, summed by the
 // caller across ranks (RCCL all-reduce of [Ng][Na+1] int64), then finalized once
@@ -2066,39 +1696,6 @@ namespace prad {
 int zone_features_launch(Context &c, hipStream_t s, const double *P, int Ni, int Njcap, long long stride_i,
                          const double *jvals_d, const int *nj_dev, double *out_d, int *empty_d);   // prad_features.hip
 }
-#define ZM_FEATURES 16   // ZM_COUNT of kernels_features.h (static_assert there)
-namespace {
-template <typename T>
-int launch_digitize(const T *image, const uint8_t *mask, long long n, const double *e_d, int nedges, int32_t *levels,
-                    int *top, unsigned long long *counts_d, hipStream_t s) {
-  // 4 workgroups per CU: every workgroup ends with global atomics on the same few words (its maximum, its nb counters), and
-  // those serialise in L2 at ~25 ns each -- with 4096 workgroups they were half of the kernel (256^3 float64: 124 -> 57 us;
-  // roi_minmax 59 -> 35 with 512 instead of 2048; profiles/r03_probes.md, section 10)
-  static const int cap = getenv("PRAD_BIN_BLOCKS") ? atoi(getenv("PRAD_BIN_BLOCKS")) : 1024;
-  const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, cap));
-  const size_t edge_b = sizeof(double) * (size_t)nedges, cnt_b = 4 * sizeof(unsigned) * ((size_t)nedges + 1);
-  const bool lds_edges = edge_b <= 60 * 1024;
-  // counts in LDS while edges + four private tables fit 64 KB (nedges <= 2 700), otherwise straight global atomics
-  // (that many levels spread the atomics over as many addresses)
-  const size_t cnt3_b = 256 * sizeof(unsigned) * ((size_t)nedges + 1);     // a table per thread
-  const int counts = !counts_d ? 0 : (nedges <= 48 ? 3 : ((lds_edges && edge_b + cnt_b <= 64 * 1024) ? 1 : 2));
-#define PRAD_DIG(LE, CN)                                                                                              \
-  hipLaunchKernelGGL((digitize_kernel<T, LE, CN>), dim3(gx), dim3(256),                                               \
-                     (LE ? edge_b : 0) + (CN == 1 ? cnt_b : (CN == 3 ? cnt3_b : 0)), s, image, mask, n, e_d, nedges, levels, top, counts_d)
-  if (lds_edges) {
-    if (counts == 0) PRAD_DIG(true, 0);
-    else if (counts == 1) PRAD_DIG(true, 1);
-    else if (counts == 3) PRAD_DIG(true, 3);
-    else PRAD_DIG(true, 2);
-  } else {
-    if (counts == 0) PRAD_DIG(false, 0);
-    else PRAD_DIG(false, 2);
-  }
-#undef PRAD_DIG
-  return check_launch("digitize_kernel");
-}
-}  // namespace
-
 extern "C" {
 
 const char *prad_version(void) { return kVersion; }
@@ -2131,15 +1728,12 @@ int prad_set_device(int device) {
     if ((pipe_state().pending.valid || pipe_state().walked.valid) && c.device_set && hipSetDevice(c.device) == hipSuccess) {
       (void)pipeline_flush(c);   // a volume still pending or walked on the old device: retire it there
       if (pipe_state().s) (void)hipStreamSynchronize(pipe_state().s);
-      (void)fin_join(nullptr, true);
     }
     pipe_state().pending.valid = false;
     pipe_state().walked.valid = false;
     set_zero_forget();
     pipe_state().s = nullptr;
     pipe_state().ev = nullptr;
-    pipe_state().fin = nullptr;      // (the side stream and its events belonged to the old device)
-    for (int l = 0; l < 4; l++) pipe_state().fin_used[l] = false;
     c.own_stream = nullptr;  // streams belong to a device; new ones are created lazily
     for (int l = 0; l < PRAD_MAX_LANES; l++) {
       if (c.lane_stream[l]) (void)hipStreamSynchronize(c.lane_stream[l]);
@@ -2161,15 +1755,11 @@ long long prad_workspace_bytes(void) {
   for (const auto &kv : ctx().bufs) total += (long long)kv.second.cap;
   return total;
 }
-namespace {
-void release_image_queues();     // (prad_image_enqueue_dev's streams and events, defined with it below)
-}
 int prad_release_workspace(void) {
   Context &c = ctx();
   if (pipe_state().pending.valid || pipe_state().walked.valid) {   // their buffers are about to go away: retire them first
     (void)pipeline_flush(c);
     if (pipe_state().s) (void)hipStreamSynchronize(pipe_state().s);
-    (void)fin_join(nullptr, true);
     pipe_state().pending.valid = false;
     pipe_state().walked.valid = false;
   }
@@ -2279,7 +1869,6 @@ int prad_set_deferred_mode(int mode) {
   PipeState &ps = pipe_state();
   PRAD_TRY(pipeline_flush(c));
   if (ps.s) PRAD_HIP(hipStreamSynchronize(ps.s));
-  PRAD_TRY(fin_join(nullptr, true));
   PRAD_TRY(c.lanes_sync());
   ps.mode = mode;
   return PRAD_OK;
@@ -2305,7 +1894,6 @@ int prad_deferred_join(void *stream) {
     PRAD_HIP(hipEventRecord(ps.ev, ps.s));
     PRAD_HIP(hipStreamWaitEvent((hipStream_t)stream, ps.ev, 0));
   }
-  PRAD_TRY(fin_join((hipStream_t)stream, false));
   return c.lanes_join((hipStream_t)stream);
 }
 int prad_deferred_mark(int *flag, void *stream) {
@@ -2313,7 +1901,6 @@ int prad_deferred_mark(int *flag, void *stream) {
   PRAD_TRY(c.ensure_device());
   if (!flag || !c.in_arena(flag, sizeof(int))) return fail(PRAD_E_ARG, "deferred_mark: flag must lie in the result arena");
   PRAD_TRY(pipeline_flush(c));
-  PRAD_TRY(fin_join((hipStream_t)stream, false));
   int *sticky = nullptr;
   PRAD_TRY(c.get<int>("deferred_sticky", 16, &sticky));
   PRAD_HIP(hipMemcpyAsync(flag, sticky, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -2324,7 +1911,6 @@ int prad_deferred_status(void *stream) {
   PRAD_TRY(c.ensure_device());
   PRAD_TRY(pipeline_flush(c));
   if (pipe_state().s) PRAD_HIP(hipStreamSynchronize(pipe_state().s));
-  PRAD_TRY(fin_join(nullptr, true));
   PRAD_HIP(hipStreamSynchronize((hipStream_t)stream));
   PRAD_TRY(c.lanes_sync());
   if (!c.has("deferred_sticky")) return PRAD_OK;  // no deferred call yet
@@ -2377,6 +1963,55 @@ int prad_build_angles(const int *size, const int *distances, int Nd, int Ndist, 
                       int *angles) {
   if (!size || !distances || !angles || Nd < 1 || Ndist < 1) return 1;
   return angle_build(size, distances, Nd, Ndist, force2Ddim, Na, angles);
+}
+
+// The sweep plan of a segment-mode GLCM / GLRLM call as ints (the record's order: include/pyradiomics_amd.h).  Host only.
+int prad_debug_sweep_plan(const int *size, int Nd, const int *angles, int Na, int Ng, int Nr, int want_glcm, int want_glrlm,
+                          int cus, int *out, int cap) {
+  if (!size || !angles || !out || Nd < 1 || Nd > PRAD_MAX_ND || Na < 1 || cap < 1) return 0;
+  for (int d = 0; d < Nd; d++)
+    if (size[d] < 1) return 0;
+  PlanInput in;
+  in.nd = Nd;
+  in.size = size;
+  in.angles = angles;
+  in.Na = Na;
+  in.Ng = Ng;
+  in.Nr = Nr;
+  in.want_glcm = want_glcm != 0;
+  in.want_glrlm = want_glrlm != 0;
+  const SweepPlan p = plan_sweep(in, sweep_knobs_from_env(), cus > 0 ? cus : cu_count());
+  std::vector<int> r;
+  r.push_back(p.ok ? 1 : 0);
+  if (p.ok) {
+    for (int v : {p.Nz, p.Ny, p.Nx, (int)p.fused, (int)p.fw, (int)p.fw2, (int)p.fw2_rows, p.RS, p.RSr, p.RSfw, p.RSfw_rows, p.RS2,
+                  p.RS2r, (int)p.LONG, (int)p.LONGr, (int)p.LONGfw, (int)p.LONGfw2, (int)p.LONGfw2r, (int)p.lds_bytes,
+                  (int)p.lds_bytes_rows, (int)p.lds_fw, (int)p.lds_fw_rows, (int)p.lds_fw2, (int)p.lds_fw2_rows, p.threads,
+                  p.fw_threads, p.fw_rows_threads, p.fwK, p.fw_blocks, p.fw2_copies, p.fw2r_copies, p.fw2r_waves, p.LPL, p.pitch,
+                  p.padw, p.pitch16, (int)p.vec_rows, (int)p.skip1, p.row_slot, p.fw_xblocks, p.lines.count})
+      r.push_back(v);
+    for (int i = 0; i < p.lines.count; i++) {
+      const SweepDesc &D = p.lines.d[i];
+      for (int v : {D.slot, D.NM, D.NU, D.NX, D.du, D.dx, (int)D.sM, (int)D.sU, D.LXc, (int)D.chunks}) r.push_back(v);
+    }
+    r.push_back(p.aset.count);
+    for (int a = 0; a < p.aset.count; a++)
+      for (int d = 0; d < 3; d++) r.push_back(p.aset.off[a][d]);
+    r.push_back((p.fw || p.fw2) ? 1 : 0);
+    if (p.fw || p.fw2) {   // (the planner fills the set only for a fixed-window launch)
+      const FwSet &f = p.fwset;
+      for (int v : {f.count, f.NX, f.pitch, f.nrows, f.xcd}) r.push_back(v);
+      for (int i = 0; i < PRAD_MAX_SWEEP + 1; i++) r.push_back(f.first_block[i]);
+      for (int v : {f.xslot, f.xRS, f.xwaves, f.xgpd}) r.push_back(v);
+      for (int i = 0; i < f.count; i++) {
+        const FwDesc &D = f.d[i];
+        for (int v : {D.slot, D.NM, D.NU, D.du, D.dx, (int)D.sM, (int)D.sU, D.CL, D.pieces, D.chunks, D.dom_kind}) r.push_back(v);
+      }
+    }
+  }
+  if ((int)r.size() > cap) return -(int)r.size();
+  std::copy(r.begin(), r.end(), out);
+  return (int)r.size();
 }
 
 // ---- GLCM / GLRLM ---------------------------------------------------------------------------
@@ -2708,239 +2343,6 @@ int prad_voxel_texture_features_dev(int family, const int32_t *image, const uint
                                     force2Ddim, feature_ids, nfeat, out, (hipStream_t)stream);
 }
 
-// ---- on-device discretisation ----------------------------------------------------------------
-int prad_roi_minmax_dev(const void *image, int dtype, const uint8_t *mask, long long n, double *minmax, void *stream) {
-  Context &c = ctx();
-  PRAD_TRY(c.ensure_device());
-  if (!image || !mask || !minmax || n < 1) return fail(PRAD_E_ARG, "roi_minmax: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  unsigned long long *keys = nullptr;
-  PRAD_TRY(c.get<unsigned long long>("minmax_keys", 2, &keys));
-  // (pinned staging: a copy from / to pageable memory goes through the runtime's bounce buffer and blocks the host)
-  void *pin = nullptr;
-  PRAD_TRY(c.get_pinned("bin_pin", 4096, &pin));
-  unsigned long long *init = (unsigned long long *)pin, *outk = init + 2;
-  init[0] = ~0ull;
-  init[1] = 0ull;
-  PRAD_HIP(hipMemcpyAsync(keys, init, 2 * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-  static const int cap = getenv("PRAD_MINMAX_BLOCKS") ? atoi(getenv("PRAD_MINMAX_BLOCKS")) : 512;
-  const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, cap));
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(roi_minmax_kernel<float>, dim3(gx), dim3(256), 0, s, (const float *)image, mask, n, keys); break;
-    case 1: hipLaunchKernelGGL(roi_minmax_kernel<double>, dim3(gx), dim3(256), 0, s, (const double *)image, mask, n, keys); break;
-    case 2: hipLaunchKernelGGL(roi_minmax_kernel<int>, dim3(gx), dim3(256), 0, s, (const int *)image, mask, n, keys); break;
-    case 3: hipLaunchKernelGGL(roi_minmax_kernel<short>, dim3(gx), dim3(256), 0, s, (const short *)image, mask, n, keys); break;
-    default: return fail(PRAD_E_ARG, "roi_minmax: dtype %d", dtype);
-  }
-  PRAD_TRY(check_launch("roi_minmax_kernel"));
-  PRAD_HIP(hipMemcpyAsync(outk, keys, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  PRAD_HIP(hipStreamSynchronize(s));
-  if (outk[1] == 0ull) return fail(PRAD_E_ARG, "roi_minmax: empty ROI");
-  minmax[0] = f64_unkey(outk[0]);
-  minmax[1] = f64_unkey(outk[1]);
-  return PRAD_OK;
-}
-
-int prad_digitize_counts_dev(const void *image, int dtype, const uint8_t *mask, long long n, const double *edges,
-                             int nedges, int32_t *levels, int *max_level, long long *counts, void *stream) {
-  Context &c = ctx();
-  PRAD_TRY(c.ensure_device());
-  if (!image || !mask || !edges || !levels || n < 1 || nedges < 1) return fail(PRAD_E_ARG, "digitize: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  double *e_d = nullptr;
-  int *top = nullptr;
-  unsigned long long *cnt_d = nullptr;
-  PRAD_TRY(c.get<double>("bin_edges", (size_t)nedges, &e_d));
-  PRAD_TRY(c.get<int>("bin_top", 1, &top));
-  // host <-> device traffic of this call through one pinned block: [edges (nedges doubles) | top (8 B) | counts]
-  const size_t pin_bytes = sizeof(double) * ((size_t)nedges + 1) + sizeof(long long) * ((size_t)nedges + 2);
-  void *pin = nullptr;
-  PRAD_TRY(c.get_pinned("digitize_pin", pin_bytes, &pin));
-  double *e_h = (double *)pin;
-  int *top_h = (int *)(e_h + nedges);
-  long long *cnt_h = (long long *)(e_h + nedges + 1);
-  memcpy(e_h, edges, sizeof(double) * nedges);
-  PRAD_HIP(hipMemcpyAsync(e_d, e_h, sizeof(double) * nedges, hipMemcpyHostToDevice, s));
-  if (counts) {
-    // counts and the level maximum sit in ONE device block [top | counts]: one memset, one copy back
-    PRAD_TRY(c.get<unsigned long long>("bin_counts", (size_t)nedges + 2, &cnt_d));
-    PRAD_HIP(hipMemsetAsync(cnt_d, 0, sizeof(unsigned long long) * ((size_t)nedges + 2), s));
-    top = (int *)cnt_d;
-    cnt_d += 1;
-  } else {
-    PRAD_HIP(hipMemsetAsync(top, 0, sizeof(int), s));
-  }
-  switch (dtype) {
-    case 0: PRAD_TRY(launch_digitize((const float *)image, mask, n, e_d, nedges, levels, top, cnt_d, s)); break;
-    case 1: PRAD_TRY(launch_digitize((const double *)image, mask, n, e_d, nedges, levels, top, cnt_d, s)); break;
-    case 2: PRAD_TRY(launch_digitize((const int *)image, mask, n, e_d, nedges, levels, top, cnt_d, s)); break;
-    case 3: PRAD_TRY(launch_digitize((const short *)image, mask, n, e_d, nedges, levels, top, cnt_d, s)); break;
-    default: return fail(PRAD_E_ARG, "digitize: dtype %d", dtype);
-  }
-  if (counts) {
-    PRAD_HIP(hipMemcpyAsync(top_h, cnt_d - 1, sizeof(long long) * ((size_t)nedges + 2), hipMemcpyDeviceToHost, s));   // [top | counts]
-  } else {
-    PRAD_HIP(hipMemcpyAsync(top_h, top, sizeof(int), hipMemcpyDeviceToHost, s));
-  }
-  PRAD_HIP(hipStreamSynchronize(s));
-  if (max_level) *max_level = *top_h;
-  if (counts) memcpy(counts, cnt_h, sizeof(long long) * ((size_t)nedges + 1));
-  return PRAD_OK;
-}
-
-// the queueing half of prad_bincount_dev: slot in [0, PRAD_BIN_SLOTS) names the device block, the pinned block and the event
-namespace {
-constexpr int PRAD_BIN_SLOTS = 4;
-struct BinSlots {
-  int device = -1;
-  hipEvent_t done[PRAD_BIN_SLOTS] = {};
-  int nedges[PRAD_BIN_SLOTS] = {};
-  unsigned long long *host[PRAD_BIN_SLOTS] = {};
-  bool used[PRAD_BIN_SLOTS] = {};
-  unsigned seq = 0;
-};
-BinSlots &bin_slots() {
-  static thread_local BinSlots b;
-  return b;
-}
-int bincount_queue(Context &c, int slot, const void *image, int dtype, const uint8_t *mask, long long n, int binCount, int32_t *levels,
-                   hipStream_t s, unsigned long long **host_out) {
-  const int nedges = binCount + 1;
-  // one device block: [keys (2 u64) | info (8 B) | top (8 B) | counts (nedges + 1) | edges (nedges doubles)] -- one copy back
-  unsigned long long *blk = nullptr;
-  const size_t words = 2 + 1 + 1 + ((size_t)nedges + 1) + (size_t)nedges;
-  char name_blk[32], name_pin[32];
-  snprintf(name_blk, sizeof(name_blk), "bincount_blk%d", slot);
-  snprintf(name_pin, sizeof(name_pin), "bincount_pin%d", slot);
-  PRAD_TRY(c.get<unsigned long long>(name_blk, words, &blk));
-  unsigned long long *keys = blk;
-  int *info = (int *)(blk + 2), *top = (int *)(blk + 3);
-  unsigned long long *cnt_d = blk + 4;
-  double *e_d = (double *)(blk + 4 + (size_t)nedges + 1);
-  void *pin = nullptr;
-  PRAD_TRY(c.get_pinned(name_pin, sizeof(unsigned long long) * (words + 2), &pin));
-  unsigned long long *h = (unsigned long long *)pin;
-  PRAD_HIP(hipMemsetAsync(blk, 0, sizeof(unsigned long long) * words, s));
-  h[words] = ~0ull;
-  h[words + 1] = 0ull;
-  PRAD_HIP(hipMemcpyAsync(keys, h + words, 2 * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-  static const int cap = getenv("PRAD_MINMAX_BLOCKS") ? atoi(getenv("PRAD_MINMAX_BLOCKS")) : 512;
-  const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, cap));
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(roi_minmax_kernel<float>, dim3(gx), dim3(256), 0, s, (const float *)image, mask, n, keys); break;
-    case 1: hipLaunchKernelGGL(roi_minmax_kernel<double>, dim3(gx), dim3(256), 0, s, (const double *)image, mask, n, keys); break;
-    case 2: hipLaunchKernelGGL(roi_minmax_kernel<int>, dim3(gx), dim3(256), 0, s, (const int *)image, mask, n, keys); break;
-    default: hipLaunchKernelGGL(roi_minmax_kernel<short>, dim3(gx), dim3(256), 0, s, (const short *)image, mask, n, keys); break;
-  }
-  if (dtype == 0)
-    hipLaunchKernelGGL(bincount_edges_kernel<true>, dim3(1), dim3(256), 0, s, (const unsigned long long *)keys, binCount, e_d, info);
-  else
-    hipLaunchKernelGGL(bincount_edges_kernel<false>, dim3(1), dim3(256), 0, s, (const unsigned long long *)keys, binCount, e_d, info);
-  PRAD_TRY(check_launch("bincount_edges_kernel"));
-  switch (dtype) {
-    case 0: PRAD_TRY(launch_digitize((const float *)image, mask, n, e_d, nedges, levels, top, cnt_d, s)); break;
-    case 1: PRAD_TRY(launch_digitize((const double *)image, mask, n, e_d, nedges, levels, top, cnt_d, s)); break;
-    case 2: PRAD_TRY(launch_digitize((const int *)image, mask, n, e_d, nedges, levels, top, cnt_d, s)); break;
-    default: PRAD_TRY(launch_digitize((const short *)image, mask, n, e_d, nedges, levels, top, cnt_d, s)); break;
-  }
-  PRAD_HIP(hipMemcpyAsync(h, blk, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, s));
-  *host_out = h;
-  return PRAD_OK;
-}
-int bincount_collect(const unsigned long long *h, int nedges, double *minmax, double *edges, int *max_level, long long *counts) {
-  if (h[1] == 0ull) return fail(PRAD_E_ARG, "roi_minmax: empty ROI");
-  minmax[0] = f64_unkey(h[0]);
-  minmax[1] = f64_unkey(h[1]);
-  if (*(const int *)(h + 2))
-    return fail(PRAD_E_UNSUPPORTED, "bincount: constant or non-finite ROI (np.histogram widens the range: host-built edges)");
-  if (max_level) *max_level = *(const int *)(h + 3);
-  if (counts) memcpy(counts, h + 4, sizeof(long long) * ((size_t)nedges + 1));
-  if (edges) memcpy(edges, h + 4 + (size_t)nedges + 1, sizeof(double) * nedges);
-  return PRAD_OK;
-}
-}  // namespace
-
-int prad_bincount_dev(const void *image, int dtype, const uint8_t *mask, long long n, int binCount, int32_t *levels,
-                      double *minmax, double *edges, int *max_level, long long *counts, void *stream) {
-  Context &c = ctx();
-  PRAD_TRY(c.ensure_device());
-  if (!image || !mask || !levels || !minmax || n < 1) return fail(PRAD_E_ARG, "bincount: bad arguments");
-  if (dtype < 0 || dtype > 3) return fail(PRAD_E_ARG, "bincount: dtype %d", dtype);
-  if (binCount < 1 || binCount > 4096) return fail(PRAD_E_UNSUPPORTED, "bincount: binCount %d outside [1, 4096]", binCount);
-  hipStream_t s = (hipStream_t)stream;
-  unsigned long long *h = nullptr;
-  PRAD_TRY(bincount_queue(c, PRAD_BIN_SLOTS, image, dtype, mask, n, binCount, levels, s, &h));   // (a block of its own: no ticket)
-  PRAD_HIP(hipStreamSynchronize(s));
-  return bincount_collect(h, binCount + 1, minmax, edges, max_level, counts);
-}
-
-// prad_bincount_dev in two halves (round 6: the case pipeline bins image i + 1 while the host still works on image i): the
-// queueing half returns a ticket, prad_bincount_wait(ticket, ...) waits for THAT work only (an event behind its copy) and hands
-// over what prad_bincount_dev returns.  Up to four tickets per thread; a ticket must be waited for exactly once.
-int prad_bincount_enqueue_dev(const void *image, int dtype, const uint8_t *mask, long long n, int binCount, int32_t *levels,
-                              int *ticket, void *stream) {
-  Context &c = ctx();
-  PRAD_TRY(c.ensure_device());
-  if (!image || !mask || !levels || !ticket || n < 1) return fail(PRAD_E_ARG, "bincount_enqueue: bad arguments");
-  if (dtype < 0 || dtype > 3) return fail(PRAD_E_ARG, "bincount_enqueue: dtype %d", dtype);
-  if (binCount < 1 || binCount > 4096) return fail(PRAD_E_UNSUPPORTED, "bincount_enqueue: binCount %d outside [1, 4096]", binCount);
-  BinSlots &b = bin_slots();
-  if (b.device != c.device) {
-    for (int t = 0; t < PRAD_BIN_SLOTS; t++) {
-      if (b.done[t]) (void)hipEventDestroy(b.done[t]);
-      PRAD_HIP(hipEventCreateWithFlags(&b.done[t], hipEventDisableTiming));
-      b.used[t] = false;
-    }
-    b.device = c.device;
-  }
-  const int t = (int)(b.seq % PRAD_BIN_SLOTS);
-  if (b.used[t]) return fail(PRAD_E_ARG, "bincount_enqueue: %d binnings are in flight on this thread; prad_bincount_wait one first", PRAD_BIN_SLOTS);
-  hipStream_t s = (hipStream_t)stream;
-  PRAD_TRY(bincount_queue(c, t, image, dtype, mask, n, binCount, levels, s, &b.host[t]));
-  PRAD_HIP(hipEventRecord(b.done[t], s));
-  b.nedges[t] = binCount + 1;
-  b.used[t] = true;
-  b.seq++;
-  *ticket = t;
-  return PRAD_OK;
-}
-
-int prad_bincount_wait(int ticket, double *minmax, double *edges, int *max_level, long long *counts) {
-  Context &c = ctx();
-  PRAD_TRY(c.ensure_device());
-  BinSlots &b = bin_slots();
-  if (ticket < 0 || ticket >= PRAD_BIN_SLOTS || !b.used[ticket] || !minmax) return fail(PRAD_E_ARG, "bincount_wait: ticket %d", ticket);
-  b.used[ticket] = false;
-  PRAD_HIP(hipEventSynchronize(b.done[ticket]));
-  return bincount_collect(b.host[ticket], b.nedges[ticket], minmax, edges, max_level, counts);
-}
-
-int prad_digitize_dev(const void *image, int dtype, const uint8_t *mask, long long n, const double *edges, int nedges,
-                      int32_t *levels, int *max_level, void *stream) {
-  return prad_digitize_counts_dev(image, dtype, mask, n, edges, nedges, levels, max_level, nullptr, stream);
-}
-
-int prad_level_counts_dev(const int32_t *levels, const uint8_t *mask, long long n, int Ng, long long *counts,
-                          void *stream) {
-  Context &c = ctx();
-  PRAD_TRY(c.ensure_device());
-  if (!levels || !mask || !counts || n < 1 || Ng < 1) return fail(PRAD_E_ARG, "level_counts: bad arguments");
-  hipStream_t s = (hipStream_t)stream;
-  unsigned long long *d = nullptr;
-  const size_t nb = (size_t)Ng + 1;
-  PRAD_TRY(c.get<unsigned long long>("level_counts", nb, &d));
-  PRAD_HIP(hipMemsetAsync(d, 0, sizeof(unsigned long long) * nb, s));
-  // per-block partial sums are 32-bit: a block sees at most n / grid voxels, bounded below 2^32 by the grid size
-  const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, 1024));   // (flush atomics: see launch_digitize)
-  const int use_lds = 4 * nb * sizeof(unsigned) <= 48 * 1024;
-  hipLaunchKernelGGL(level_counts_kernel, dim3(gx), dim3(256), use_lds ? 4 * nb * sizeof(unsigned) : 0, s, levels, mask,
-                     n, Ng, use_lds, d);
-  PRAD_TRY(check_launch("level_counts_kernel"));
-  PRAD_HIP(hipMemcpyAsync(counts, d, sizeof(long long) * nb, hipMemcpyDeviceToHost, s));
-  PRAD_HIP(hipStreamSynchronize(s));
-  return PRAD_OK;
-}
-
 int prad_glszm_sizes(int *sizes, int capacity) {
   Context &c = ctx();
   PRAD_TRY(c.ensure_device());
@@ -2962,5 +2364,3 @@ long long prad_glszm_zones(int v, int *tempData, long long capacity_pairs) {
 
 
 }  // extern "C"
-
-#include "prad_image.h"   // the case pipeline's native half: image queues, prad_image_enqueue_dev, the launcher thread

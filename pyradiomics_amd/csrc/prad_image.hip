@@ -1,9 +1,18 @@
-// prad_image.h -- the case pipeline's native half (a textual part of prad_api.hip: it uses that unit's internal entry points;
-// split off in round 6 so that the dispatch code of the matrix calls and the pipeline's queues / launcher do not share a file):
+// prad_image.hip -- the case pipeline's native half, a host-only unit (no kernel header: what it needs of prad_api.hip's
+// internals it reaches through prad_internal.h):
 //   prad_image_enqueue_dev / prad_image_wait          every class of ONE derived image queued by one call on four side streams
 //   prad_image_submit / _result / _wait / _release    the same call issued by a launcher thread that belongs to the calling thread
-// Included by prad_api.hip only.
-#pragma once
+#include "prad_internal.h"
+
+#include <algorithm>
+#include <condition_variable>
+#include <cstdlib>
+#include <deque>
+#include <mutex>
+#include <thread>
+#include <vector>
+
+using namespace prad;
 
 // ---- one derived image, every class, one call (the case pipeline's enqueue half in native code) -------------------------
 // What pyradiomics_amd/featureextractor.py did with ~25 calls per derived image -- GLCM + GLRLM sweep, their formulas and the MCC
@@ -30,7 +39,8 @@ ImageQueues *image_queue_table() {
   return q;
 }
 ImageQueues &image_queues() { return image_queue_table()[ctx().device & 15]; }
-void release_image_queues() {
+}  // namespace
+extern "C" void release_image_queues(void) {
   ImageQueues *tab = image_queue_table();
   for (int d = 0; d < 16; d++) {
     ImageQueues &q = tab[d];
@@ -45,7 +55,6 @@ void release_image_queues() {
     q = ImageQueues();
   }
 }
-}  // namespace
 extern "C" {
 
 int prad_image_enqueue_dev(const int32_t *levels, const uint8_t *mask, const void *raw, int raw_dtype, const int *size,
@@ -84,7 +93,7 @@ int prad_image_enqueue_dev(const int32_t *levels, const uint8_t *mask, const voi
   } restore{c};
   const int one = 1;
   const int Na = angle_count(size, &one, Nd, 1, 0, force2Ddim), Nab = angle_count(size, &one, Nd, 1, 1, force2Ddim);
-  if (Na < 1 || Nab < 1 || Na > PRAD_MAX_SWEEP) return fail(PRAD_E_UNSUPPORTED, "image_enqueue: %d / %d angles", Na, Nab);
+  if (Na < 1 || Nab < 1 || Na > kMaxSweepAngles) return fail(PRAD_E_UNSUPPORTED, "image_enqueue: %d / %d angles", Na, Nab);
   std::vector<int> ang((size_t)Na * Nd), angb((size_t)Nab * Nd);
   if (angle_build(size, &one, Nd, 1, force2Ddim, Na, ang.data()) || angle_build(size, &one, Nd, 1, force2Ddim, Nab, angb.data()))
     return fail(PRAD_E_ARG, "image_enqueue: angles");
@@ -126,25 +135,11 @@ int prad_image_enqueue_dev(const int32_t *levels, const uint8_t *mask, const voi
   // ONE byte-packed copy of the volume for the neighbourhood pass and the GLSZM (each of them packed for itself until round 6),
   // made on the caller's stream in front of the fork; a buffer per ticket: up to four images are in flight
   struct ClearShared {
-    ~ClearShared() { shared_pack() = SharedPack(); }
+    ~ClearShared() { image_shared_pack_clear(); }
   } clear_shared;
   if ((classes & (PRAD_IMG_GLDM | PRAD_IMG_NGTDM | PRAD_IMG_GLSZM)) && Nd <= 3 && Ng <= 255 && n < 0x7fffffffLL &&
       !getenv("PRAD_IMG_NO_SHARED_PACK")) {
-    char name[32];
-    snprintf(name, sizeof(name), "img_pack%d", (int)(q.seq % PRAD_IMG_TICKETS));
-    uint8_t *pk = nullptr;
-    int *pf = nullptr;
-    c.workspace = 0;
-    PRAD_TRY(c.get<uint8_t>(name, (size_t)n + 64 + 16, &pk));
-    pf = (int *)(pk + (((size_t)n + 64 + 3) & ~(size_t)3));
-    PRAD_HIP(hipMemsetAsync(pf, 0, sizeof(int) * 2, (hipStream_t)stream));
-    const int vec_ok = ((((uintptr_t)levels) | ((uintptr_t)mask) | ((uintptr_t)pk)) & 15) == 0;
-    const int NX = size[Nd - 1];
-    const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((n / 16 + 255) / 256, 4096));
-    hipLaunchKernelGGL(pack_levels_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, levels, mask, n, NX, NX, 0, Ng, pk, pf, vec_ok, 0);
-    PRAD_TRY(check_launch("pack_levels_kernel"));
-    SharedPack &sp = shared_pack();
-    sp.image = levels; sp.mask = mask; sp.n = n; sp.Ng = Ng; sp.levels = pk; sp.flags = pf;
+    PRAD_TRY(image_shared_pack(c, levels, mask, n, size[Nd - 1], Ng, (int)(q.seq % PRAD_IMG_TICKETS), (hipStream_t)stream));
   }
   // the side streams wait for everything queued on the caller's stream (binning produced the levels there)
   PRAD_HIP(hipEventRecord(q.in, (hipStream_t)stream));

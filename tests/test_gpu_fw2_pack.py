@@ -199,7 +199,7 @@ def _check_x(cm, checker, img, mask, Ng):
 @pytest.mark.parametrize("Ng", [64, 100, 128, 160, 45])
 @pytest.mark.parametrize("nx", [512, 300, 72])
 def test_fw2_rows_runs_around_the_last_length_slot(cm, checker, Ng, nx):
-    """runs along x of every length from 18 to 81 -- the table keeps 48 .. 63 length slots at these level counts (prad_api.hip
+    """runs along x of every length from 18 to 81 -- the table keeps 48 .. 63 length slots at these level counts (prad_sweep_plan.h
     plan_sweep; PRAD_FW2_ROWS_WAVES moves them), so lengths below, at and above the last slot -- starting at every offset of
     the 8-voxel blocks the plain path vouches for, ending inside the row, at the row's last voxel and at the ROI's edge; a
     run longer than the slots goes to the global table"""
