@@ -392,6 +392,7 @@ inline int neigh_accumulate(Context *c, hipStream_t s, const Geo &g, const VoxMo
     PRAD_HIP(hipMemsetAsync(acc32, 0, sizeof(u32) * nacc, s));
     *acc_out = acc32;
   }
+  c->last_variant = "none";      // (an empty plane range launches nothing)
   if (zhi > zlo) {
     Timed t(*c, "neigh", s);
     const size_t lds = (NGTDM ? sizeof(u64) : sizeof(u32)) * nacc;
@@ -402,7 +403,9 @@ inline int neigh_accumulate(Context *c, hipStream_t s, const Geo &g, const VoxMo
       // (grid: neigh_blocks above)
       const unsigned bt = neigh_threads();
       const unsigned gx = neigh_blocks(ncent >> 2, bt);
-      if (row_masks_full26(R))
+      const bool full26 = row_masks_full26(R);
+      c->last_variant = full26 ? "neigh4-full26" : "neigh4-rows";
+      if (full26)
         hipLaunchKernelGGL((neigh4_kernel<NGTDM, true>), dim3(gx), dim3(bt), lds, s, R, levels, p.Nz, p.Ny, p.Nx, zlo, zhi,
                            Ng, Na, acc32, acc64, flags_d);
       else
@@ -410,6 +413,7 @@ inline int neigh_accumulate(Context *c, hipStream_t s, const Geo &g, const VoxMo
                            Ng, Na, acc32, acc64, flags_d);
       PRAD_TRY(check_launch("neigh4_kernel"));
     } else {
+      c->last_variant = "neigh1";
       const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((ncent + 255) / 256, 4096));
       hipLaunchKernelGGL((neigh_kernel<NGTDM>), dim3(gx), dim3(256), lds, s, p.set, levels, p.Nz, p.Ny, p.Nx, zlo,
                          zhi, Ng, alpha, acc32, acc64, flags_d);
@@ -455,7 +459,9 @@ inline int neigh_try_both(Context *c, hipStream_t s, const Geo &g, const VoxMode
     const long long ncent = (long long)p.Nz * p.Ny * p.Nx;
     const unsigned bt = neigh_threads();
     const unsigned gx = neigh_blocks(ncent >> 2, bt);
-    if (row_masks_full26(R))
+    const bool full26 = row_masks_full26(R);
+    c->last_variant = full26 ? "neigh4-full26" : "neigh4-rows";
+    if (full26)
       hipLaunchKernelGGL((neigh4_kernel<2, true>), dim3(gx), dim3(bt), (sizeof(u64) + sizeof(u32)) * nacc, s, R, levels, p.Nz, p.Ny,
                          p.Nx, 0, p.Nz, Ng, Na, acc32, acc64, flags_d);
     else

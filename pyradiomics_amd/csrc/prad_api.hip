@@ -1285,8 +1285,13 @@ int pairs_neigh(Call &k, bool ngtdm, int Ng, int alpha, double *out, bool *used,
       want = std::max(want, (k.g.n + cap - 1) / cap);
     }
     const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((k.g.n + bt - 1) / bt, want));
+    // which bin placement (and which box-sum word) serves the call: prad_last_variant()
+    static const char *const kVariant[3][3] = {{"pairs-global", "pairs-global+box32", "pairs-global+box64"},
+                                               {"pairs-lds64", "pairs-lds64+box32", "pairs-lds64+box64"},
+                                               {"pairs-lds32", "pairs-lds32+box32", "pairs-lds32+box64"}};
+    const bool narrow = box && cube <= 127 && cube * Ng < (1LL << 24);      // (ROI voxels << 24 | level sum) fits 32 bits
+    c.last_variant = kVariant[!ngtdm && mode ? 2 : mode][box ? (narrow ? 1 : 2) : 0];   // (the label names the LDS bin width: GLDM's are u32)
     if (box) {
-      const bool narrow = cube <= 127 && cube * Ng < (1LL << 24);      // (ROI voxels << 24 | level sum) fits 32 bits
       void *b1 = nullptr, *b2 = nullptr;
       PRAD_TRY(c.get("pairs_box1", (size_t)k.g.n * (narrow ? 4 : 8), &b1));
       PRAD_TRY(c.get("pairs_box2", (size_t)k.g.n * (narrow ? 4 : 8), &b2));
@@ -1377,6 +1382,7 @@ int texture_gldm(const int32_t *image, const uint8_t *mask, const int *size, int
     PRAD_TRY(generic_gldm(k, Ng, alpha, out));
     PRAD_TRY(read_flags(k));
     c.last_path = "generic";
+    c.last_variant = "none";
   }
   PRAD_TRY(c.end_call(s));
   PRAD_HIP(hipStreamSynchronize(s));
@@ -1427,6 +1433,7 @@ int texture_ngtdm(const int32_t *image, const uint8_t *mask, const int *size, in
     PRAD_TRY(generic_ngtdm(k, Ng, out));
     PRAD_TRY(read_flags(k));
     c.last_path = "generic";
+    c.last_variant = "none";
   }
   PRAD_TRY(c.end_call(s));
   PRAD_HIP(hipStreamSynchronize(s));

@@ -588,7 +588,8 @@ def last_path() -> str:
 
 
 def last_variant() -> str:
-    """which sweep kernels served the last GLCM / GLRLM call: "fw", "fw2" or "lines" """
+    """which kernels served the last call: "fw", "fw2", "lines" or "pairs" for GLCM / GLRLM; "neigh4-full26", "neigh4-rows",
+    "neigh1" or "pairs-lds64|lds32|global[+box32|+box64]" for GLDM / NGTDM (INTEGRATION.md)"""
     return _lib.last_variant()
 
 
