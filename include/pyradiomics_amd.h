@@ -540,6 +540,19 @@ int prad_batch_plan(const int *sizes, int B, int Ng, int families, const int *di
 int prad_calculate_batch_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B, int Ng,
                              int families, const int *distances, int Ndist, int alpha, double *glcm, double *glrlm,
                              double *gldm, double *ngtdm, int *status, void *stream);
+/* force2D on the batched route.  force2Ddim: -1 none -- the two functions above are these with -1 --, or 0 / 1 / 2, the axis (z,
+ * y, x) that no angle may leave: the last argument of prad_get_angle_count / prad_build_angles, from which the counts and the
+ * angle tables of every ROI come, as they do for the single calls.  Everything else is as above: the same layouts with the
+ * forced Na / Na1, the same domain, the same synchronisation.  A ROI whose angles all vanish under the forced dimension (a
+ * 5 x 1 x 1 box with dimension 0; the 1 x 1 x 1 box with any) is legal: Na = Na1 = 0, its GLCM and GLRLM are empty, its GLDM
+ * [Ng][1] counts the masked voxels per level and its NGTDM is (count, 0, level): the matrices of voxels without neighbours,
+ * what the reference's cmatrices.c computes from an empty angle table.  prad_last_path "batch"; prad_last_variant "batch-lds"
+ * for -1, "batch-lds-f2d" otherwise (the kernel is the same one: it consumes whatever table it is given). */
+int prad_batch_plan_f2d(const int *sizes, int B, int Ng, int families, const int *distances, int Ndist, int force2Ddim,
+                        long long *out_offsets, int *Na);
+int prad_calculate_batch_f2d_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B,
+                                 int Ng, int families, const int *distances, int Ndist, int alpha, int force2Ddim, double *glcm,
+                                 double *glrlm, double *gldm, double *ngtdm, int *status, void *stream);
 
 /* ---- GLSZM of many small ROIs (csrc/kernels_batch_glszm.h) -------------------------------------------------------------
  * The same batch layout (levels / mask DEVICE, sizes [B][3] / off HOST).  One workgroup per ROI packs the box into LDS and
@@ -570,6 +583,15 @@ int prad_batch_glszm_dev(const int32_t *levels, const uint8_t *mask, const int *
 int prad_batch_glszm_fill_dev(const int *zones, const int *summary_host, const long long *off, int B, int Ng, int compact,
                               double *out, const long long *out_offsets, int *sizes_out, const long long *sizes_offsets,
                               void *stream);
+/* prad_batch_glszm_f2d_dev: prad_batch_glszm_dev (which is this call with force2Ddim = -1) with the neighbourhood of force2D:
+ *   force2Ddim 0 / 1 / 2 joins a voxel to its up to 8 neighbours in the plane of the two OTHER axes (z, y, x) -- the angle
+ *   set the single call is given with that forced dimension --, so zones never cross a plane.  The neighbourhood is a
+ *   compile-time variant of the labelling kernel; outputs, order of the zone list, domain (the LDS budget does not depend on
+ *   the neighbourhood: prad_batch_glszm_max_vox()) and synchronisation are unchanged, and prad_batch_glszm_fill_dev serves
+ *   all variants.  prad_last_path "batch"; prad_last_variant "batch-glszm-lds" for -1, "batch-glszm-lds-f2d0" / "-f2d1" /
+ *   "-f2d2" otherwise.  A force2Ddim outside [-1, 2] is PRAD_E_ARG. */
+int prad_batch_glszm_f2d_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B, int Ng,
+                             int force2Ddim, int *zones, int *summary, int *status, void *stream);
 
 /* ---- feature formulas of many small ROIs (csrc/kernels_batch_features.h) -------------------------------------------------
  * The formulas of prad_glcm_features_dev, prad_glcm_mcc_dev, prad_zone_matrix_features_dev and prad_ngtdm_features_dev on the
@@ -609,6 +631,31 @@ int prad_batch_features_dev(const int *sizes, int B, int Ng, int families, const
                             const long long *offsets, const double *glszm, const long long *glszm_offsets,
                             const int *glszm_sizes, const long long *glszm_sizes_offsets, int symmetric, int want_mcc,
                             double *out, int *empty, void *stream);
+
+/* ---- weighted angle merge of many small ROIs: weightingNorm (csrc/kernels_batch_merge.h) --------------------------------------
+ * One launch for the whole batch turns the per-angle GLCM and GLRLM buffers of prad_calculate_batch[_f2d]_dev into ONE matrix
+ * per ROI, what the feature classes form with weightingNorm set:
+ *   PRAD_BATCH_GLCM   glcm_w  float64 [Ng][Ng][1]       glcm_w[i][j]  = sum_a w_a * (P[i][j][a] + (symmetric ? P[j][i][a] : 0))
+ *   PRAD_BATCH_GLRLM  glrlm_w float64 [Ng][Nr][1]       glrlm_w[i][r] = sum_a w_a * R[i][r][a],   Nr = max(size[b])
+ * ROI after ROI in flat buffers.  The sum runs over a ascending from 0.0, every term a rounded product followed by a rounded add
+ * (no FMA contraction), so the result depends on the inputs alone and equals the host loop `acc = acc + P[..., a] * w[a]` bit
+ * for bit.  Work is divided by output cells (records of up to 1024 cells of one matrix), every element is written, a ROI with
+ * no angle of a family or with status != PRAD_OK gets zeros.  prad_batch_features_dev then takes the merged buffers with Na =
+ * Na1 = 1 for every ROI and symmetric = 0 (the merge has symmetrised); MCC is evaluated on the merged matrix.
+ * prad_batch_merge_plan (host only, needs no device): Na is the int [2][B] of prad_batch_plan[_f2d]; out_offsets int64
+ *   [3][B + 1]: row 0 / 1 = first double of ROI b in glcm_w / glrlm_w (all zero for a family not in `families`), row 2 = first
+ *   weight of ROI b in `weights`; [.][B] = the lengths.  The weights of ROI b are Na[0][b] doubles for its GLCM angles followed
+ *   by Na[1][b] doubles for its GLRLM angles, each in the order of the ROI's rows of prad_build_angles (both always present,
+ *   whatever `families`).
+ * prad_batch_merge_angles_dev: sizes / Na / offsets / weights HOST; glcm / glrlm / status / glcm_w / glrlm_w DEVICE.  offsets
+ *   int64 [4][B + 1] as prad_batch_plan[_f2d] writes them (rows 0 and 1 are read); status: the int [B] of the matrix call, or
+ *   NULL (every ROI counts).  families: a non-empty subset of PRAD_BATCH_GLCM | PRAD_BATCH_GLRLM, else PRAD_E_ARG.  Covered:
+ *   every valid argument with fewer than 2^31 cells per matrix.  Enqueues one copy (records and weights) and one launch on
+ *   `stream` and synchronises it; kernel family "batch_merge"; prad_last_path "batch", prad_last_variant "batch-merge". */
+int prad_batch_merge_plan(const int *sizes, int B, int Ng, int families, const int *Na, long long *out_offsets);
+int prad_batch_merge_angles_dev(const int *sizes, int B, int Ng, int families, const int *Na, const double *glcm,
+                                const double *glrlm, const long long *offsets, const double *weights, const int *status,
+                                int symmetric, double *glcm_w, double *glrlm_w, void *stream);
 
 /* ---- first-order statistics and discretisation of many small ROIs (csrc/kernels_batch_firstorder.h) --------------------
  * The front end of the batched route: raw intensity boxes in, the statistics of prad_firstorder_dev and the levels and level

@@ -336,21 +336,97 @@ def batch_family_bits(families) -> int:
     return sum(1 << BATCH_FAMILIES.index(f) for f in set(families))
 
 
-def batch_plan(sizes, Ng, families=BATCH_FAMILIES, distances=(1,)):
-    """Host-side layout of a batch (prad_batch_plan; needs no device).  sizes: int [B, 3].  -> (covered, offsets int64
+def batch_forced_dim(force2D, force2Ddimension) -> int:
+    """the C `force2Ddim` of the batched calls: -1 without force2D, else the axis (0 z, 1 y, 2 x) no angle may leave"""
+    if not force2D:
+        return -1
+    d = int(force2Ddimension)
+    if not 0 <= d <= 2:
+        raise ValueError("force2Ddimension must be 0, 1 or 2 for 3-D ROIs, got %r" % (force2Ddimension,))
+    return d
+
+
+def batch_plan(sizes, Ng, families=BATCH_FAMILIES, distances=(1,), force2D=False, force2Ddimension=0):
+    """Host-side layout of a batch (prad_batch_plan_f2d; needs no device).  sizes: int [B, 3].  -> (covered, offsets int64
     [4, B + 1], Na int32 [2, B]): covered = the native call takes the batch; offsets[f] = first double of every ROI in the
     flat buffer of family BATCH_FAMILIES[f] (last entry: its length); Na[0] = unidirectional angle count of `distances`
-    (GLCM; GLDM rows hold 2 * (2 * Na) + 1 columns), Na[1] = that of distance 1 (GLRLM)."""
+    (GLCM; GLDM rows hold 2 * (2 * Na) + 1 columns), Na[1] = that of distance 1 (GLRLM) -- with force2D the counts of
+    generate_angles(size, distances, False, True, force2Ddimension), 0 where no angle is left."""
     sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
     dist = np.ascontiguousarray(np.asarray(distances, dtype=np.intc).ravel())
     B = int(sizes.shape[0])
     offsets = np.zeros((4, B + 1), dtype=np.int64)
     Na = np.zeros((2, B), dtype=np.intc)
-    rc = _lib.load().prad_batch_plan(_iptr(sizes), B, int(Ng), batch_family_bits(families), _iptr(dist), int(dist.shape[0]),
-                                     offsets.ctypes.data_as(C.POINTER(C.c_longlong)), _iptr(Na))
+    rc = _lib.load().prad_batch_plan_f2d(_iptr(sizes), B, int(Ng), batch_family_bits(families), _iptr(dist), int(dist.shape[0]),
+                                         batch_forced_dim(force2D, force2Ddimension),
+                                         offsets.ctypes.data_as(C.POINTER(C.c_longlong)), _iptr(Na))
     if rc != _lib.PRAD_OK and rc != _lib.PRAD_E_UNSUPPORTED:
         _lib.raise_for(rc, "batch plan")
     return rc == _lib.PRAD_OK, offsets, Na
+
+
+MERGE_FAMILIES = ("glcm", "glrlm")       # the families weightingNorm merges: bit f of the C `families`, row f of the merge plan
+
+
+def batch_merge_plan(sizes, Ng, Na, families=MERGE_FAMILIES):
+    """Host-side layout of the weighted angle merge (prad_batch_merge_plan; needs no device).  Na: the int [2, B] of
+    batch_plan.  -> offsets int64 [3, B + 1]: rows 0 / 1 = first double of every ROI's merged GLCM [Ng, Ng, 1] / GLRLM [Ng,
+    max(size), 1] in its flat buffer (zeros for a family not asked for), row 2 = first weight of every ROI in the flat weight
+    table (Na[0, b] GLCM weights, then Na[1, b] GLRLM weights); last entries: the lengths."""
+    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
+    Na = np.ascontiguousarray(np.asarray(Na, dtype=np.intc).reshape(2, -1))
+    B = int(sizes.shape[0])
+    if Na.shape[1] != B or not families or any(f not in MERGE_FAMILIES for f in families):
+        raise ValueError("batch_merge_plan: Na must be [2, B], families a non-empty subset of %s" % (MERGE_FAMILIES,))
+    offsets = np.zeros((3, B + 1), dtype=np.int64)
+    rc = _lib.load().prad_batch_merge_plan(_iptr(sizes), B, int(Ng), sum(1 << MERGE_FAMILIES.index(f) for f in set(families)),
+                                           _iptr(Na), offsets.ctypes.data_as(C.POINTER(C.c_longlong)))
+    _lib.raise_for(rc, "batch merge plan")
+    return offsets
+
+
+def batch_spacing(spacing, B):
+    """`spacing` of the batched calls -- one (z, y, x) triple or a float array [B, 3] -- as float64 [B, 3]"""
+    sp = np.asarray(spacing, dtype=np.float64)
+    if sp.shape == (3,):
+        sp = np.broadcast_to(sp, (B, 3))
+    if sp.shape != (B, 3):
+        raise ValueError("spacing must be one (z, y, x) triple or an array [B, 3]")
+    return np.ascontiguousarray(sp)
+
+
+def batch_weighting_norm(weightingNorm):
+    """None, or one of the names paramcheck accepts; anything else is a ValueError (the classes only warn)"""
+    from .paramcheck import _WEIGHTINGS
+    if weightingNorm is not None and weightingNorm not in _WEIGHTINGS:
+        raise ValueError("weightingNorm must be None or one of %s, got %r" % (_WEIGHTINGS, weightingNorm))
+    return weightingNorm
+
+
+def batch_weights(sizes, Na, distances, weightingNorm, spacing=(1.0, 1.0, 1.0), force2D=False, force2Ddimension=0):
+    """The flat weight table of the weighted angle merge, in the layout of batch_merge_plan's row 2: per ROI the GLCM weights of
+    its Na[0, b] angles, then the GLRLM weights of its Na[1, b] distance-1 angles, both from glcm._weights -- the one function the
+    feature classes use -- on the ROI's own angle rows and spacing.  -> float64 [sum(Na)]."""
+    import logging
+    from .glcm import _weights
+    sizes = np.asarray(sizes, dtype=np.intc).reshape(-1, 3)
+    sp = batch_spacing(spacing, len(sizes))
+    f2d = batch_forced_dim(force2D, force2Ddimension)
+    norm, log = batch_weighting_norm(weightingNorm), logging.getLogger(__name__)
+    parts = [np.zeros(0)]
+    seen = {}          # (size, spacing) -> the ROI's weights: a table of lesions repeats few box shapes
+    for b, size in enumerate(sizes):
+        key = (size.tobytes(), sp[b].tobytes())
+        if key not in seen:
+            size = np.ascontiguousarray(size)
+            one = [np.zeros(0)]
+            if Na[0][b]:
+                one.append(_weights(_build_angles(size, distances, False, f2d), sp[b], norm, "glcm", log))
+            if Na[1][b]:
+                one.append(_weights(_build_angles(size, None, False, f2d), sp[b], norm, "glrlm", log))
+            seen[key] = np.concatenate(one)
+        parts.append(seen[key])
+    return np.ascontiguousarray(np.concatenate(parts))
 
 
 def batch_shapes(sizes, Ng, Na):
@@ -362,33 +438,43 @@ def batch_shapes(sizes, Ng, Na):
             "ngtdm": [(Ng, 3) for _ in Na[0]]}
 
 
-def _one_voxel_matrices(level, masked, Ng, fam):
-    """the matrices of a 1 x 1 x 1 box (no angle exists: the single calls refuse it, cmatrices.c computes these)"""
+def _host_box(image, mask):
+    """(levels, mask) of one ROI as numpy arrays, wherever they live"""
+    back = lambda t: t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    return back(image), back(mask) != 0
+
+
+def _no_angle_matrices(image, mask, Ng, fam):
+    """Family `fam` of a box in which no angle of the family fits -- 1 x 1 x 1, or every angle removed by the forced dimension
+    (5 x 1 x 1 with dimension 0): the single calls refuse it, cmatrices.c computes these from an empty angle table.  GLCM and
+    GLRLM have no angle; every masked voxel is a voxel without neighbours: dependence 0 (GLDM [Ng, 1] = voxels per level),
+    NGTDM (voxels per level, 0, level)."""
     if fam in ("glcm", "glrlm"):
-        return np.zeros((Ng, Ng if fam == "glcm" else 1, 0))
+        return np.zeros((Ng, Ng if fam == "glcm" else int(max(image.shape)), 0))
+    lv, mk = _host_box(image, mask)
+    inside = lv[mk].astype(np.int64)
+    if inside.size and (inside.min() < 1 or inside.max() > Ng):
+        raise IndexError("level outside [1, Ng]")
     out = np.zeros((Ng, 1 if fam == "gldm" else 3))
+    out[:, 0] = np.bincount(inside, minlength=Ng + 1)[1:]
     if fam == "ngtdm":
         out[:, 2] = np.arange(1, Ng + 1)
-    if masked:
-        if not 1 <= level <= Ng:
-            raise IndexError("level outside [1, Ng]")
-        out[level - 1, 0] = 1
     return out
 
 
 def _looped_matrices(rois, Ng, families, shapes, single, wrap=lambda a: a):
     """The looped route: every ROI of `rois`, pairs (image, mask), through the single calls -> ({family: [B matrices]}, status).
     single[f](image, mask) is the call of family f; wrap makes the caller's kind of result of a numpy matrix (the device route
-    puts it where its other results are)."""
+    puts it where its other results are).  A family without an angle in a box (its planned shape says so) is not sent to the
+    single call, which would refuse the box."""
     _set_batch_route("looped")
     mats, status = {f: [] for f in families}, []
     for b, (image, mask) in enumerate(rois):
+        no_angle = {"glcm": shapes["glcm"][b][2] == 0, "glrlm": shapes["glrlm"][b][2] == 0}
+        no_angle["gldm"] = no_angle["ngtdm"] = no_angle["glcm"]
         try:
-            if int(np.prod(image.shape)) == 1:      # no angle exists: the single calls refuse the box
-                lv, mk = int(image.reshape(-1)[0]), bool(mask.reshape(-1)[0])
-                one = {f: wrap(_one_voxel_matrices(lv, mk, Ng, f)) for f in families}
-            else:
-                one = {f: single[f](image, mask) for f in BATCH_FAMILIES if f in families}
+            one = {f: (wrap(_no_angle_matrices(image, mask, Ng, f)) if no_angle[f] else single[f](image, mask))
+                   for f in BATCH_FAMILIES if f in families}
             status.append(_lib.PRAD_OK)
         except IndexError:          # a masked level outside [1, Ng]: as the native route, the matrices of an empty mask
             one = {f: np.zeros(shapes[f][b]) for f in families}
@@ -401,31 +487,59 @@ def _looped_matrices(rois, Ng, families, shapes, single, wrap=lambda a: a):
     return mats, status
 
 
-def _one_voxel_glszm(level, masked, Ng, compact, wrap):
-    """the GLSZM of a 1 x 1 x 1 box (no angle exists: the single call refuses it), dense or as calculate_glszm_compact"""
-    if masked and not 1 <= level <= Ng:
+def merge_looped(mats, sizes, Na, distances, weightingNorm, spacing, force2D, force2Ddimension, symmetric, wrap=lambda a: a):
+    """The weighted angle merge on the host, for the looped routes: adds "glcm_w" / "glrlm_w" to `mats` for the families it
+    holds, with the arithmetic of the merge launch (kernels_batch_merge.h) -- transpose added first, then acc = acc + P[..., a] *
+    w[a] over a ascending in float64 -- so that "looped", "mixed" and "batch" agree bit for bit."""
+    w = batch_weights(sizes, Na, distances, weightingNorm, spacing, force2D, force2Ddimension)
+    at = 0
+    for f in MERGE_FAMILIES:
+        if f in mats:
+            mats[f + "_w"] = []
+    for b in range(len(sizes)):
+        for k, f in enumerate(MERGE_FAMILIES):
+            n = int(Na[k][b])
+            if f in mats:
+                P = mats[f][b].cpu().numpy() if hasattr(mats[f][b], "cpu") else np.asarray(mats[f][b])
+                if f == "glcm" and symmetric:
+                    P = P + P.transpose(1, 0, 2)
+                acc = np.zeros(P.shape[:2] + (1,))
+                for a in range(n):
+                    acc[..., 0] = acc[..., 0] + P[..., a] * w[at + a]
+                mats[f + "_w"].append(wrap(acc))
+            at += n
+    return mats
+
+
+def _no_angle_glszm(image, mask, Ng, compact, wrap):
+    """the GLSZM of a box without neighbours (1 x 1 x 1, or every neighbour removed by the forced dimension: the single call
+    refuses it): every masked voxel is a zone of size 1; dense or as calculate_glszm_compact"""
+    lv, mk = _host_box(image, mask)
+    inside = lv[mk].astype(np.int64)
+    if inside.size and (inside.min() < 1 or inside.max() > Ng):
         raise IndexError("level outside [1, Ng]")
     P = np.zeros((Ng, 1))
-    if masked:
-        P[level - 1, 0] = 1
+    P[:, 0] = np.bincount(inside, minlength=Ng + 1)[1:]
     if not compact:
         return wrap(P)
-    return (wrap(P), np.ones(1, dtype=np.intc)) if masked else (wrap(P[:, :0]), np.zeros(0, dtype=np.intc))
+    return (wrap(P), np.ones(1, dtype=np.intc)) if inside.size else (wrap(P[:, :0]), np.zeros(0, dtype=np.intc))
 
 
-def _looped_glszm(rois, Ng, compact, single, wrap=lambda a: a):
+def _looped_glszm(rois, Ng, compact, single, wrap=lambda a: a, f2d=-1):
     """every ROI of `rois`, pairs (image, mask), through the single call -> (results, status): single(image, mask, Ns) is that
-    call, dense or compact as asked for; wrap as in _looped_matrices"""
+    call, dense or compact as asked for; wrap as in _looped_matrices; f2d: the forced dimension the single call is given"""
     results, status = [], []
+    lib, one = _lib.load(), np.ones(1, dtype=np.intc)
     for image, mask in rois:
         try:
-            if int(np.prod(image.shape)) == 1:
-                results.append(_one_voxel_glszm(int(image.reshape(-1)[0]), bool(mask.reshape(-1)[0]), Ng, compact, wrap))
+            size = np.array(image.shape, dtype=np.intc)
+            if lib.prad_get_angle_count(_iptr(size), _iptr(one), 3, 1, 1, int(f2d)) == 0:
+                results.append(_no_angle_glszm(image, mask, Ng, compact, wrap))
             else:
                 results.append(single(image, mask, max(1, int(mask.sum()))))
             status.append(_lib.PRAD_OK)
         except IndexError:          # as the native route: status 0, the result of an empty mask
-            results.append(_one_voxel_glszm(0, False, Ng, compact, wrap))
+            results.append(_no_angle_glszm(np.zeros((1, 1, 1), dtype=np.intc), np.zeros((1, 1, 1), dtype=bool), Ng, compact, wrap))
             status.append(_lib.PRAD_INDEX_ERROR)
     return results, status
 
@@ -469,10 +583,13 @@ def _host_roi_batch(images, masks, noun, raw=False, loops=False):
     return imgs, msks, sizes, upload
 
 
-def calculate_matrices_batch(images, masks, Ng, families=BATCH_FAMILIES, distances=(1,), gldm_a=0):
+def calculate_matrices_batch(images, masks, Ng, families=BATCH_FAMILIES, distances=(1,), gldm_a=0, force2D=False,
+                             force2Ddimension=0, weightingNorm=None, spacing=(1.0, 1.0, 1.0), symmetricalGLCM=True):
     """GLCM / GLRLM / GLDM / NGTDM of B small 3-D ROIs (lists of host arrays: int levels, bool masks) with one upload, one
     native call and one download per family.  -> ({family: [B numpy matrices in the single calls' layouts]}, status [B]:
     1, or 0 for a ROI with a masked level outside [1, Ng] -- the single calls' IndexError; its matrices are void).
+    force2D / force2Ddimension / weightingNorm / spacing / symmetricalGLCM: as engine.texture_matrices_batch (weightingNorm
+    adds the merged "glcm_w" [Ng, Ng, 1] / "glrlm_w" [Ng, max(size), 1]).
     Where the native call does not cover the batch (Ng > 64, a box above prad_batch_max_vox() voxels, > 127 angles) or no
     device is visible, the single calls are looped ROI by ROI (and raise as they do without a device); last_batch_route()
     tells which.  GLSZM: calculate_glszm_batch."""
@@ -480,17 +597,26 @@ def calculate_matrices_batch(images, masks, Ng, families=BATCH_FAMILIES, distanc
     batch_family_bits(families)
     imgs, msks, sizes, upload = _host_roi_batch(images, masks, "matrices", loops=True)
     dist = [int(d) for d in np.asarray(distances).ravel()]
-    covered, offsets, Na = batch_plan(sizes, Ng, families, dist)
+    f2, fd = bool(force2D), int(force2Ddimension)
+    covered, offsets, Na = batch_plan(sizes, Ng, families, dist, f2, fd)
     shapes = batch_shapes(sizes, int(Ng), Na)
     B = len(imgs)
+    batch_weighting_norm(weightingNorm)
+    if weightingNorm is not None and upload is not None:      # the merge is a device launch: the device route serves it
+        mats, status = _engine().texture_matrices_batch(*upload(), sizes, int(Ng), families, dist, int(gldm_a), f2, fd,
+                                                        weightingNorm, spacing, symmetricalGLCM)
+        return {f: [m.cpu().numpy() for m in mats[f]] for f in mats}, status
     if not covered or upload is None:
-        single = {"glcm": lambda i, m: calculate_glcm(i, m, dist, int(Ng), False, 0)[0][0],
-                  "glrlm": lambda i, m: calculate_glrlm(i, m, int(Ng), int(max(i.shape)), False, 0)[0][0],
-                  "gldm": lambda i, m: calculate_gldm(i, m, dist, int(Ng), int(gldm_a), False, 0)[0],
-                  "ngtdm": lambda i, m: calculate_ngtdm(i, m, dist, int(Ng), False, 0)[0]}
-        return _looped_matrices(zip(imgs, msks), int(Ng), families, shapes, single)
+        single = {"glcm": lambda i, m: calculate_glcm(i, m, dist, int(Ng), f2, fd)[0][0],
+                  "glrlm": lambda i, m: calculate_glrlm(i, m, int(Ng), int(max(i.shape)), f2, fd)[0][0],
+                  "gldm": lambda i, m: calculate_gldm(i, m, dist, int(Ng), int(gldm_a), f2, fd)[0],
+                  "ngtdm": lambda i, m: calculate_ngtdm(i, m, dist, int(Ng), f2, fd)[0]}
+        mats, status = _looped_matrices(zip(imgs, msks), int(Ng), families, shapes, single)
+        if weightingNorm is not None:
+            merge_looped(mats, sizes, Na, dist, weightingNorm, spacing, f2, fd, symmetricalGLCM)
+        return mats, status
     flat_l, flat_m = upload()
-    flat, status = _engine().texture_matrices_batch_flat(flat_l, flat_m, sizes, int(Ng), families, dist, int(gldm_a))
+    flat, status = _engine().texture_matrices_batch_flat(flat_l, flat_m, sizes, int(Ng), families, dist, int(gldm_a), f2, fd)
     mats = {}
     for f in families:
         host = flat[f].cpu().numpy()
@@ -499,24 +625,29 @@ def calculate_matrices_batch(images, masks, Ng, families=BATCH_FAMILIES, distanc
     return mats, status
 
 
-def calculate_glszm_batch(images, masks, Ng, compact=False):
+def calculate_glszm_batch(images, masks, Ng, compact=False, force2D=False, force2Ddimension=0, weightingNorm=None,
+                          spacing=(1.0, 1.0, 1.0)):
     """GLSZM of B small 3-D ROIs (lists of host arrays: int levels, bool masks) with one upload and the two launches of
     engine.glszm_batch.  -> (list of B results, status [B]: 1, or 0 for a ROI with a masked level outside [1, Ng] -- the
     single call's IndexError; its result is that of an empty mask).  compact=False: a result is the float64 matrix [Ng,
     max(maxRegion, 1)] of calculate_glszm (without its leading axis); compact=True: (P [Ng, k], sizes int32 [k]) as
     calculate_glszm_compact.  With no device visible the single calls are looped ROI by ROI (and raise as they do without a
-    device); last_batch_route() tells which route ran."""
+    device); last_batch_route() tells which route ran.  force2D / force2Ddimension: zones join only in the plane across that
+    axis; weightingNorm / spacing are accepted and ignored, as the class ignores them."""
     imgs, msks, sizes, upload = _host_roi_batch(images, masks, "GLSZM", loops=True)
     Ng = int(Ng)
+    f2, fd = bool(force2D), int(force2Ddimension)
+    f2d = batch_forced_dim(f2, fd)
+    batch_weighting_norm(weightingNorm)
     if upload is None:
         def single(img, msk, Ns):
-            P = calculate_glszm(img, msk, Ng, Ns, False, 0)[0]
+            P = calculate_glszm(img, msk, Ng, Ns, f2, fd)[0]
             cols = np.flatnonzero(P.any(0))
             return (np.ascontiguousarray(P[:, cols]), (cols + 1).astype(np.intc)) if compact else P
         _set_batch_route("looped")
-        return _looped_glszm(zip(imgs, msks), Ng, compact, single)
+        return _looped_glszm(zip(imgs, msks), Ng, compact, single, f2d=f2d)
     flat_l, flat_m = upload()
-    results, status = _engine().glszm_batch(flat_l, flat_m, sizes, Ng, compact=compact)
+    results, status = _engine().glszm_batch(flat_l, flat_m, sizes, Ng, compact=compact, force2D=f2, force2Ddimension=fd)
     if compact:
         return [(P.cpu().numpy(), s) for P, s in results], status
     return [P.cpu().numpy() for P in results], status
@@ -528,15 +659,18 @@ def batch_feature_names(cls):
 
 
 def calculate_features_batch(images, masks, Ng, classes=("glcm", "glrlm", "glszm", "gldm", "ngtdm"), distances=(1,), gldm_a=0,
-                             symmetricalGLCM=True, mcc=True):
+                             symmetricalGLCM=True, mcc=True, force2D=False, force2Ddimension=0, weightingNorm=None,
+                             spacing=(1.0, 1.0, 1.0)):
     """The texture features of B small 3-D ROIs (lists of host arrays: int levels, bool masks): one upload, the batched matrix
     calls and the batched formulas of engine.texture_features_batch.  -> {class: {feature name: float64 [B]}}; a ROI with a masked level
     outside [1, Ng] (the single calls' IndexError) has NaN everywhere, the others are not affected.  The names are those of the feature classes
-    (VOXEL_*_FEATURES, plus "MCC").  Needs a device (RuntimeError without one); last_batch_route() tells which route ran."""
+    (VOXEL_*_FEATURES, plus "MCC").  Needs a device (RuntimeError without one); last_batch_route() tells which route ran.
+    force2D / force2Ddimension / weightingNorm / spacing: as engine.texture_features_batch."""
     _, _, sizes, upload = _host_roi_batch(images, masks, "features")
     table, _ = _engine().texture_features_batch(*upload(), sizes, int(Ng), tuple(classes),
                                                 [int(d) for d in np.asarray(distances).ravel()], int(gldm_a),
-                                                bool(symmetricalGLCM), bool(mcc))
+                                                bool(symmetricalGLCM), bool(mcc), False, bool(force2D), int(force2Ddimension),
+                                                weightingNorm, spacing)
     return {cls: {name: table[cls][:, i].copy() for i, name in enumerate(batch_feature_names(cls)) if name}
             for cls in table}
 
@@ -566,15 +700,17 @@ def calculate_firstorder_batch(images, masks, voxelArrayShift=0.0, voxelVolume=1
 
 def calculate_roi_features_batch(images, masks, classes=("firstorder", "glcm", "glrlm", "glszm", "gldm", "ngtdm"), binWidth=None,
                                  binCount=None, voxelArrayShift=0.0, voxelVolume=1.0, distances=(1,), gldm_a=0,
-                                 symmetricalGLCM=True, mcc=True):
+                                 symmetricalGLCM=True, mcc=True, force2D=False, force2Ddimension=0, weightingNorm=None,
+                                 spacing=(1.0, 1.0, 1.0)):
     """The features of all six classes of B small 3-D ROIs from raw intensity boxes and masks (lists of host arrays): one upload,
     then engine.roi_features_batch.  -> {class: {feature name: float64 [B]}} (FIRSTORDER_FEATURES / batch_feature_names); an
     empty ROI has NaN everywhere, the others are not affected.  Needs a device (RuntimeError without one); last_batch_route()
-    tells which route ran."""
+    tells which route ran.  force2D / force2Ddimension / weightingNorm / spacing: as engine.roi_features_batch."""
     _, _, sizes, upload = _host_roi_batch(images, masks, "ROI features", raw=True)
     table, _ = _engine().roi_features_batch(*upload(), sizes, tuple(classes), binWidth, binCount, float(voxelArrayShift),
                                             voxelVolume, [int(d) for d in np.asarray(distances).ravel()], int(gldm_a),
-                                            bool(symmetricalGLCM), bool(mcc))
+                                            bool(symmetricalGLCM), bool(mcc), False, bool(force2D), int(force2Ddimension),
+                                            weightingNorm, spacing)
     names = {cls: (FIRSTORDER_FEATURES if cls == "firstorder" else batch_feature_names(cls)) for cls in table}
     return {cls: {name: table[cls][:, i].copy() for i, name in enumerate(names[cls]) if name} for cls in table}
 

@@ -12,7 +12,10 @@
 //   cap takes a CU alone; a batch of 16^3 boxes asks for 12.3 KiB and runs 8 workgroups per CU (the 32-wave limit).
 //
 // Labelling.  label[v] starts as v.  A sweep replaces label[v] by the minimum of label[v], label[label[v]] (pointer jump)
-// and the labels of the up to 26 neighbours of v's level inside the box; sweeps repeat until one changes nothing.
+// and the labels of the neighbours of v's level inside the box; sweeps repeat until one changes nothing.  The neighbourhood
+// is a compile-time variant of the kernel (template argument F2D, the forced dimension of force2D): -1 the up to 26
+// neighbours, 0 / 1 / 2 the up to 8 neighbours in the plane of the two other axes (z, y, x) -- the angle sets the single call
+// is given.  The argument below holds for any symmetric neighbourhood, so for all four.
 //   * There are no 16-bit LDS atomics and none are needed: a voxel's slot is written by its own thread only (ds_write_b16),
 //     the other threads only read it, and a 16-bit LDS access is single-copy atomic -- a reader sees the old or the new label.
 //   * Invariant: label[v] is the index of a voxel of v's zone and label[v] <= v (true at the start; every candidate of the
@@ -27,6 +30,13 @@
 //     sweep, in either direction.  The pointer jump doubles the reach along any path whose indices grow away from the zone's
 //     first voxel.  What remains slow is a one-voxel-wide path that runs against the raster order along y or z: one voxel
 //     per sweep.  A serpentine through all 54528 voxels of a 1 x 213 x 256 box is the test of that.
+//     Forced x (F2D = 2): the neighbours lie in the (z, y) plane, so two consecutive voxels of a range are no neighbours
+//     (unless nx = 1) and the Gauss-Seidel reach along x joins nothing; a label crosses a range only between the rows of the
+//     range that lie above one another (ranges longer than nx).  A straight line along y or z is left to the pointer jump: its
+//     indices grow away from the zone's first voxel, O(log length) sweeps.  The slow path is now EVERY one-voxel-wide path
+//     that runs against the raster order, whichever its direction in the plane -- e.g. the rising arm of a U: one voxel per
+//     sweep, at most the nz * ny voxels of one x-plane.  Forced z and forced y keep the reach along x and the slow path of
+//     the unforced kernel, confined to one plane.
 //   * LDS traffic.  Labels are read as ds_read_u16 and levels as ds_read_u8 through address_space(3) pointers (through a
 //     generic volatile pointer the compiler emits flat loads: kernels_glszm.h:175-177).  Banks are 4 bytes wide, 32 of them
 //     for these instructions: with a range of `chunk` voxels per thread, lane l reads label bytes 2 * chunk * l + const, so
@@ -108,7 +118,9 @@ __device__ __forceinline__ int bz_block_scan(int v, volatile bz_lds_u32 *waves, 
   return base + inc - v;
 }
 
+template <int F2D>
 __global__ void __launch_bounds__(PRAD_BZ_THREADS) batch_glszm_kernel(BatchZoneArgs A) {
+  static_assert(F2D >= -1 && F2D <= 2, "forced dimension: none, z, y or x");
   extern __shared__ __align__(16) unsigned char bz_lds[];
   volatile bz_lds_u32 *misc = (volatile bz_lds_u32 *)bz_lds;
   bz_lds_u8 *L = (bz_lds_u8 *)(bz_lds + PRAD_BZ_MISC_BYTES);
@@ -169,14 +181,14 @@ __global__ void __launch_bounds__(PRAD_BZ_THREADS) batch_glszm_kernel(BatchZoneA
           unsigned m = min(cur, (unsigned)lab[cur]);
 #pragma unroll
           for (int dz = -1; dz <= 1; dz++) {
-            if ((unsigned)(z + dz) >= (unsigned)nz) continue;
+            if ((F2D == 0 && dz) || (unsigned)(z + dz) >= (unsigned)nz) continue;
 #pragma unroll
             for (int dy = -1; dy <= 1; dy++) {
-              if ((unsigned)(y + dy) >= (unsigned)ny) continue;
+              if ((F2D == 1 && dy) || (unsigned)(y + dy) >= (unsigned)ny) continue;
               const int row = v + dz * plane + dy * nx;
 #pragma unroll
               for (int dx = -1; dx <= 1; dx++) {
-                if (!(dz | dy | dx) || (unsigned)(x + dx) >= (unsigned)nx) continue;
+                if ((F2D == 2 && dx) || !(dz | dy | dx) || (unsigned)(x + dx) >= (unsigned)nx) continue;
                 if (L[row + dx] == c) m = min(m, (unsigned)lab[row + dx]);
               }
             }

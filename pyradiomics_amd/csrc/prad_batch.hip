@@ -1,5 +1,7 @@
-// prad_batch.hip -- C ABI of the batched small-ROI texture matrices (include/pyradiomics_amd.h: prad_batch_plan,
-// prad_calculate_batch_dev); translation unit of libpyradiomics_amd.so.
+// prad_batch.hip -- C ABI of the batched small-ROI texture matrices (include/pyradiomics_amd.h: prad_batch_plan[_f2d],
+// prad_calculate_batch[_f2d]_dev); translation unit of libpyradiomics_amd.so.  The kernel consumes an arbitrary angle table per
+// ROI, so the forced dimension (force2D) lives here alone: the counts and tables come from prad_get_angle_count /
+// prad_build_angles with it, the very functions the single calls use.
 #include "kernels_batch.h"
 #include "prad_batch_common.h"
 
@@ -18,16 +20,18 @@ struct BatchLayout {
   char why[160] = {0};
 };
 
-// Shapes of the per-ROI outputs, the same arithmetic the single calls use: Na = prad_get_angle_count (unidirectional),
+// Shapes of the per-ROI outputs, the same arithmetic the single calls use: Na = prad_get_angle_count (unidirectional, forced
+// dimension f2d: -1 none, 0 / 1 / 2 the axis no angle may leave),
 // GLCM [Ng][Ng][Na], GLRLM [Ng][max(size)][Na1] (distance 1), GLDM [Ng][2 Nb + 1] with Nb = 2 Na, NGTDM [Ng][3].
 // Host only: no device is touched.
-int batch_layout(const int *sizes, int B, int Ng, int families, const int *distances, int Ndist, BatchLayout *lay) {
+int batch_layout(const int *sizes, int B, int Ng, int families, const int *distances, int Ndist, int f2d, BatchLayout *lay) {
   PRAD_TRY(roi_count_check("batch", sizes, B, 0));
   if (Ng < 1) return fail(PRAD_E_ARG, "batch: Ng=%d < 1", Ng);
   if (!distances || Ndist < 1) return fail(PRAD_E_ARG, "batch: no distances");
   if (families < 1 || families > PRAD_BATCH_ALL) return fail(PRAD_E_ARG, "batch: families=%d outside [1, %d]", families, PRAD_BATCH_ALL);
   for (int k = 0; k < Ndist; k++)
     if (distances[k] < 1) return fail(PRAD_E_ARG, "batch: distance %d < 1", distances[k]);
+  if (f2d < -1 || f2d > 2) return fail(PRAD_E_ARG, "batch: forced dimension %d outside [-1, 2]", f2d);
   PRAD_TRY(roi_sizes_check("batch", sizes, B, nullptr));
   lay->offsets.assign((size_t)4 * (B + 1), 0);
   lay->na.assign((size_t)2 * B, 0);
@@ -39,8 +43,8 @@ int batch_layout(const int *sizes, int B, int Ng, int families, const int *dista
   for (int b = 0; b < B; b++) {
     const int *sz = sizes + 3 * b;
     const long long nvox = roi_nvox(sizes, b);
-    const int na = prad_get_angle_count(sz, distances, 3, Ndist, 0, -1);
-    const int na1 = prad_get_angle_count(sz, &kOne, 3, 1, 0, -1);
+    const int na = prad_get_angle_count(sz, distances, 3, Ndist, 0, f2d);
+    const int na1 = prad_get_angle_count(sz, &kOne, 3, 1, 0, f2d);
     lay->na[b] = na;
     lay->na[(size_t)B + b] = na1;
     if (lay->in_domain && nvox > PRAD_BATCH_MAX_VOX) {
@@ -65,9 +69,14 @@ extern "C" int prad_batch_max_vox(void) { return PRAD_BATCH_MAX_VOX; }
 
 extern "C" int prad_batch_plan(const int *sizes, int B, int Ng, int families, const int *distances, int Ndist,
                                long long *out_offsets, int *Na) {
+  return prad_batch_plan_f2d(sizes, B, Ng, families, distances, Ndist, -1, out_offsets, Na);
+}
+
+extern "C" int prad_batch_plan_f2d(const int *sizes, int B, int Ng, int families, const int *distances, int Ndist,
+                                   int force2Ddim, long long *out_offsets, int *Na) {
   if (!out_offsets || !Na) return fail(PRAD_E_ARG, "batch plan: NULL output");
   BatchLayout lay;
-  PRAD_TRY(batch_layout(sizes, B, Ng, families, distances, Ndist, &lay));
+  PRAD_TRY(batch_layout(sizes, B, Ng, families, distances, Ndist, force2Ddim, &lay));
   std::copy(lay.offsets.begin(), lay.offsets.end(), out_offsets);
   std::copy(lay.na.begin(), lay.na.end(), Na);
   if (!lay.in_domain) return fail(PRAD_E_UNSUPPORTED, "batch: %s (use the single calls per ROI)", lay.why);
@@ -78,8 +87,16 @@ extern "C" int prad_calculate_batch_dev(const int32_t *levels, const uint8_t *ma
                                         int B, int Ng, int families, const int *distances, int Ndist, int alpha,
                                         double *glcm, double *glrlm, double *gldm, double *ngtdm, int *status,
                                         void *stream) {
+  return prad_calculate_batch_f2d_dev(levels, mask, sizes, off, B, Ng, families, distances, Ndist, alpha, -1, glcm, glrlm, gldm,
+                                      ngtdm, status, stream);
+}
+
+extern "C" int prad_calculate_batch_f2d_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off,
+                                            int B, int Ng, int families, const int *distances, int Ndist, int alpha,
+                                            int force2Ddim, double *glcm, double *glrlm, double *gldm, double *ngtdm,
+                                            int *status, void *stream) {
   BatchLayout lay;
-  PRAD_TRY(batch_layout(sizes, B, Ng, families, distances, Ndist, &lay));
+  PRAD_TRY(batch_layout(sizes, B, Ng, families, distances, Ndist, force2Ddim, &lay));
   if (!lay.in_domain) return fail(PRAD_E_UNSUPPORTED, "batch: %s (use the single calls per ROI)", lay.why);   // nothing launched
   if (B == 0) return PRAD_OK;
   double *outs[4] = {glcm, glrlm, gldm, ngtdm};
@@ -115,13 +132,13 @@ extern "C" int prad_calculate_batch_dev(const int32_t *levels, const uint8_t *ma
     r.na_run = lay.na[(size_t)B + b];
     r.pad = 0;
     r.ang = (int)row;
-    if (r.na > 0 && prad_build_angles(sz, distances, 3, Ndist, -1, r.na, angles + 3 * row) != 0)
+    if (r.na > 0 && prad_build_angles(sz, distances, 3, Ndist, force2Ddim, r.na, angles + 3 * row) != 0)
       return fail(PRAD_E_ARG, "batch: angles of ROI %d", b);
     row += (size_t)r.na;
     r.ang_run = r.ang;
     if (runs && !same) {
       r.ang_run = (int)row;
-      if (r.na_run > 0 && prad_build_angles(sz, &kOne, 3, 1, -1, r.na_run, angles + 3 * row) != 0)
+      if (r.na_run > 0 && prad_build_angles(sz, &kOne, 3, 1, force2Ddim, r.na_run, angles + 3 * row) != 0)
         return fail(PRAD_E_ARG, "batch: distance-1 angles of ROI %d", b);
       row += (size_t)r.na_run;
     }
@@ -165,7 +182,7 @@ extern "C" int prad_calculate_batch_dev(const int32_t *levels, const uint8_t *ma
   const long long jobs = A.groups_glcm + A.groups_glrlm + A.neigh;
   if ((long long)B * jobs > 0x7fffffffLL) return fail(PRAD_E_UNSUPPORTED, "batch: %d ROIs x %lld jobs", B, jobs);
 
-  return batch_call(c, s, table, "batch-lds", [&]() {
+  return batch_call(c, s, table, force2Ddim < 0 ? "batch-lds" : "batch-lds-f2d", [&]() {
     PRAD_TRY(allow_dynamic_lds(&batch_rois_kernel, lds));
     Timed t(c, "batch", s);
     hipLaunchKernelGGL(batch_rois_kernel, dim3((unsigned)(B * jobs)), dim3(PRAD_BATCH_THREADS), lds, s, A);

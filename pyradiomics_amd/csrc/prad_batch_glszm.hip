@@ -1,5 +1,5 @@
 // prad_batch_glszm.hip -- C ABI of the batched small-ROI GLSZM (include/pyradiomics_amd.h: prad_batch_glszm_max_vox,
-// prad_batch_glszm_dev, prad_batch_glszm_fill_dev); translation unit of libpyradiomics_amd.so.
+// prad_batch_glszm[_f2d]_dev, prad_batch_glszm_fill_dev); translation unit of libpyradiomics_amd.so.
 #include "kernels_batch_glszm.h"
 #include "prad_batch_common.h"
 
@@ -9,10 +9,28 @@ using namespace prad;
 
 extern "C" int prad_batch_glszm_max_vox(void) { return PRAD_BATCH_GLSZM_MAX_VOX; }
 
+namespace {
+
+template <int F2D>
+int launch_zones(Context &c, hipStream_t s, int B, size_t lds, const BatchZoneArgs &A) {
+  PRAD_TRY(allow_dynamic_lds(&batch_glszm_kernel<F2D>, lds));
+  Timed t(c, "batch_glszm", s);
+  hipLaunchKernelGGL(batch_glszm_kernel<F2D>, dim3((unsigned)B), dim3(PRAD_BZ_THREADS), lds, s, A);
+  return check_launch("batch_glszm_kernel");
+}
+
+}  // namespace
+
 extern "C" int prad_batch_glszm_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B,
                                     int Ng, int *zones, int *summary, int *status, void *stream) {
+  return prad_batch_glszm_f2d_dev(levels, mask, sizes, off, B, Ng, -1, zones, summary, status, stream);
+}
+
+extern "C" int prad_batch_glszm_f2d_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B,
+                                        int Ng, int force2Ddim, int *zones, int *summary, int *status, void *stream) {
   PRAD_TRY(roi_count_check("batch GLSZM", sizes, B, 0));
   if (Ng < 1) return fail(PRAD_E_ARG, "batch GLSZM: Ng=%d < 1", Ng);
+  if (force2Ddim < -1 || force2Ddim > 2) return fail(PRAD_E_ARG, "batch GLSZM: forced dimension %d outside [-1, 2]", force2Ddim);
   long long max_vox = 1;
   PRAD_TRY(roi_sizes_check("batch GLSZM", sizes, B, &max_vox));
   if (B > 0 && (!levels || !mask || !off || !zones || !summary || !status)) return fail(PRAD_E_ARG, "batch GLSZM: NULL pointer");
@@ -48,11 +66,14 @@ extern "C" int prad_batch_glszm_dev(const int32_t *levels, const uint8_t *mask, 
   const size_t lds = PRAD_BZ_MISC_BYTES + 3 * (size_t)A.vox_bytes;
   if (lds > 160 * 1024) return fail(PRAD_E_HIP, "batch GLSZM: %zu bytes of LDS per workgroup", lds);
 
-  return batch_call(c, s, table, "batch-glszm-lds", [&]() {
-    PRAD_TRY(allow_dynamic_lds(&batch_glszm_kernel, lds));
-    Timed t(c, "batch_glszm", s);
-    hipLaunchKernelGGL(batch_glszm_kernel, dim3((unsigned)B), dim3(PRAD_BZ_THREADS), lds, s, A);
-    return check_launch("batch_glszm_kernel");
+  static const char *const kVariant[4] = {"batch-glszm-lds", "batch-glszm-lds-f2d0", "batch-glszm-lds-f2d1", "batch-glszm-lds-f2d2"};
+  return batch_call(c, s, table, kVariant[force2Ddim + 1], [&]() {
+    switch (force2Ddim) {
+      case 0: return launch_zones<0>(c, s, B, lds, A);
+      case 1: return launch_zones<1>(c, s, B, lds, A);
+      case 2: return launch_zones<2>(c, s, B, lds, A);
+      default: return launch_zones<-1>(c, s, B, lds, A);
+    }
   });
 }
 

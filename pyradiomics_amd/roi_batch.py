@@ -134,57 +134,127 @@ def batch_max_vox() -> int:
     return int(_lib.load().prad_batch_max_vox())
 
 
-def _matrices_flat(rois, Ng, families, dist, gldm_a, plan=None):
-    covered, offsets, _ = plan if plan is not None else _cm.batch_plan(rois.sizes, Ng, families, dist)
+class Planar(NamedTuple):
+    """the settings the batched route shares with the single calls and the feature classes beyond its own arguments"""
+    force2D: bool = False
+    force2Ddimension: int = 0
+    weightingNorm: Optional[str] = None
+    spacing: object = (1.0, 1.0, 1.0)          # (z, y, x): one triple, or float [B, 3]; used only for the weights
+    symmetric: bool = True                     # symmetricalGLCM, for the merge
+
+    @property
+    def f2d(self):
+        return _cm.batch_forced_dim(self.force2D, self.force2Ddimension)
+
+    @property
+    def axes(self):
+        """(force2D, force2Ddimension) as the single calls take them"""
+        return bool(self.force2D), int(self.force2Ddimension)
+
+    def subset(self, idx, B):
+        return self._replace(spacing=_cm.batch_spacing(self.spacing, B)[idx])
+
+
+def _planar(force2D, force2Ddimension, weightingNorm, spacing, symmetric=True):
+    p = Planar(bool(force2D), int(force2Ddimension), _cm.batch_weighting_norm(weightingNorm), spacing, bool(symmetric))
+    p.f2d          # (raises on a dimension outside 0 .. 2)
+    return p
+
+
+def _merge_flat(rois, Ng, families, dist, flat, status, plan, pl):
+    """the weighted angle merge of the flat per-angle buffers (prad_batch_merge_angles_dev) -> ({"glcm_w" / "glrlm_w": flat
+    float64 device buffer}, merge offsets int64 [3, B + 1])"""
+    fams = tuple(f for f in _cm.MERGE_FAMILIES if f in families)
+    _, offsets, Na = plan
+    moff = _cm.batch_merge_plan(rois.sizes, Ng, Na, fams)
+    w = _cm.batch_weights(rois.sizes, Na, dist, pl.weightingNorm, pl.spacing, *pl.axes)
+    out = {f: torch.empty(int(moff[_cm.MERGE_FAMILIES.index(f), rois.B]), dtype=torch.float64, device=rois.device) for f in fams}
+    rc = rois.lib.prad_batch_merge_angles_dev(_iptr(rois.sizes), rois.B, int(Ng), sum(1 << _cm.MERGE_FAMILIES.index(f) for f in fams),
+                                              _iptr(Na), _vp(flat.get("glcm")), _vp(flat.get("glrlm")), _lp(offsets),
+                                              w.ctypes.data_as(C.POINTER(C.c_double)), _vp(status), 1 if pl.symmetric else 0,
+                                              _vp(out.get("glcm")), _vp(out.get("glrlm")), _eng._stream_ptr())
+    _lib.raise_for(rc, "batched angle merge")
+    return {f + "_w": out[f] for f in fams}, moff
+
+
+def _matrices_flat(rois, Ng, families, dist, gldm_a, plan=None, pl=Planar()):
+    plan = plan if plan is not None else _cm.batch_plan(rois.sizes, Ng, families, dist, *pl.axes)
+    covered, offsets, _ = plan
     if not covered:
         return None
     B, dist = rois.B, np.ascontiguousarray(np.asarray(dist, dtype=np.intc).ravel())
     flat = {f: torch.empty(int(offsets[_cm.BATCH_FAMILIES.index(f), B]), dtype=torch.float64, device=rois.device) for f in families}
     status = torch.empty(B, dtype=torch.int32, device=rois.device)
     ptr = [_vp(flat.get(f)) for f in _cm.BATCH_FAMILIES]
-    rc = rois.lib.prad_calculate_batch_dev(_vp(rois.data), _vp(rois.mask), _iptr(rois.sizes), _lp(rois.off), B, int(Ng),
-                                           _cm.batch_family_bits(families), _iptr(dist), int(dist.shape[0]), int(gldm_a),
-                                           ptr[0], ptr[1], ptr[2], ptr[3], _vp(status), _eng._stream_ptr())
+    rc = rois.lib.prad_calculate_batch_f2d_dev(_vp(rois.data), _vp(rois.mask), _iptr(rois.sizes), _lp(rois.off), B, int(Ng),
+                                               _cm.batch_family_bits(families), _iptr(dist), int(dist.shape[0]), int(gldm_a),
+                                               pl.f2d, ptr[0], ptr[1], ptr[2], ptr[3], _vp(status), _eng._stream_ptr())
     if rc == _lib.PRAD_E_UNSUPPORTED:
         return None
     _lib.raise_for(rc, "batched texture matrices")
+    if pl.weightingNorm is not None and any(f in families for f in _cm.MERGE_FAMILIES):
+        flat.update(_merge_flat(rois, Ng, families, dist, flat, status, plan, pl)[0])
     _cm._set_batch_route("batch")
     return flat, status.tolist()
 
 
-def texture_matrices_batch_flat(levels, masks, sizes, Ng, families=_cm.BATCH_FAMILIES, distances=(1,), gldm_a=0):
-    """the native call alone: -> ({family: flat float64 device buffer}, status list), or None when it declines the batch"""
-    return _matrices_flat(_roi_batch(levels, masks, sizes), Ng, tuple(families), list(distances), gldm_a)
+def texture_matrices_batch_flat(levels, masks, sizes, Ng, families=_cm.BATCH_FAMILIES, distances=(1,), gldm_a=0, force2D=False,
+                                force2Ddimension=0, weightingNorm=None, spacing=(1.0, 1.0, 1.0), symmetricalGLCM=True):
+    """the native calls alone: -> ({family: flat float64 device buffer}, status list), or None when they decline the batch.
+    force2D / force2Ddimension / weightingNorm / spacing / symmetricalGLCM as texture_matrices_batch: with weightingNorm the
+    dict also holds the flat merged buffers "glcm_w" / "glrlm_w" (cmatrices.batch_merge_plan lays them out)."""
+    return _matrices_flat(_roi_batch(levels, masks, sizes), Ng, tuple(families), list(distances), gldm_a,
+                          pl=_planar(force2D, force2Ddimension, weightingNorm, spacing, symmetricalGLCM))
 
 
-def _matrices(rois, Ng, families, distances, gldm_a):
+def _matrices(rois, Ng, families, distances, gldm_a, pl=Planar()):
     dist = [int(d) for d in distances]
-    plan = _cm.batch_plan(rois.sizes, Ng, families, dist)
+    plan = _cm.batch_plan(rois.sizes, Ng, families, dist, *pl.axes)
     shapes = _cm.batch_shapes(rois.sizes, int(Ng), plan[2])
-    res = _matrices_flat(rois, Ng, families, dist, gldm_a, plan)
+    merged = [f for f in _cm.MERGE_FAMILIES if f in families] if pl.weightingNorm is not None else []
+    res = _matrices_flat(rois, Ng, families, dist, gldm_a, plan, pl)
     if res is not None:
         flat, status = res
         mats = {}
         for f in families:
             o = plan[1][_cm.BATCH_FAMILIES.index(f)]
             mats[f] = [flat[f][int(o[b]):int(o[b + 1])].view(shapes[f][b]) for b in range(rois.B)]
+        if merged:
+            moff = _cm.batch_merge_plan(rois.sizes, Ng, plan[2], merged)
+            for f in merged:
+                o = moff[_cm.MERGE_FAMILIES.index(f)]
+                mats[f + "_w"] = [flat[f + "_w"][int(o[b]):int(o[b + 1])].view(shapes[f][b][:2] + (1,)) for b in range(rois.B)]
         return mats, status
-    single = {"glcm": lambda i, m: _eng.glcm(i, m, int(Ng), dist)[0],
-              "glrlm": lambda i, m: _eng.glcm_glrlm(i, m, int(Ng), max(i.shape), want_glcm=False)[1],
-              "gldm": lambda i, m: _eng.gldm(i, m, int(Ng), int(gldm_a), dist),
-              "ngtdm": lambda i, m: _eng.ngtdm(i, m, int(Ng), dist)}
-    return _cm._looped_matrices(rois.boxes(range(rois.B)), int(Ng), families, shapes, single, rois.to_device)
+    f2 = pl.axes
+    single = {"glcm": lambda i, m: _eng.glcm(i, m, int(Ng), dist, *f2)[0],
+              "glrlm": lambda i, m: _eng.glcm_glrlm(i, m, int(Ng), max(i.shape), *f2, want_glcm=False)[1],
+              "gldm": lambda i, m: _eng.gldm(i, m, int(Ng), int(gldm_a), dist, *f2),
+              "ngtdm": lambda i, m: _eng.ngtdm(i, m, int(Ng), dist, *f2)}
+    mats, status = _cm._looped_matrices(rois.boxes(range(rois.B)), int(Ng), families, shapes, single, rois.to_device)
+    if merged:
+        _cm.merge_looped(mats, rois.sizes, plan[2], dist, pl.weightingNorm, pl.spacing, *f2, pl.symmetric, rois.to_device)
+    return mats, status
 
 
-def texture_matrices_batch(levels, masks, sizes, Ng, families=_cm.BATCH_FAMILIES, distances=(1,), gldm_a=0):
-    """GLCM / GLRLM / GLDM / NGTDM of B small ROIs in ONE launch (segment mode, 3-D).  levels / masks: lists of 3-D device
+def texture_matrices_batch(levels, masks, sizes, Ng, families=_cm.BATCH_FAMILIES, distances=(1,), gldm_a=0, force2D=False,
+                           force2Ddimension=0, weightingNorm=None, spacing=(1.0, 1.0, 1.0), symmetricalGLCM=True):
+    """GLCM / GLRLM / GLDM / NGTDM of B small ROIs in ONE launch (segment mode).  levels / masks: lists of 3-D device
     tensors (concatenated here; `sizes` is then ignored), or flat device tensors holding the ROIs back to back plus `sizes`
     (int [B, 3]).  -> ({family: [B float64 device tensors, views into one flat buffer, in the single calls' layouts:
     glcm [Ng, Ng, Na], glrlm [Ng, max(size), Na1], gldm [Ng, 2 * Nb + 1] with Nb = 2 * Na, ngtdm [Ng, 3]]}, status [B]: 1,
     or 0 for a ROI with a masked level outside [1, Ng] -- the single calls' IndexError; its matrices are void).
     Covered: Ng <= 64, boxes of at most batch_max_vox() voxels, at most 127 angles; otherwise the single calls are looped ROI
-    by ROI (same results, separate tensors) and last_batch_route() says "looped".  GLSZM: glszm_batch."""
-    return _matrices(_roi_batch(levels, masks, sizes), Ng, tuple(families), distances, gldm_a)
+    by ROI (same results, separate tensors) and last_batch_route() says "looped".  GLSZM: glszm_batch.
+    force2D / force2Ddimension: the angle sets of the single calls with the same arguments -- no angle leaves the plane across
+    axis force2Ddimension (0 z, 1 y, 2 x).  A ROI that keeps no angle (5 x 1 x 1 with dimension 0, 1 x 1 x 1 always) is legal:
+    empty GLCM / GLRLM, GLDM and NGTDM of voxels without neighbours.
+    weightingNorm ("euclidean", "manhattan", "infinity", "no_weighting"; anything else: ValueError) adds, in one more launch, the
+    entries "glcm_w" [Ng, Ng, 1] and "glrlm_w" [Ng, max(size), 1]: the per-angle matrices -- GLCM plus its transpose when
+    symmetricalGLCM -- summed over the angles with the weights glcm._weights gives the feature classes for the ROI's angles and
+    `spacing` ((z, y, x): one triple or float [B, 3]; used for nothing else).  The sum adds rounded products over the angles
+    ascending (csrc/kernels_batch_merge.h), on every route; a ROI without angles or with status 0 gets zeros."""
+    return _matrices(_roi_batch(levels, masks, sizes), Ng, tuple(families), distances, gldm_a,
+                     _planar(force2D, force2Ddimension, weightingNorm, spacing, symmetricalGLCM))
 
 
 # ---- GLSZM (prad_batch_glszm_dev / prad_batch_glszm_fill_dev, csrc/kernels_batch_glszm.h) ------------------------------------
@@ -193,14 +263,14 @@ def batch_glszm_max_vox() -> int:
     return int(_lib.load().prad_batch_glszm_max_vox())
 
 
-def _glszm_label(rois, sizes, off, Ng):
+def _glszm_label(rois, sizes, off, Ng, f2d=-1):
     """the labelling launch on the ROIs (sizes[b], off[b]) of the batch's buffers -> (zones int32 device buffer indexed by
     2 * off[b], summary int32 numpy [B, 3], status int32 numpy [B]); summary and status come back in ONE copy"""
     B = int(sizes.shape[0])
     zones = torch.empty(2 * rois.data.numel(), dtype=torch.int32, device=rois.device)
     meta = torch.empty(4 * B, dtype=torch.int32, device=rois.device)
-    rc = rois.lib.prad_batch_glszm_dev(_vp(rois.data), _vp(rois.mask), _iptr(sizes), _lp(off), B, int(Ng), _vp(zones), _vp(meta),
-                                       C.c_void_p(meta.data_ptr() + 12 * B), _eng._stream_ptr())
+    rc = rois.lib.prad_batch_glszm_f2d_dev(_vp(rois.data), _vp(rois.mask), _iptr(sizes), _lp(off), B, int(Ng), int(f2d), _vp(zones),
+                                           _vp(meta), C.c_void_p(meta.data_ptr() + 12 * B), _eng._stream_ptr())
     _lib.raise_for(rc, "batched GLSZM")
     host = meta.cpu().numpy()
     return zones, np.ascontiguousarray(host[:3 * B].reshape(B, 3)), host[3 * B:].copy()
@@ -221,24 +291,25 @@ class _GlszmBatch(list):
     flat = None
 
 
-def glszm_batch_zones(levels, masks, sizes, Ng):
+def glszm_batch_zones(levels, masks, sizes, Ng, force2D=False, force2Ddimension=0, weightingNorm=None, spacing=(1.0, 1.0, 1.0)):
     """the zone lists of B small ROIs from the labelling launch alone -> (list of B int32 device tensors [nzones, 2] of
     (level, size) in raster order of each zone's first voxel -- views into one buffer --, summary int32 numpy [B, 3]: zones,
     largest zone, distinct sizes; status int32 numpy [B]).  Raises NotImplementedError outside the native domain (Ng > 64, a box
-    above batch_glszm_max_vox() voxels)."""
+    above batch_glszm_max_vox() voxels).  force2D / force2Ddimension: as glszm_batch; weightingNorm / spacing are ignored."""
     rois = _roi_batch(levels, masks, sizes)
-    zones, summary, status = _glszm_label(rois, rois.sizes, rois.off, Ng)
+    pl = _planar(force2D, force2Ddimension, weightingNorm, spacing)
+    zones, summary, status = _glszm_label(rois, rois.sizes, rois.off, Ng, pl.f2d)
     _cm._set_batch_route("batch")
     return [zones[2 * int(o):2 * int(o) + 2 * int(n)].view(-1, 2) for o, n in zip(rois.off, summary[:, 0])], summary, status
 
 
-def _glszm(rois, Ng, compact):
+def _glszm(rois, Ng, compact, pl=Planar()):
     Ng, B, dev = int(Ng), rois.B, rois.device
     covered = np.flatnonzero(rois.nvox <= batch_glszm_max_vox()) if Ng <= 64 else np.zeros(0, dtype=np.int64)
     results, status = _GlszmBatch([None] * B), [_lib.PRAD_OK] * B
     if len(covered):
         coff = np.ascontiguousarray(rois.off[covered])
-        zones, summary, st = _glszm_label(rois, np.ascontiguousarray(rois.sizes[covered]), coff, Ng)
+        zones, summary, st = _glszm_label(rois, np.ascontiguousarray(rois.sizes[covered]), coff, Ng, pl.f2d)
         cols = np.maximum(summary[:, 2 if compact else 1], 1).astype(np.int64)
         k = summary[:, 2].astype(np.int64)
         out_off, s_off = np.append(np.int64(0), np.cumsum(Ng * cols)), np.append(np.int64(0), np.cumsum(k))
@@ -255,22 +326,25 @@ def _glszm(rois, Ng, compact):
         # (batch_features_per_angle evaluates the formulas on these buffers, in place)
         results.flat = GlszmFlat(flat, covered, out_off[:-1], cols, sizes_dev if compact else None, np.where(k > 0, s_off[:-1], -1))
     rest = sorted(set(range(B)) - set(int(b) for b in covered))
-    single = lambda i, m, Ns: _eng.glszm_compact(i, m, Ng, Ns) if compact else _eng.glszm(i, m, Ng, Ns)
-    for b, one, st in zip(rest, *_cm._looped_glszm(rois.boxes(rest), Ng, compact, single, rois.to_device)):
+    single = lambda i, m, Ns: _eng.glszm_compact(i, m, Ng, Ns, *pl.axes) if compact else _eng.glszm(i, m, Ng, Ns, *pl.axes)
+    for b, one, st in zip(rest, *_cm._looped_glszm(rois.boxes(rest), Ng, compact, single, rois.to_device, pl.f2d)):
         results[b], status[b] = one, st
     _cm._set_batch_route("looped" if not len(covered) else _route(len(rest), B))
     return results, status
 
 
-def glszm_batch(levels, masks, sizes, Ng, compact=True):
-    """GLSZM of B small ROIs in two launches (segment mode, 3-D, the full neighbourhood): zones labelled in LDS by one workgroup
+def glszm_batch(levels, masks, sizes, Ng, compact=True, force2D=False, force2Ddimension=0, weightingNorm=None,
+                spacing=(1.0, 1.0, 1.0)):
+    """GLSZM of B small ROIs in two launches (segment mode; the full neighbourhood, or with force2D the 8 neighbours in the plane
+    across axis force2Ddimension, as the single calls; weightingNorm / spacing are accepted and ignored, as the class ignores
+    them): zones labelled in LDS by one workgroup
     per ROI, one read-back of the per-ROI summary, one fill.  Inputs as texture_matrices_batch.  -> (list of B results, status
     [B]: 1, or 0 for a ROI with a masked level outside [1, Ng] -- the single call's IndexError; its result is that of an empty
     mask).  compact=True: a result is (P float64 [Ng, k] device tensor, sizes int32 numpy [k] ascending) as glszm_compact
     returns; compact=False: the dense [Ng, max(maxRegion, 1)] tensor as glszm returns.  The results of the native route are
     views into one flat buffer.  ROIs above batch_glszm_max_vox() voxels, or every ROI when Ng > 64, go through glszm_compact /
     glszm one by one (Ns = max(1, masked voxels)); last_batch_route() says "batch", "mixed" or "looped"."""
-    return _glszm(_roi_batch(levels, masks, sizes), Ng, compact)
+    return _glszm(_roi_batch(levels, masks, sizes), Ng, compact, _planar(force2D, force2Ddimension, weightingNorm, spacing))
 
 
 # ---- feature formulas (prad_batch_features_dev, csrc/kernels_batch_features.h) -----------------------------------------------
@@ -383,21 +457,31 @@ def batch_features_per_angle(mats, Ng, glszm=None, symmetric=True, mcc=True):
     return out
 
 
-def _texture_features(rois, Ng, classes, distances, gldm_a, symmetricalGLCM, mcc, mcc_angles):
+def _texture_features(rois, Ng, classes, distances, gldm_a, symmetricalGLCM, mcc, mcc_angles, pl=Planar()):
     B = rois.B
     fams = tuple(f for f in FEATURE_FAMILIES[:4] if f in classes)
     status = np.ones(B, dtype=np.int64)
     routes = []
     mats, zones = {}, None
+    pl = pl._replace(symmetric=bool(symmetricalGLCM))
     if fams:
-        mats, st = _matrices(rois, Ng, fams, distances, gldm_a)
+        mats, st = _matrices(rois, Ng, fams, distances, gldm_a, pl)
         routes.append(last_batch_route())
         status &= np.asarray(st, dtype=np.int64) == _lib.PRAD_OK
     if "glszm" in classes:
-        zones, st = _glszm(rois, Ng, True)
+        zones, st = _glszm(rois, Ng, True, pl)
         routes.append(last_batch_route())
         status &= np.asarray(st, dtype=np.int64) == _lib.PRAD_OK
-    per = batch_features_per_angle(mats, Ng, zones, symmetricalGLCM, mcc)
+    weighted = {f: mats[f + "_w"] for f in _cm.MERGE_FAMILIES if f + "_w" in mats}
+    if weighted:
+        # the ROI's one merged matrix per family, one angle and already symmetrised; the other families are laid out by the
+        # true angle counts (the GLDM width), so they take a call of their own
+        per = batch_features_per_angle(weighted, Ng, None, False, mcc)
+        rest = {f: mats[f] for f in mats if f in FEATURE_FAMILIES and f not in weighted}
+        if rest or zones is not None:
+            per.update(batch_features_per_angle(rest, Ng, zones, symmetricalGLCM, mcc))
+    else:
+        per = batch_features_per_angle(mats, Ng, zones, symmetricalGLCM, mcc)
     table = {}
     for f in classes:
         rows = np.full((B, _FEATURE_ROW[f]), np.nan)
@@ -413,20 +497,26 @@ def _texture_features(rois, Ng, classes, distances, gldm_a, symmetricalGLCM, mcc
 
 
 def texture_features_batch(levels, masks, sizes, Ng, classes=("glcm", "glrlm", "glszm", "gldm", "ngtdm"),
-                           distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True, mcc_angles=False):
-    """The texture FEATURES of B small ROIs (segment mode, 3-D; inputs as texture_matrices_batch): texture_matrices_batch,
+                           distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True, mcc_angles=False, force2D=False,
+                           force2Ddimension=0, weightingNorm=None, spacing=(1.0, 1.0, 1.0)):
+    """The texture FEATURES of B small ROIs (segment mode; inputs as texture_matrices_batch): texture_matrices_batch,
     glszm_batch(compact=True), the formulas of all matrices in two launches (batch_features_per_angle) and, per ROI, the mean
     over the angles the reference keeps (cmatrices._angle_mean).  -> ({class: float64 numpy [B, nfeat]}, status [B]): glcm 24
     columns (cmatrices.VOXEL_GLCM_FEATURES, then MCC -- NaN without `mcc`), glrlm / gldm / glszm 16 (the shared zone numbering),
-    ngtdm 5.  status 0: a masked level outside [1, Ng]; that ROI's rows are NaN, the others are not affected.  weightingNorm is
-    not offered.  Outside the native domain (Ng > 64, boxes above the batch caps) the single calls are looped and give the same
+    ngtdm 5.  status 0: a masked level outside [1, Ng]; that ROI's rows are NaN, the others are not affected.
+    force2D / force2Ddimension: every class uses the in-plane angle sets (texture_matrices_batch, glszm_batch).  weightingNorm +
+    spacing ((z, y, x): one triple or float [B, 3]): the GLCM and GLRLM rows come from the ROI's ONE merged matrix ("glcm_w" /
+    "glrlm_w" of texture_matrices_batch; MCC is evaluated on it) as the feature classes form them; GLDM, NGTDM and GLSZM ignore
+    the weights, as the classes do.  Outside the native domain (Ng > 64, boxes above the batch caps) the single calls are looped and give the same
     values; last_batch_route() says "batch", "mixed" or "looped".  mcc_angles=True adds the entry "glcm_mcc_angles": per ROI the
     MCC of every angle (float64 [Na], NaN for an empty angle; None with status 0) -- what the feature class averages as a flat
-    vector (cmatrices._mcc_angle_mean), in another order of additions than the column mean of the table."""
+    vector (cmatrices._mcc_angle_mean), in another order of additions than the column mean of the table; with weightingNorm
+    it has length 1."""
     rois, classes = _roi_batch(levels, masks, sizes), tuple(classes)
     if not classes or any(c not in FEATURE_FAMILIES for c in classes):
         raise ValueError("classes must be a non-empty subset of %s" % (FEATURE_FAMILIES,))
-    return _texture_features(rois, Ng, classes, distances, gldm_a, symmetricalGLCM, mcc, mcc_angles)
+    return _texture_features(rois, Ng, classes, distances, gldm_a, symmetricalGLCM, mcc, mcc_angles,
+                             _planar(force2D, force2Ddimension, weightingNorm, spacing))
 
 
 # ---- first-order statistics and discretisation (prad_batch_firstorder_dev / prad_batch_digitize_dev, -------------------------
@@ -537,7 +627,8 @@ def bin_batch(images, masks, sizes=None, stats=None, **binning):
 
 
 def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, binWidth=None, binCount=None, voxelArrayShift=0,
-                       voxelVolume=1.0, distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True, extras=False):
+                       voxelVolume=1.0, distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True, extras=False, force2D=False,
+                       force2Ddimension=0, weightingNorm=None, spacing=(1.0, 1.0, 1.0)):
     """The feature table of B small ROIs from their raw intensity boxes and masks (inputs as firstorder_batch): firstorder_batch
     and bin_batch -- two launches and two read-backs for the whole batch (binWidth, default 25, or binCount) -- then
     texture_features_batch once per distinct Ng of the batch on the ROIs that share it.  -> ({class: float64 numpy [B, nfeat]},
@@ -547,9 +638,11 @@ def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, b
     "looped" (texture_features_batch loops the single calls above 64 levels; MCC is not evaluated there -- its column is NaN
     for a ROI with more than 64 levels, as without `mcc`).  extras=True adds two entries the label route of the feature extractor
     needs to report what the feature classes report: "gray_levels" int64 [B], the number of grey levels that occur in the ROI, and
-    (with glcm) "glcm_mcc_angles", see texture_features_batch."""
+    (with glcm) "glcm_mcc_angles", see texture_features_batch.  force2D / force2Ddimension / weightingNorm / spacing: passed
+    to texture_features_batch; the first-order columns do not depend on them."""
     from . import firstorder as _fo
     rois = _roi_batch(images, masks, sizes, raw=True)
+    pl = _planar(force2D, force2Ddimension, weightingNorm, spacing)
     classes = tuple(classes)
     if not classes or any(c not in ROI_FEATURE_CLASSES for c in classes):
         raise ValueError("classes must be a non-empty subset of %s" % (ROI_FEATURE_CLASSES,))
@@ -576,7 +669,7 @@ def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, b
             idx = np.flatnonzero((Ng == ng) & (status == 1))
             sub, st = _texture_features(binned.subset(idx), ng, texture, distances, gldm_a, symmetricalGLCM,
                                         mcc and ng <= 64,       # (glcm_mcc declines more than 64 occurring levels)
-                                        extras and mcc and ng <= 64)
+                                        extras and mcc and ng <= 64, pl.subset(idx, B))
             routes.append(last_batch_route())
             for k, b in enumerate(idx):
                 if "glcm_mcc_angles" in sub:
