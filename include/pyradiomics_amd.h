@@ -714,6 +714,31 @@ int prad_batch_gather_dev(const void *image, int image_dtype, const void *labelm
                           const int *labels, const int *lo, const int *box, const long long *offsets, void *out_image,
                           unsigned char *out_mask, void *stream);
 
+/* ---- the wavelet sub-bands of many small boxes (csrc/kernels_batch_swt.h) ----------------------------------------------
+ * prad_batch_swt_dev: the level-1, undecimated, periodised 3-D transform of B boxes in ONE launch -- per box what
+ * getWaveletImage computes on it: one wrapped sample appended to every odd axis (imageoperations.py:914-919), pywt.swtn over
+ * axes (2, 1, 0), the pad cropped again -- with the pad folded into the kernel's index arithmetic.  `in` (DEVICE) holds the boxes
+ * in the batch layout of prad_batch_firstorder_dev, in the image's own dtype (0 float32, 1 float64, 2 int32, 3 int16; widened
+ * to float64 when staged: exact); sizes ([B][3], z y x), off (element offsets, ascending, boxes not overlapping) and the flen
+ * taps of dec_lo / dec_hi are HOST arrays.  out DEVICE float64 [8][band_stride], band_stride >= off[B - 1] + its voxels: band k
+ * of ROI b lies at out + k * band_stride + off[b] in the box's own shape, k = (bx * 2 + by) * 2 + bz as prad_swt_level1_dev
+ * numbers the bands for axes (2, 1, 0) -- every out[k] is itself a batch-layout buffer.  Each band of each native ROI equals,
+ * bit for bit, what the fused kernel of prad_swt_level1_any_dev gives for the padded box.
+ * verdict HOST int [B]: 0 the ROI was computed here; 8 it must be served by the single route (a padded extent -- n + (n & 1)
+ * -- below flen, the condition of the fused single kernel; or a box above 2^31 - 1 voxels): its slice of `out` is not touched.
+ * flen must be 2, 4 or 6 (haar / db1, db2 / sym2, coif1 / db3 / sym3): any other length in [2, 32] is PRAD_E_UNSUPPORTED with
+ * nothing launched and nothing written; outside [2, 32] PRAD_E_ARG.  PRAD_E_ARG also for a NULL pointer, B < 1, a size < 1, a
+ * negative offset, off[b] before the end of ROI b - 1, band_stride before the end of the last box, a dtype outside the list.
+ * One copy (the record and item tables) and one launch on `stream`, which is then synchronised; no atomics, no memset; kernel
+ * family "batch_swt" (prad_last_kernel_ms), prad_last_path "batch", prad_last_variant "batch-swt-fused".
+ * prad_batch_swt_plan (host only, pure, needs no device): the planner the call itself uses.  verdict as above; *n_items = the
+ * workgroups of the launch; items (may be NULL; int [*n_items][8], size it with a first call) = per workgroup ROI, z0, z1, y0,
+ * y1, x0, x1 (half-open ranges clipped to the box) and the tile width TX (8, 16 or 32; TY = 256 / TX).  The items of a native
+ * ROI tile its box exactly once; other ROIs get none.  Same argument errors as the call. */
+int prad_batch_swt_plan(const int *sizes, int B, int flen, int *verdict, long long *n_items, int *items);
+int prad_batch_swt_dev(const void *in, int dtype, const int *sizes, const long long *off, int B, const double *dec_lo,
+                       const double *dec_hi, int flen, double *out, long long band_stride, int *verdict, void *stream);
+
 /* ---- filter stack in front of the matrices (radiomics/imageoperations.py:756-970) ---------------------------
  * The arithmetic of both filters lives in third-party wheels (PyWavelets, SimpleITK/ITK) that are not part of
  * the reference tree; these entry points implement their published algorithms (see oracle/filters_oracle.py):

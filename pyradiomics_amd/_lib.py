@@ -137,7 +137,10 @@ SYMBOLS = {
                                           _vp, _vp, C.POINTER(C.c_longlong), _vp, _vp]),
     "prad_batch_gather_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _ip, C.c_int, _ip, _ip, _ip, C.POINTER(C.c_longlong), _vp,
                                         _vp, _vp]),
-    "prad_swt_level1": (C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp]),
+    "prad_batch_swt_plan": (C.c_int, [_ip, C.c_int, C.c_int, _ip, C.POINTER(C.c_longlong), _ip]),
+    "prad_batch_swt_dev": (C.c_int, [_vp, C.c_int, _ip, C.POINTER(C.c_longlong), C.c_int, _vp, _vp, C.c_int, _vp, C.c_longlong,
+                                     _ip, _vp]),
+    "prad_swt_level1":(C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp]),
     "prad_swt_level1_dev": (C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp, _vp]),
     "prad_swt_level1_any_dev": (C.c_int, [_vp, C.c_int, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp, _vp]),
     "prad_log": (C.c_int, [_vp, _ip, C.c_int, _vp, C.c_double, C.c_int, _vp]),

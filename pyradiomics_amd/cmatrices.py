@@ -715,6 +715,22 @@ def calculate_roi_features_batch(images, masks, classes=("firstorder", "glcm", "
     return {cls: {name: table[cls][:, i].copy() for i, name in enumerate(names[cls]) if name} for cls in table}
 
 
+def calculate_wavelet_batch(images, wavelet="coif1", level=1, start_level=0, force2D=False, force2Ddimension=0):
+    """The wavelet sub-bands of B small 3-D boxes (a list of host arrays: raw intensities): one upload, engine.wavelet_batch --
+    one launch for all boxes and all eight bands inside its native domain -- and one download.  -> ({image type name: [B float64
+    numpy arrays in the boxes' shapes]}, names): the names getWaveletImage yields, in its order ("wavelet-LLH" ...
+    "wavelet-LLL").  Needs a device (RuntimeError without one); last_batch_route() tells which route ran."""
+    ones = [np.ones(np.shape(i), dtype=bool) for i in images]
+    _, _, sizes, upload = _host_roi_batch(images, ones, "wavelet sub-bands", raw=True)
+    bands, names, _ = _engine().wavelet_batch(upload()[0], sizes, wavelet, level, start_level, force2D,
+                                              force2Ddimension=force2Ddimension)
+    host = bands.cpu().numpy()
+    nvox = sizes.astype(np.int64).prod(1)
+    off = np.concatenate([[0], np.cumsum(nvox)])
+    return {name: [host[row, off[b]:off[b + 1]].reshape(tuple(sizes[b])).copy() for b in range(len(nvox))]
+            for name, row in zip(names, names.rows)}, tuple(names)
+
+
 # ---- fused voxel-based features of the other four texture classes (prad_voxel_texture_features_dev) ---------
 _ZONE_LIKE = {
     "glrlm": (3, ["ShortRunEmphasis", "LongRunEmphasis", "GrayLevelNonUniformity", "GrayLevelNonUniformityNormalized",

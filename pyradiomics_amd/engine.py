@@ -1124,4 +1124,6 @@ def log_image(image: torch.Tensor, spacing_xyz, sigma: float, normalize: bool = 
 from .roi_batch import (FEATURE_FAMILIES, ROI_FEATURE_CLASSES, batch_digitize_max_edges, batch_features_per_angle,  # noqa: E402,F401
                         batch_firstorder_max_roi, batch_glszm_max_vox, batch_max_vox, bin_batch, firstorder_batch,
                         gather_rois_batch, glszm_batch, glszm_batch_zones, last_batch_route, roi_features_batch,
-                        texture_features_batch, texture_matrices_batch, texture_matrices_batch_flat)
+                        texture_features_batch, texture_matrices_batch, texture_matrices_batch_flat,
+                        BandNames, batch_swt_occupancy, batch_swt_plan, roi_features_batch_images, wavelet_band_names,
+                        wavelet_batch)

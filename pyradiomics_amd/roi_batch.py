@@ -686,6 +686,238 @@ def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, b
     return table, status.tolist()
 
 
+# ---- wavelet sub-bands of the boxes (prad_batch_swt_dev, csrc/kernels_batch_swt.h) -------------------------------------------
+class BandNames(tuple):
+    """the image type names of the sub-bands in the order getWaveletImage yields them; rows[i] = the row of `bands` that
+    names[i] refers to (row(name) looks it up)"""
+    def __new__(cls, names, rows):
+        self = super().__new__(cls, names)
+        self.rows = tuple(int(r) for r in rows)
+        return self
+
+    def row(self, name):
+        return self.rows[self.index(name)]
+
+
+def wavelet_band_names(level=1, naxes=3) -> BandNames:
+    """The names getWaveletImage yields for `level` levels over `naxes` transformed axes (3, or 2 with force2D), in its order:
+    the detail bands of every level ("wavelet-LLH" ... "wavelet-HHH", from level 2 on "wavelet2-LLH" ...), then the last
+    approximation.  Rows: at level 1 the band index of the kernels, (bx * 2 + by) * 2 + bz with L = 0 and H = 1 -- so the
+    approximation, yielded last, is row 0; with more levels the rows follow the names."""
+    keys = [""]
+    for _ in range(int(naxes)):
+        keys = [k + c for k in keys for c in "LH"]
+    level = int(level)
+    if level < 1:
+        raise ValueError("wavelet level %d" % level)
+    names = [("wavelet-%s" if idx == 1 else "wavelet%d-%%s" % idx) % k for idx in range(1, level + 1) for k in keys[1:]]
+    names.append(("wavelet-%s" if level == 1 else "wavelet%d-%%s" % level) % keys[0])
+    rows = list(range(1, len(keys))) + [0] if level == 1 else range(len(names))
+    return BandNames(names, rows)
+
+
+def batch_swt_plan(sizes, flen):
+    """Host-side plan of the batched wavelet launch (prad_batch_swt_plan; pure, needs no device).  sizes: int [B, 3]; flen: the
+    filter length.  -> (verdict int [B]: 0 native, 8 the single route; items int [n, 8]: per workgroup ROI, z0, z1, y0, y1,
+    x0, x1 -- half-open, clipped to the box -- and the tile width TX).  NotImplementedError for a filter length the kernel is
+    not built for (everything but 2, 4, 6), ValueError for bad arguments."""
+    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
+    B = int(sizes.shape[0])
+    lib = _lib.load()
+    verdict = np.zeros(max(B, 1), dtype=np.intc)
+    n = C.c_longlong(0)
+    _lib.raise_for(lib.prad_batch_swt_plan(_iptr(sizes), B, int(flen), _iptr(verdict), C.byref(n), None), "batch swt plan")
+    items = np.zeros((max(int(n.value), 1), 8), dtype=np.intc)
+    _lib.raise_for(lib.prad_batch_swt_plan(_iptr(sizes), B, int(flen), _iptr(verdict), C.byref(n), _iptr(items)), "batch swt plan")
+    return verdict[:B].copy(), items[:int(n.value)]
+
+
+def batch_swt_occupancy(sizes, flen):
+    """Counts -- not measurements -- of what the plan of a batch leaves idle, from `sizes` alone: {"items", "active_lanes": share
+    of the 256 lanes of the workgroups that own an output, "warmup_planes": share of the staged planes that are warm-up (F - 1
+    per item) rather than output planes, "native": ROIs}."""
+    verdict, items = batch_swt_plan(sizes, flen)
+    if not len(items):
+        return {"items": 0, "active_lanes": 0.0, "warmup_planes": 0.0, "native": 0}
+    it = items.astype(np.int64)
+    planes = it[:, 2] - it[:, 1]
+    lanes = (it[:, 4] - it[:, 3]) * (it[:, 6] - it[:, 5])
+    steps = planes + (int(flen) - 1)
+    return {"items": int(len(it)), "active_lanes": float((lanes * steps).sum() / (256.0 * steps.sum())),
+            "warmup_planes": float((int(flen) - 1) * len(it) / steps.sum()), "native": int((verdict == 0).sum())}
+
+
+def _image_batch(images, sizes) -> RoiBatch:
+    """raw intensity boxes without masks, as _roi_batch(raw=True) normalises them (the batch's `mask` is None)"""
+    if isinstance(images, (list, tuple)):
+        if not len(images):
+            raise ValueError("empty batch")
+        if any(i.dim() != 3 for i in images):
+            raise ValueError("the batched wavelet takes 3-D boxes")
+        sizes = np.array([tuple(i.shape) for i in images], dtype=np.intc).reshape(-1, 3)
+        dts = [i.dtype for i in images]
+        dt = dts[0] if dts[0] in _eng._DTYPE_CODES and all(d == dts[0] for d in dts) else torch.float64
+        images = torch.cat([i.reshape(-1).to(dt) for i in images])
+    elif sizes is None:
+        raise ValueError("a flat image tensor needs `sizes`")
+    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
+    data = images.reshape(-1)
+    if not data.is_cuda:
+        raise ValueError("engine.* expects CUDA/HIP tensors; use pyradiomics_amd.cmatrices for numpy input")
+    data = (data if data.dtype in _eng._DTYPE_CODES else data.to(torch.float64)).contiguous()
+    lib = _lib.load()
+    _set_device(lib, data.device)
+    nvox = sizes.astype(np.int64).prod(1)
+    if not len(nvox) or int(nvox.sum()) != data.numel():
+        raise ValueError("sizes describe %d voxels, the buffer holds %d" % (int(nvox.sum()), data.numel()))
+    return RoiBatch(lib, data, None, sizes, nvox, _offsets(nvox), data.device)
+
+
+def _wavelet(rois, wavelet, level, start_level, force2D, force2Ddimension, out):
+    from . import filters
+    lo, hi = filters.wavelet_filters(wavelet)
+    lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+    level, start_level = int(level), int(start_level)
+    axes = [2, 1, 0]
+    if force2D:
+        _cm.batch_forced_dim(True, force2Ddimension)          # (raises on a dimension outside 0 .. 2)
+        axes.remove(int(force2Ddimension))
+    names = wavelet_band_names(level, len(axes))
+    B, W = rois.B, rois.data.numel()
+    if out is None:
+        out = torch.empty((len(names), W), dtype=torch.float64, device=rois.device)
+    elif (out.dtype != torch.float64 or out.device != rois.device or out.dim() != 2 or tuple(out.shape) != (len(names), W)
+          or (W > 1 and out.stride(1) != 1) or out.stride(0) < W):
+        raise ValueError("out must be a float64 [%d, %d] tensor on %s with contiguous rows" % (len(names), W, rois.device))
+    verdict = np.full(B, 8, dtype=np.intc)
+    if level == 1 and start_level == 0 and not force2D:
+        rc = rois.lib.prad_batch_swt_dev(_vp(rois.data), _eng._DTYPE_CODES[rois.data.dtype], _iptr(rois.sizes), _lp(rois.off), B,
+                                         C.c_void_p(lo.ctypes.data), C.c_void_p(hi.ctypes.data), len(lo), _vp(out),
+                                         int(out.stride(0)), _iptr(verdict), _eng._stream_ptr())
+        if rc == _lib.PRAD_E_UNSUPPORTED:          # a filter length the kernel is not built for: nothing was launched
+            verdict[:] = 8
+        else:
+            _lib.raise_for(rc, "batched wavelet")
+    rest = np.flatnonzero(verdict != 0)
+    for b in rest:
+        approx, ret = filters._swt3_device(rois.view(rois.data, b), tuple(axes), wavelet=(lo, hi), level=level,
+                                           start_level=start_level)
+        o, n = int(rois.off[b]), int(rois.nvox[b])
+        for row, band in zip(names.rows, [t for wl in ret for t in wl.values()] + [approx]):
+            out[row, o:o + n] = band.reshape(-1)
+    _cm._set_batch_route(_route(len(rest), B))
+    return out, names
+
+
+def wavelet_batch(images, sizes=None, wavelet="coif1", level=1, start_level=0, force2D=False, out=None, force2Ddimension=0):
+    """The wavelet sub-bands of B small boxes in ONE launch: per box what getWaveletImage computes on it (one wrapped sample
+    appended to every odd axis, the undecimated periodised transform over x, y, z, the pad cropped), bit for bit.  images: a list
+    of 3-D device tensors of one dtype (float32, float64, int32, int16; anything else is widened to float64), or a flat device
+    tensor holding the boxes back to back plus `sizes` (int [B, 3]).  -> (bands, names, sizes): bands float64 [8, W] on the
+    device, W the voxels of the batch -- every row is itself a flat batch tensor that roi_features_batch takes as `images`;
+    names a BandNames: the strings getWaveletImage yields, in its order ("wavelet-LLH" ... "wavelet-HHH", "wavelet-LLL"), with
+    names.rows[i] the row of `bands` that names[i] refers to; sizes int32 [B, 3].  out: a preallocated float64 [8, W] tensor
+    (rows contiguous, row stride >= W) to fill instead.
+    Native: filters of 2, 4 or 6 taps (haar / db1, db2 / sym2, coif1 / db3 / sym3) and boxes whose padded extents all hold the
+    filter; the other boxes are filled from filters._swt3_device one by one.  Every box goes that way -- into the same layout --
+    for a longer filter, for level != 1 or start_level != 0 (bands [7 * level + 1, W], rows in the order of the names) and
+    with force2D (the axis force2Ddimension is not transformed: [4, W] at level 1).  last_batch_route() says "batch", "mixed"
+    or "looped".  The sub-bands are float64 whatever the input (the single route's stated deviation for float32 images)."""
+    rois = _image_batch(images, sizes)
+    bands, names = _wavelet(rois, wavelet, level, start_level, force2D, force2Ddimension, out)
+    return bands, names, rois.sizes
+
+
+def _tight_boxes(rois):
+    """The box the feature classes of the reference see -- computeFeatures crops every derived image to the ROI's bounding box
+    (featureextractor.py:560-604), here cropToTumorMask(padDistance=0)'s box: the bounding box of the mask with its x extent
+    grown to a multiple of four inside the given box (imageoperations.alignedBox) -- for every ROI of the batch, worked out on
+    the device, ROIs of one shape together.  -> (int64 device tensor: the elements of the flat buffers that make up the tight
+    boxes, back to back in the ROIs' order; sizes intc [B, 3]).  A ROI with an empty mask keeps its whole box."""
+    from . import imageoperations
+    dev, B = rois.device, rois.B
+    tight = rois.sizes.copy()
+    picks, owners = [], []
+    shapes, inverse = np.unique(rois.sizes, axis=0, return_inverse=True)
+    inverse = np.asarray(inverse).reshape(-1)
+    for g, shape in enumerate(shapes):
+        bs = np.flatnonzero(inverse == g)
+        G, n = len(bs), int(np.prod(shape.astype(np.int64)))
+        pos = torch.from_numpy(rois.off[bs]).to(dev)[:, None] + torch.arange(n, device=dev)[None, :]
+        m = (rois.mask[pos] != 0).view(G, *[int(s) for s in shape])
+        ends = []
+        for ax in range(3):
+            line = m.to(torch.uint8).amax(dim=tuple(d + 1 for d in range(3) if d != ax)).to(torch.int32)
+            ends += [line.argmax(1), int(shape[ax]) - 1 - line.flip(1).argmax(1), line.sum(1)]
+        ends = torch.stack(ends, 1).cpu().numpy().astype(np.int64)       # one read-back per shape
+        lo, hi = ends[:, 0::3].copy(), ends[:, 1::3].copy()
+        empty = ends[:, 2] == 0
+        lo[empty], hi[empty] = 0, shape.astype(np.int64) - 1
+        lo, hi = imageoperations.alignedBox(lo, hi, tuple(int(s) for s in shape))
+        tight[bs] = (hi - lo + 1).astype(np.intc)
+        d_lo, d_hi = torch.from_numpy(lo).to(dev), torch.from_numpy(hi).to(dev)
+        keep = None
+        for ax in range(3):
+            i = torch.arange(int(shape[ax]), device=dev).view([1] + [-1 if d == ax else 1 for d in range(3)])
+            inside = (i >= d_lo[:, ax].view(G, 1, 1, 1)) & (i <= d_hi[:, ax].view(G, 1, 1, 1))
+            keep = inside if keep is None else keep & inside
+        keep = keep.reshape(G, n)
+        picks.append(pos[keep])
+        owners.append(torch.from_numpy(bs).to(dev)[:, None].expand(G, n)[keep])
+    idx = torch.cat(picks)
+    if len(shapes) > 1:          # (the groups follow one another: back into the ROIs' order, each box keeping its own)
+        idx = idx[torch.argsort(torch.cat(owners), stable=True)]
+    return idx, np.ascontiguousarray(tight)
+
+
+_WAVELET_SETTINGS = ("wavelet", "level", "start_level")
+
+
+def roi_features_batch_images(images, masks, sizes=None, imageTypes=None, classes=ROI_FEATURE_CLASSES, **settings):
+    """roi_features_batch on the boxes themselves ("Original") and on their wavelet sub-bands ("Wavelet": wavelet_batch, one
+    launch for all eight), each derived image binned on its own per ROI as the reference bins every derived image.  The
+    transform sees the boxes as they are given -- with the margin around the ROI that the filter needs, padDistance in the
+    reference --; the feature calls see every image cut to the ROI's bounding box (_tight_boxes: one gather per image), as the
+    reference's feature classes do, so a ROI's values do not depend on the margin it was handed over with.  imageTypes:
+    {"Original": {}, "Wavelet": {}} by default; the dict of a type holds settings for that type alone (for "Wavelet" also
+    wavelet / level / start_level), which override **settings -- the keyword arguments of roi_features_batch; force2D and
+    force2Ddimension also steer the transform, as in getWaveletImage.  Any other image type: NotImplementedError.
+    -> ({image name: {class: float64 numpy [B, nfeat]}}, status [B]): image names "original" and those of wavelet_batch, in
+    the reference's order; status[b] is the AND over the images.  last_batch_route() joins the routes of all calls."""
+    imageTypes = {"Original": {}, "Wavelet": {}} if imageTypes is None else dict(imageTypes)
+    for t in imageTypes:
+        if t not in ("Original", "Wavelet"):
+            raise NotImplementedError("roi_features_batch_images: image type %r (Original and Wavelet are batched)" % (t,))
+    if not imageTypes:
+        raise ValueError("roi_features_batch_images: no image type")
+    rois = _roi_batch(images, masks, sizes, raw=True)
+    tables, routes = {}, []
+    status = np.ones(rois.B, dtype=np.int64)
+    pick, tight_sizes = _tight_boxes(rois)
+    tight_mask = rois.mask[pick]
+
+    def features(name, data, kw):
+        table, st = roi_features_batch(data[pick], tight_mask, tight_sizes, classes, **kw)
+        routes.append(last_batch_route())
+        tables[name] = table
+        status[:] &= np.asarray(st, dtype=np.int64)
+
+    for t, custom in imageTypes.items():
+        kw = dict(settings)
+        kw.update(custom or {})
+        if t == "Original":
+            features("original", rois.data, kw)
+            continue
+        wkw = {k: kw.pop(k) for k in _WAVELET_SETTINGS if k in kw}
+        bands, names = _wavelet(rois, wkw.get("wavelet", "coif1"), wkw.get("level", 1), wkw.get("start_level", 0),
+                                kw.get("force2D", False), kw.get("force2Ddimension", 0), None)
+        routes.append(last_batch_route())
+        for name, row in zip(names, names.rows):
+            features(name, bands[row], kw)
+    _cm._set_batch_route(_joined_route(routes))
+    return tables, status.tolist()
+
+
 # ---- the boxes of many labels of one label map in the batch layout (prad_batch_gather_dev, csrc/kernels_batch_gather.h) -------
 def gather_rois_batch(image, labelmap, labels, lo, hi, masks=True, images=True):
     """The boxes of B labels cut out of one 3-D volume in ONE launch, packed the way the *_batch functions take raw images.
