@@ -96,14 +96,23 @@ int prad_timing_end(void);
  * caller's stream does NOT wait for a lane: inputs and outputs of a deferred call belong to the library until
  * prad_deferred_status returns (it synchronises the stream and every lane).
  * Pipeline (the default deferred mode; prad_set_deferred_mode(0) or PRAD_DEFERRED_MODE=lanes selects the lanes):
- * deferred whole-volume calls stay on the caller's stream and form a two-stage pipeline -- call N launches the walks of
+ * deferred whole-volume calls stay on the caller's stream (but see "Twin pipelines" below) and form a two-stage pipeline -- call N launches the walks of
  * volume N-1 with the PACK of volume N riding in the same launch as a side job of the walking waves (the pack is
  * HBM-bound, the walk issue-bound: the pack's memory time disappears), then finalizes volume N-1.  Volume N is walked by
  * the next deferred call, or by prad_deferred_join / prad_deferred_status, which flush the pipeline.  As with the lanes,
  * inputs and outputs of a deferred call belong to the library until one of those two returns.  The pipeline takes the
  * volumes of the fixed-window kernels -- fused table (up to 44 levels) and, since round 5, two tables (45 .. 160 levels;
  * a volume of the other kind than the one before it packs in a launch of its own) -- every other whole-volume call is
- * dealt onto the lanes. */
+ * dealt onto the lanes.
+ * Twin pipelines: large volumes (from 2^27 voxels, 512^3; PRAD_PIPE_TWIN=1 forces it for every pipeline volume,
+ * PRAD_PIPE_TWIN=0 switches it off) do NOT stay on the caller's stream: they are dealt alternately onto TWO instances of the
+ * pipeline, each on an internal stream of its own (the lanes' streams 0 and 1) that waits for the work queued on the caller's
+ * stream at the time of the call, each with workspace sets of its own.  Consecutive walk launches are then unordered on the
+ * device and fill each other's uneven ends.  The contract is the one above -- inputs and outputs belong to the library until
+ * prad_deferred_status or prad_deferred_join returns; both cover both pipelines -- with a volume's outputs written two calls
+ * later than on one pipeline.  Two in-flight calls that name the same output buffer end with the later call's values, as on
+ * one stream.  The brackets of prad_timing_* are recorded on the stream a launch goes to; with overlapping launches a bracket's
+ * duration is no kernel speed (take those with PRAD_PIPE_TWIN=0). */
 #define PRAD_E_DEFERRED (-6)
 int prad_set_deferred(int on);
 int prad_set_lanes(int n);                 /* 0 = default; returns PRAD_E_ARG outside [0, 4] */

@@ -466,13 +466,17 @@ struct SetZero {
   size_t rz_zero = 0;      // leading words known to be zero
   bool fl_zero = false;
 };
-constexpr int kPipeSets = 4;   // workspace sets of the pipeline: packed, walked, being finalized, and one that is re-zeroed
+constexpr int kPipeSets = 4;   // workspace sets of ONE pipeline: packed, walked, being finalized, and one that is re-zeroed
+constexpr int kPipes = 2;      // pipeline instances (twin: volumes are dealt alternately onto both); instance p owns sets p * kPipeSets ...
+constexpr int kAllPipeSets = kPipes * kPipeSets;   // (the lanes' sets lie behind them)
+inline bool pipe_set(int lane) { return lane >= 0 && lane < kAllPipeSets; }
+inline int next_pipe_set(int lane) { return lane - lane % kPipeSets + (lane + 1) % kPipeSets; }   // the next set of the same instance
 SetZero *set_zero_book() {
-  static thread_local SetZero book[kPipeSets];
+  static thread_local SetZero book[kAllPipeSets];
   return book;
 }
 void set_zero_forget() {
-  for (int i = 0; i < kPipeSets; i++) set_zero_book()[i] = SetZero();
+  for (int i = 0; i < kAllPipeSets; i++) set_zero_book()[i] = SetZero();
 }
 int launch_zero3(hipStream_t s, const ZeroNeed &z) {
   const size_t total_w = z.acc_w + z.rz_w + z.fl_w;
@@ -526,7 +530,7 @@ int vol_prepare(Call &k, const SweepKnobs &kn, const SweepPlan &p, int Ng, int N
   z.rz_w = v.rowzero ? ((size_t)nrows + 3) / 4 : 0;
   z.fl = reinterpret_cast<u32 *>(v.flags_d);
   z.fl_w = 4;
-  if (c.lane >= 0 && c.lane < kPipeSets) {   // a set of the pipeline: what an earlier walk launch re-zeroed need not be zeroed again
+  if (pipe_set(c.lane)) {   // a set of a pipeline: what an earlier walk launch re-zeroed need not be zeroed again
     SetZero &S = set_zero_book()[c.lane];
     const size_t cap = v.rowzero ? c.bufs[c.key("rowzero")].cap : 0;
     if (fin_ride(kn)) {
@@ -797,7 +801,7 @@ int sweep_glcm_glrlm(Call &k, const SweepKnobs &kn, const SweepPlan &p, int Ng, 
 // is untouched: its volumes are finalized behind their walk launch.
 //
 // Workspace sets.  Three volumes are in flight -- packed, walked, being finalized (whose LEVELS the rare exact test reads) -- so
-// FOUR sets alternate (Context::lane = seq % 4; the stream is the caller's).  Launch N walks N-1 (set N-1), packs N (set N),
+// FOUR sets alternate (Context::lane = base + seq % 4; the stream is the caller's, or the instance's own: "Twin" below).  Launch N walks N-1 (set N-1), packs N (set N),
 // finalizes N-2 (set N-2) and zeroes
 //   * the accumulators and control words of set N: used by the walks of N in launch N+1, last read by the finalize of N-4;
 //   * the row flags and the four flag words of set N+1 = set N-3: written by the pack of N+1 in launch N+1, last read in
@@ -806,22 +810,94 @@ int sweep_glcm_glrlm(Call &k, const SweepKnobs &kn, const SweepPlan &p, int Ng, 
 // It holds by construction: make_fin_job names a range only after comparing its SET with the sets of the three volumes the
 // launch works on, and everything earlier is ordered by the stream.  A set remembers what is known to be zero (SetZero):
 // vol_prepare launches zero3_kernel only for the rest (the first volumes of a run, a grown buffer, more rows than were re-zeroed).
+//
+// Twin (PRAD_PIPE_TWIN; automatic from kTwinMinVoxels voxels).  All of the above is ONE instance (PipeState).  There are two per
+// thread.  A twin call n -- n counts the twin calls of the thread -- goes to instance n % 2, which runs on internal stream n % 2
+// (Context::lane_stream; the stream first waits for an event recorded on the caller's stream at the call) and owns the workspace
+// sets (n % 2) * 4 ... + 3.  Its launch { walk n-2, pack n, finalize n-4, zeroing } depends on launch n-2 only, so launches n and
+// n+1 are unordered on the device and the line workgroups of n+1 take the CUs that come free at the uneven end of n.  "N-1" above
+// reads "the instance's previous call".  The sets of the two instances are disjoint, no launch names a set of the other instance
+// (make_fin_job and vol_prepare stay inside next_pipe_set's instance), so the INVARIANT holds per instance, by construction, and
+// across instances there is nothing shared to order -- except
+//   * the sticky verdict word, which every writer only ever SETS (the finalize kernels, the latch kernels); only
+//     prad_deferred_status clears it, after it has synchronised both streams;
+//   * output buffers a caller hands to calls on BOTH instances: each instance remembers the output ranges of what it has in flight
+//     (PipeState::outs); a call whose outputs overlap a range of the other instance first flushes that instance and lets its own
+//     stream wait for it (an event), so the later call's values stand last, as on one stream.
+// A call that is not twin runs on instance 0 on the caller's stream, as ever; a change of kind is a change of the instance's
+// stream, which pipeline_step orders with an event.  Every drain (join, status, mark, mode / lanes / device changes, workspace
+// release, a volume the pipeline does not take) covers both instances.
+// automatic twin from this many voxels (512^3): the smallest size of the sweep 128^3 ... 512^3 from which twin was faster in EVERY
+// pair; the smaller sizes gained more on average (26 % at 128^3) but one pair of eight at 384^3 was slower
+// (profiles/twin_pipeline_measurements.md section 3).  Never below 2^21: tests count the launches of the single pipeline on small volumes.
+constexpr long long kTwinMinVoxels = 1LL << 27;
+struct OutRange {
+  const char *lo, *hi;
+};
 struct PipeState {
   VolState pending;
   VolState walked;              // walked, not finalized: its finalize rides in the next walk launch or runs stand-alone first
   hipStream_t s = nullptr;      // stream the pending volume's pack was enqueued on
   unsigned long long seq = 0;
   hipEvent_t ev = nullptr;
-  int mode = -1;                // 1 pipeline, 0 lanes
+  int base = 0;                 // first workspace set of the instance
+  std::vector<OutRange> outs;   // outputs of calls enqueued since the instance was last waited for by the host or by the other one
 };
-PipeState &pipe_state() {
-  static thread_local PipeState p;
+struct PipeShared {
+  int mode = -1;                // 1 pipeline, 0 lanes
+  unsigned long long twin_calls = 0;
+};
+PipeState &pipe_state(int i) {
+  static thread_local PipeState p[kPipes];
+  p[i].base = i * kPipeSets;
+  return p[i];
+}
+PipeShared &pipe_shared() {
+  static thread_local PipeShared p;
   return p;
 }
 bool pipeline_mode(const SweepKnobs &kn) {
-  PipeState &ps = pipe_state();
+  PipeShared &ps = pipe_shared();
   if (ps.mode < 0) ps.mode = kn.lanes_mode ? 0 : 1;
   return ps.mode == 1;
+}
+bool pipelines_busy() {
+  for (int i = 0; i < kPipes; i++)
+    if (pipe_state(i).pending.valid || pipe_state(i).walked.valid) return true;
+  return false;
+}
+// `s` waits (on the device) for everything the instance has enqueued on a stream of its own
+int pipeline_order(PipeState &ps, hipStream_t s) {
+  if (!ps.s || ps.s == s) return PRAD_OK;
+  if (!ps.ev) PRAD_HIP(hipEventCreateWithFlags(&ps.ev, hipEventDisableTiming));
+  PRAD_HIP(hipEventRecord(ps.ev, ps.s));
+  PRAD_HIP(hipStreamWaitEvent(s, ps.ev, 0));
+  return PRAD_OK;
+}
+void out_ranges_add(PipeState &ps, const double *glcm, size_t nglcm, const double *glrlm, size_t nglrlm) {
+  const OutRange r[2] = {{(const char *)glcm, (const char *)(glcm + nglcm)}, {(const char *)glrlm, (const char *)(glrlm + nglrlm)}};
+  for (int i = 0; i < 2; i++) {
+    if (!r[i].lo) continue;
+    bool known = false;
+    for (OutRange &o : ps.outs)
+      if (o.lo <= r[i].lo && r[i].hi <= o.hi) known = true;
+    if (known) continue;
+    if (ps.outs.size() >= 64) {   // (a caller with ever new buffers: one range that covers them all -- overlaps may be reported that are none)
+      for (const OutRange &o : ps.outs) {
+        ps.outs[0].lo = std::min(ps.outs[0].lo, o.lo);
+        ps.outs[0].hi = std::max(ps.outs[0].hi, o.hi);
+      }
+      ps.outs.resize(1);
+    }
+    ps.outs.push_back(r[i]);
+  }
+}
+bool out_ranges_overlap(const PipeState &ps, const double *glcm, size_t nglcm, const double *glrlm, size_t nglrlm) {
+  const OutRange r[2] = {{(const char *)glcm, (const char *)(glcm + nglcm)}, {(const char *)glrlm, (const char *)(glrlm + nglrlm)}};
+  for (int i = 0; i < 2; i++)
+    for (const OutRange &o : ps.outs)
+      if (r[i].lo && r[i].lo < o.hi && o.lo < r[i].hi) return true;
+  return false;
 }
 int pipeline_sticky(Context &c, int **sticky) { return c.get<int>("deferred_sticky", 16, sticky); }
 
@@ -831,7 +907,7 @@ bool fin_job_empty(const FinJob &fj) { return fj.Na == 0 && fj.zn[0] + fj.zn[1] 
 // last, and the job's 32-bit element indices)
 bool fin_can_ride(const SweepKnobs &kn, const VolState &v) {
   const SweepPlan &p = v.p;
-  if (!(v.glcm && v.glrlm && p.fw && p.fused && p.lines.count > 0 && v.levels && v.lane >= 0 && v.lane < kPipeSets)) return false;
+  if (!(v.glcm && v.glrlm && p.fw && p.fused && p.lines.count > 0 && v.levels && pipe_set(v.lane))) return false;
   if (p.row_slot >= 0 && p.fw_xblocks == 0) return false;   // (PRAD_FW_XROLE=0: the x angle is a launch behind the walk launch)
   if (!finalize_one(kn) || (long long)v.Ng * v.Nr >= (1LL << 30) || v.Ng > 255 || v.Na > PRAD_MAX_SWEEP || v.Na != p.aset.count) return false;
   return ((long long)v.Ng * v.Nr + (long long)v.Ng * v.Ng) * v.Na < (1LL << 31);
@@ -846,8 +922,8 @@ bool fin_host_ok(const SweepKnobs &kn, const PipeState &ps, const VolState &host
 
 // The riding job of the launch that walks `host` and packs the volume of set `new_lane`: the finalize of `walked` (or none) and
 // the zeroing of `need` (the new volume's accumulators; or none) and of the NEXT set's row flags and flag words.  Each range is
-// named only if its set is none of the sets this launch works on (see the invariant above).
-FinJob make_fin_job(const VolState &host, const VolState *walked, const ZeroNeed *need, int new_lane) {
+// named only if its set is one of instance ps and none of the sets this launch works on (see the invariant above).
+FinJob make_fin_job(const PipeState &ps, const VolState &host, const VolState *walked, const ZeroNeed *need, int new_lane) {
   FinJob j;
   memset(&j, 0, sizeof(j));
   const int nline = host.p.fw_blocks;
@@ -878,12 +954,13 @@ FinJob make_fin_job(const VolState &host, const VolState *walked, const ZeroNeed
     }
   }
   const int wl = walked ? walked->lane : -1;
-  if (need && need->acc_w > 0 && new_lane >= 0 && new_lane < kPipeSets && new_lane != host.lane && new_lane != wl) {
+  const bool mine = new_lane >= ps.base && new_lane < ps.base + kPipeSets;
+  if (need && need->acc_w > 0 && mine && new_lane != host.lane && new_lane != wl) {
     j.z[0] = need->acc;
     j.zn[0] = (unsigned)need->acc_w;
   }
-  if (new_lane >= 0 && new_lane < kPipeSets) {
-    const int t = (new_lane + 1) % kPipeSets;
+  if (mine) {
+    const int t = next_pipe_set(new_lane);
     SetZero &S = set_zero_book()[t];
     if (t != host.lane && t != wl && t != new_lane && S.rz_zero < S.rz_used && S.rz) {
       j.z[1] = S.rz;
@@ -900,8 +977,7 @@ FinJob make_fin_job(const VolState &host, const VolState *walked, const ZeroNeed
 }
 
 // the stand-alone finalize of the walked volume on stream s (ordered behind its walk launch by the caller)
-int pipeline_finish_walked(Context &c, const SweepKnobs &kn, hipStream_t s) {
-  PipeState &ps = pipe_state();
+int pipeline_finish_walked(Context &c, const SweepKnobs &kn, PipeState &ps, hipStream_t s) {
   if (!ps.walked.valid) return PRAD_OK;
   Call k;
   k.c = &c;
@@ -918,15 +994,10 @@ int pipeline_finish_walked(Context &c, const SweepKnobs &kn, hipStream_t s) {
 // walks of the pending volume on stream s (pj: the next volume's pack as a side job, or n16 == 0) and its finalize -- at once, or,
 // with `keep`, left to the next walk launch (the volume becomes `walked`).  The finalize of the volume walked BEFORE rides in
 // this launch if it can, else it is launched first.  need / new_lane: the zeroing the next volume still asks for and its set.
-int pipeline_retire(Context &c, const SweepKnobs &kn, hipStream_t s, const PackJob &pj, bool keep = false, const ZeroNeed *need = nullptr,
-                    int new_lane = -1) {
-  PipeState &ps = pipe_state();
+int pipeline_retire(Context &c, const SweepKnobs &kn, PipeState &ps, hipStream_t s, const PackJob &pj, bool keep = false,
+                    const ZeroNeed *need = nullptr, int new_lane = -1) {
   const bool host_ok = fin_host_ok(kn, ps, ps.pending, pj, s);   // (before ps.s moves)
-  if (ps.s != s) {   // the pack ran on another stream: order the two on the device
-    if (!ps.ev) PRAD_HIP(hipEventCreateWithFlags(&ps.ev, hipEventDisableTiming));
-    PRAD_HIP(hipEventRecord(ps.ev, ps.s));
-    PRAD_HIP(hipStreamWaitEvent(s, ps.ev, 0));
-  }
+  PRAD_TRY(pipeline_order(ps, s));   // the pack ran on another stream: order the two on the device
   Call k;
   k.c = &c;
   k.s = s;
@@ -938,12 +1009,12 @@ int pipeline_retire(Context &c, const SweepKnobs &kn, hipStream_t s, const PackJ
   memset(&fj, 0, sizeof(fj));
   if (host_ok) {
     const bool rides = ps.walked.valid && fin_can_ride(kn, ps.walked) && ps.walked.lane != ps.pending.lane && ps.walked.lane != new_lane;
-    if (ps.walked.valid && !rides) PRAD_TRY(pipeline_finish_walked(c, kn, s));
-    fj = make_fin_job(ps.pending, rides ? &ps.walked : nullptr, need, new_lane);
+    if (ps.walked.valid && !rides) PRAD_TRY(pipeline_finish_walked(c, kn, ps, s));
+    fj = make_fin_job(ps, ps.pending, rides ? &ps.walked : nullptr, need, new_lane);
     fj.sticky = sticky;
     ps.walked.valid = false;   // (enqueued with the launch below)
   } else {
-    PRAD_TRY(pipeline_finish_walked(c, kn, s));
+    PRAD_TRY(pipeline_finish_walked(c, kn, ps, s));
   }
   if (need && need->acc_w > 0 && fj.zn[0] == 0) {   // (the job did not take the accumulators: their set is one the launch works on)
     ZeroNeed acc;
@@ -962,33 +1033,58 @@ int pipeline_retire(Context &c, const SweepKnobs &kn, hipStream_t s, const PackJ
   return PRAD_OK;
 }
 
-// nothing pending or walked afterwards (kernels enqueued on the pending volume's own stream; no host synchronisation).
-int pipeline_flush(Context &c, const SweepKnobs &kn) {
-  PipeState &ps = pipe_state();
+// nothing pending or walked in the instance afterwards (kernels enqueued on the pending volume's own stream; no host
+// synchronisation).  A failure leaves the instance empty: what could not be enqueued is not tried again.
+int pipeline_flush(Context &c, const SweepKnobs &kn, PipeState &ps) {
   if (!ps.pending.valid && !ps.walked.valid) return PRAD_OK;
   PackJob none;
   memset(&none, 0, sizeof(none));
   const size_t before = c.times.size();
-  if (ps.pending.valid) PRAD_TRY(pipeline_retire(c, kn, ps.s, none));
-  else PRAD_TRY(pipeline_finish_walked(c, kn, ps.s));
+  const int rc = ps.pending.valid ? pipeline_retire(c, kn, ps, ps.s, none) : pipeline_finish_walked(c, kn, ps, ps.s);
+  if (rc != PRAD_OK) ps.pending.valid = ps.walked.valid = false;
   if (c.timing_accumulate) c.all_times.insert(c.all_times.end(), c.times.begin() + (long)before, c.times.end());
-  return PRAD_OK;
+  return rc;
+}
+// ... both instances (every drain does; the first failure is reported, the other instance is flushed all the same)
+int pipeline_flush(Context &c, const SweepKnobs &kn) {
+  int rc = PRAD_OK;
+  for (int i = 0; i < kPipes; i++) {
+    const int r = pipeline_flush(c, kn, pipe_state(i));
+    if (rc == PRAD_OK) rc = r;
+  }
+  return rc;
 }
 // ... from an entry point that is no GLCM / GLRLM call (join, mark, status, set_device, ...): it reads the switches itself, and
 // only when there is a volume to flush
 int pipeline_flush(Context &c) {
-  PipeState &ps = pipe_state();
-  if (!ps.pending.valid && !ps.walked.valid) return PRAD_OK;
+  if (!pipelines_busy()) return PRAD_OK;
   return pipeline_flush(c, sweep_knobs_from_env());
+}
+// `s` waits (on the device) for what both instances have enqueued on streams of their own
+int pipelines_order(hipStream_t s) {
+  for (int i = 0; i < kPipes; i++) PRAD_TRY(pipeline_order(pipe_state(i), s));
+  return PRAD_OK;
+}
+// the host waits for both instances; afterwards none of their outputs is in flight
+int pipelines_sync() {
+  for (int i = 0; i < kPipes; i++) {
+    PipeState &ps = pipe_state(i);
+    if (ps.s) PRAD_HIP(hipStreamSynchronize(ps.s));
+    ps.outs.clear();
+  }
+  return PRAD_OK;
 }
 
 // one deferred call in pipeline mode; *handled = false: the volume is not a fixed-window one, the caller takes the
 // ordinary deferred route (the pipeline has been drained)
-int pipeline_step(Call &k, const SweepKnobs &kn, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm, bool *handled) {
+int pipeline_step(Call &k, const SweepKnobs &kn, PipeState &ps, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm,
+                  bool *handled) {
   Context &c = *k.c;
-  PipeState &ps = pipe_state();
   *handled = false;
   if (!pipeline_volume(p, glcm != nullptr, glrlm != nullptr)) return pipeline_flush(c, kn);
+  // the instance changes its stream (a twin call behind one that was not, or the reverse; a caller with two streams): the new
+  // stream waits for the old one before anything of this call -- its zeroing included -- is enqueued
+  PRAD_TRY(pipeline_order(ps, k.s));
   VolState v;
   ZeroNeed need;
   PRAD_TRY(vol_prepare(k, kn, p, Ng, Nr, glcm, glrlm, v, &need));
@@ -1007,15 +1103,16 @@ int pipeline_step(Call &k, const SweepKnobs &kn, const SweepPlan &p, int Ng, int
       need.rz_w = need.fl_w = 0;
     }
     PRAD_TRY(launch_zero3(k.s, now));
-    PRAD_TRY(pipeline_retire(c, kn, k.s, pj, true, ride ? &need : nullptr, v.lane));
+    PRAD_TRY(pipeline_retire(c, kn, ps, k.s, pj, true, ride ? &need : nullptr, v.lane));
   } else {
-    PRAD_TRY(pipeline_finish_walked(c, kn, ps.s));   // (a walked volume without a pending one: only after a failed call)
+    PRAD_TRY(pipeline_finish_walked(c, kn, ps, ps.s));   // (a walked volume without a pending one: only after a failed call)
     PRAD_TRY(launch_zero3(k.s, need));
   }
   if (!inl) PRAD_TRY(vol_pack_standalone(k, v));
   v.packed_inline = inl;
   ps.pending = v;
   ps.s = k.s;
+  out_ranges_add(ps, glcm, (size_t)k.Na * Ng * Ng, glrlm, (size_t)k.Na * Ng * Nr);
   *handled = true;
   return PRAD_OK;
 }
@@ -1146,23 +1243,50 @@ int texture_pairs_runs(const int32_t *image, const uint8_t *mask, const int *siz
     ~LaneGuard() { c.lane = -1; }
   } lane_guard{c};
   bool pipe = c.deferred && !voxels && pipeline_mode(kn);
+  const hipStream_t user = s;
   if (c.deferred && !voxels && !pipe) {   // lanes mode: whole-volume deferred calls alternate between lanes
     PRAD_TRY(c.lane_begin(s, &s));
-    if (c.lane >= 0) c.lane += kPipeSets;   // (workspace sets of their own: #0 .. #3 belong to the pipeline)
+    if (c.lane >= 0) c.lane += kAllPipeSets;   // (workspace sets of their own: #0 .. #7 belong to the pipelines)
   }
-  if (pipe) c.lane = (int)(pipe_state().seq++ % (unsigned)kPipeSets);   // pipeline mode: four workspace sets alternate (see the pipeline's header), the stream is the caller's
+  int inst = 0;
+  if (pipe) {
+    // twin: the call goes to one of two pipelines on internal streams (see the pipeline's header); else instance 0 on the caller's stream
+    bool twin = kn.pipe_twin == 1;
+    if (kn.pipe_twin < 0 && size && Nd >= 1 && Nd <= PRAD_MAX_ND) {
+      long long n = 1;
+      for (int d = 0; d < Nd; d++) n *= std::max(size[d], 1);
+      twin = n >= kTwinMinVoxels;
+    }
+    if (twin) {
+      inst = (int)(pipe_shared().twin_calls++ % (unsigned)kPipes);
+      PRAD_TRY(c.twin_streams());
+      PRAD_TRY(c.lane_enter(inst, user, &s));
+    } else {
+      PRAD_TRY(pipeline_flush(c, kn, pipe_state(1)));   // (instance 1 holds volumes of twin calls only)
+    }
+    // an output buffer that the other instance still writes: that instance finishes first, and this call's stream waits for it
+    PipeState &other = pipe_state(1 - inst);
+    if (Na >= 1 && out_ranges_overlap(other, glcm, glcm ? (size_t)Na * Ng * Ng : 0, glrlm, glrlm ? (size_t)Na * Ng * Nr : 0)) {
+      PRAD_TRY(pipeline_flush(c, kn, other));
+      PRAD_TRY(pipeline_order(other, s));
+      other.outs.clear();
+    }
+    PipeState &ps = pipe_state(inst);
+    c.lane = ps.base + (int)(ps.seq++ % (unsigned)kPipeSets);   // four workspace sets of the instance alternate
+  }
   Call k;
   PRAD_TRY(setup_call(k, image, mask, size, Nd, angles, Na, Nvox, voxels, kernelRadius, force2Ddim, s, false));
   SweepPlan p = plan_sweep(k, kn, Ng, Nr, glcm != nullptr, glrlm != nullptr);
   if (pipe && !pipeline_volume(p, glcm != nullptr, glrlm != nullptr)) {
     // Not a volume for the two-stage pipeline (the wrapped-lines kernels): its pack is a launch of its own, so deal the call
     // onto the lanes, where the pack of one volume runs under the walk of the previous one
-    const hipStream_t user = s;
     PRAD_TRY(pipeline_flush(c, kn));
+    PRAD_TRY(pipelines_order(user));   // (twin volumes sit on internal streams: the lane's stream waits for `user`, so for them too)
     pipe = false;
     c.lane = -1;
+    s = user;
     PRAD_TRY(c.lane_begin(user, &s));
-    if (c.lane >= 0) c.lane += kPipeSets;      // (workspace sets of their own: #0 .. #3 belong to the pipeline's alternating volumes)
+    if (c.lane >= 0) c.lane += kAllPipeSets;   // (workspace sets of their own: #0 .. #7 belong to the pipelines' alternating volumes)
     PRAD_TRY(setup_call(k, image, mask, size, Nd, angles, Na, Nvox, voxels, kernelRadius, force2Ddim, s, false));
     p = plan_sweep(k, kn, Ng, Nr, glcm != nullptr, glrlm != nullptr);
   }
@@ -1171,7 +1295,7 @@ int texture_pairs_runs(const int32_t *image, const uint8_t *mask, const int *siz
   bool done = false;
   c.last_variant = !p.ok ? "none" : (p.fw2 ? "fw2" : (p.fw && glcm && glrlm ? "fw" : "lines"));
   if (pipe) {
-    PRAD_TRY(pipeline_step(k, kn, p, Ng, Nr, glcm, glrlm, &done));
+    PRAD_TRY(pipeline_step(k, kn, pipe_state(inst), p, Ng, Nr, glcm, glrlm, &done));
     if (done) c.last_path = "sweep";
   }
   if (!done && p.ok) {
@@ -1732,15 +1856,19 @@ int prad_set_device(int device) {
   if (device < 0 || device >= n) return fail(PRAD_E_ARG, "device %d not in [0,%d)", device, n);
   Context &c = ctx();
   if (c.device != device) {
-    if ((pipe_state().pending.valid || pipe_state().walked.valid) && c.device_set && hipSetDevice(c.device) == hipSuccess) {
-      (void)pipeline_flush(c);   // a volume still pending or walked on the old device: retire it there
-      if (pipe_state().s) (void)hipStreamSynchronize(pipe_state().s);
+    if (pipelines_busy() && c.device_set && hipSetDevice(c.device) == hipSuccess) {
+      (void)pipeline_flush(c);   // volumes still pending or walked on the old device, in either instance: retire them there
+      (void)pipelines_sync();
     }
-    pipe_state().pending.valid = false;
-    pipe_state().walked.valid = false;
+    for (int i = 0; i < kPipes; i++) {
+      PipeState &ps = pipe_state(i);
+      ps.pending.valid = false;
+      ps.walked.valid = false;
+      ps.s = nullptr;
+      ps.ev = nullptr;
+      ps.outs.clear();
+    }
     set_zero_forget();
-    pipe_state().s = nullptr;
-    pipe_state().ev = nullptr;
     c.own_stream = nullptr;  // streams belong to a device; new ones are created lazily
     for (int l = 0; l < PRAD_MAX_LANES; l++) {
       if (c.lane_stream[l]) (void)hipStreamSynchronize(c.lane_stream[l]);
@@ -1764,11 +1892,10 @@ long long prad_workspace_bytes(void) {
 }
 int prad_release_workspace(void) {
   Context &c = ctx();
-  if (pipe_state().pending.valid || pipe_state().walked.valid) {   // their buffers are about to go away: retire them first
+  if (pipelines_busy()) {   // their buffers are about to go away: retire them first, in both instances
     (void)pipeline_flush(c);
-    if (pipe_state().s) (void)hipStreamSynchronize(pipe_state().s);
-    pipe_state().pending.valid = false;
-    pipe_state().walked.valid = false;
+    (void)pipelines_sync();
+    for (int i = 0; i < kPipes; i++) pipe_state(i).pending.valid = pipe_state(i).walked.valid = false;
   }
   set_zero_forget();                      // (what was known to be zero lived in the workspace)
   glszm_state().valid = false;            // its zone list lives in the workspace
@@ -1864,6 +1991,11 @@ int prad_set_deferred(int on) {
 int prad_set_lanes(int n) {
   Context &c = ctx();
   if (n < 0 || n > PRAD_MAX_LANES) return fail(PRAD_E_ARG, "lanes=%d outside [0, %d]", n, PRAD_MAX_LANES);
+  if (pipelines_busy()) {   // (twin volumes share the lanes' streams: nothing of theirs stays behind)
+    PRAD_TRY(c.ensure_device());
+    PRAD_TRY(pipeline_flush(c));
+    PRAD_TRY(pipelines_sync());
+  }
   PRAD_TRY(c.lanes_sync());
   c.lanes = n;          // 0: back to the default (PRAD_LANES or 2) at the next deferred call
   c.lane_seq = 0;
@@ -1873,11 +2005,10 @@ int prad_set_deferred_mode(int mode) {
   if (mode < -1 || mode > 1) return fail(PRAD_E_ARG, "deferred mode %d (0 lanes, 1 pipeline, -1 environment default)", mode);
   Context &c = ctx();
   PRAD_TRY(c.ensure_device());
-  PipeState &ps = pipe_state();
   PRAD_TRY(pipeline_flush(c));
-  if (ps.s) PRAD_HIP(hipStreamSynchronize(ps.s));
+  PRAD_TRY(pipelines_sync());
   PRAD_TRY(c.lanes_sync());
-  ps.mode = mode;
+  pipe_shared().mode = mode;
   return PRAD_OK;
 }
 int prad_set_workspace(int id) {
@@ -1894,13 +2025,8 @@ int prad_result_alloc(size_t bytes, void **out) {
 int prad_deferred_join(void *stream) {
   Context &c = ctx();
   PRAD_TRY(c.ensure_device());
-  PipeState &ps = pipe_state();
   PRAD_TRY(pipeline_flush(c));
-  if (ps.s && ps.s != (hipStream_t)stream) {   // the flushed work sits on the stream of its pack
-    if (!ps.ev) PRAD_HIP(hipEventCreateWithFlags(&ps.ev, hipEventDisableTiming));
-    PRAD_HIP(hipEventRecord(ps.ev, ps.s));
-    PRAD_HIP(hipStreamWaitEvent((hipStream_t)stream, ps.ev, 0));
-  }
+  PRAD_TRY(pipelines_order((hipStream_t)stream));   // the flushed work of either instance sits on the stream of its pack
   return c.lanes_join((hipStream_t)stream);
 }
 int prad_deferred_mark(int *flag, void *stream) {
@@ -1908,6 +2034,7 @@ int prad_deferred_mark(int *flag, void *stream) {
   PRAD_TRY(c.ensure_device());
   if (!flag || !c.in_arena(flag, sizeof(int))) return fail(PRAD_E_ARG, "deferred_mark: flag must lie in the result arena");
   PRAD_TRY(pipeline_flush(c));
+  PRAD_TRY(pipelines_order((hipStream_t)stream));   // the copy of the verdict word stands behind both instances
   int *sticky = nullptr;
   PRAD_TRY(c.get<int>("deferred_sticky", 16, &sticky));
   PRAD_HIP(hipMemcpyAsync(flag, sticky, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -1917,7 +2044,7 @@ int prad_deferred_status(void *stream) {
   Context &c = ctx();
   PRAD_TRY(c.ensure_device());
   PRAD_TRY(pipeline_flush(c));
-  if (pipe_state().s) PRAD_HIP(hipStreamSynchronize(pipe_state().s));
+  PRAD_TRY(pipelines_sync());
   PRAD_HIP(hipStreamSynchronize((hipStream_t)stream));
   PRAD_TRY(c.lanes_sync());
   if (!c.has("deferred_sticky")) return PRAD_OK;  // no deferred call yet

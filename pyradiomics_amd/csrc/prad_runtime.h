@@ -148,14 +148,31 @@ struct Context {
     }
     if (lanes == 1) return PRAD_OK;
     const int l = (int)(lane_seq++ % (unsigned)lanes);
-    if (!lane_stream[l]) {
+    const int rc = lane_enter(l, user, s);
+    if (rc == PRAD_OK) lane = l;
+    return rc;
+  }
+  // internal stream l (created on first use) waits for everything queued on `user` so far; neither `lane` nor the lanes'
+  // round-robin moves (the twin deferred pipelines of prad_api.hip run on streams 0 and 1 and name their workspace sets themselves)
+  int lane_enter(int l, hipStream_t user, hipStream_t *s) {
+    if (!lane_stream[l]) {   // (twin_streams() has created both for the twin pipelines)
       PRAD_HIP(hipStreamCreateWithFlags(&lane_stream[l], hipStreamNonBlocking));
       PRAD_HIP(hipEventCreateWithFlags(&lane_in[l], hipEventDisableTiming));
     }
     PRAD_HIP(hipEventRecord(lane_in[l], user));
     PRAD_HIP(hipStreamWaitEvent(lane_stream[l], lane_in[l], 0));
-    lane = l;
     *s = lane_stream[l];
+    return PRAD_OK;
+  }
+  // streams 0 and 1 created back to back, before the first twin call needs either: the runtime deals hardware queues to streams
+  // in the order of their creation, and two streams that share a queue run their launches one after the other
+  int twin_streams() {
+    for (int l = 0; l < 2; l++)
+      if (!lane_stream[l]) {
+        // (equal priorities: one high and one low stream measured 4 % SLOWER than the single pipeline, profiles/twin_pipeline_measurements.md)
+        PRAD_HIP(hipStreamCreateWithFlags(&lane_stream[l], hipStreamNonBlocking));
+        PRAD_HIP(hipEventCreateWithFlags(&lane_in[l], hipEventDisableTiming));
+      }
     return PRAD_OK;
   }
   // `s` waits (on the device, no host synchronisation) for everything queued on the lanes so far

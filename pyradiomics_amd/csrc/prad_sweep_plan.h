@@ -39,6 +39,8 @@ struct SweepKnobs {
   bool no_inline_pack = false; // PRAD_NO_INLINE_PACK: every pack a launch of its own (baseline)
   bool no_pairs = false;       // PRAD_NO_PAIRS: no pairs tier between the sweeps and the exact kernels (baseline)
   bool lanes_mode = false;     // PRAD_DEFERRED_MODE=lanes
+  int pipe_twin = -1;          // PRAD_PIPE_TWIN: 1 = deal pipeline volumes onto two pipelines on two internal streams, 0 = one
+                               // pipeline on the caller's stream, unset (-1) = by volume size (prad_api.hip kTwinMinVoxels)
 };
 
 inline Knob env_knob(const char *name, bool wide = false) {
@@ -89,6 +91,10 @@ inline SweepKnobs sweep_knobs_from_env() {
   {
     const char *e = getenv("PRAD_DEFERRED_MODE");
     k.lanes_mode = e && strcmp(e, "lanes") == 0;
+  }
+  {
+    const char *e = getenv("PRAD_PIPE_TWIN");
+    k.pipe_twin = (e && e[0] != '\0') ? (atoi(e) != 0 ? 1 : 0) : -1;
   }
   return k;
 }

@@ -147,10 +147,12 @@ def glcm_glrlm(image: torch.Tensor, mask: torch.Tensor, Ng: int, Nr: int | None 
     mode, distance 1.  Returns (glcm, glrlm, angles).  `angles` (int32 [na, Nd]) restricts the sweep to a subset
     of the unidirectional distance-1 angles -- the angle shard of one rank when one segment is spread over
     several GPUs (batch.segment_matrices_sharded); the outputs then carry those na angles only.
-    deferred=True only enqueues the kernels (no host synchronisation; consecutive volumes alternate between the
-    library's two internal streams and share the GPU): the outputs are valid after deferred_status() -- which also
-    reports whether a volume held masked levels outside [1, Ng] -- or, for work queued on the current stream, after
-    deferred_join(); see include/pyradiomics_amd.h."""
+    deferred=True only enqueues the kernels (no host synchronisation; consecutive volumes form a pipeline on the current
+    stream or, large ones, alternate between two pipelines on the library's two internal streams and share the GPU; the
+    current stream does not wait for those): inputs and outputs belong to the library until deferred_status() -- which also
+    reports whether a volume held masked levels outside [1, Ng] -- or deferred_join() returns, after which work queued on the
+    current stream may read the outputs; a volume's outputs are written up to four calls after its own; see
+    include/pyradiomics_amd.h."""
     lib, image, mask, size = _prep(image, mask)
     f2d = int(force2Ddimension) if force2D else -1
     if angles is None:
@@ -310,8 +312,10 @@ def set_lanes(n: int) -> None:
 
 
 def set_deferred_mode(mode: int) -> None:
-    """how deferred whole-volume calls overlap: 1 = two-stage pipeline on the caller's stream (volume N's pack rides in the
-    walk launch of volume N-1; default), 0 = lanes (internal streams), -1 = environment default; flushes pending work"""
+    """how deferred whole-volume calls overlap: 1 = two-stage pipeline (volume N's pack rides in the walk launch of the
+    volume before it; default) -- on the caller's stream, or, for large volumes and under PRAD_PIPE_TWIN=1, dealt alternately
+    onto two such pipelines on two internal streams, so that consecutive walk launches share the GPU --, 0 = lanes (internal
+    streams), -1 = environment default; flushes pending work of both pipelines"""
     _lib.raise_for(_lib.load().prad_set_deferred_mode(int(mode)), "deferred mode")
 
 
