@@ -178,10 +178,10 @@ def test_device_resampling_is_bit_identical_to_the_pinned_numpy_route(interp, dt
         di, dm = imageoperations.resampleImage(Image(arr, spacing), Image(msk, spacing), deviceResident=True, **kw)
         assert di.on_device and di.array.dtype == hi.array.dtype and di.array.shape == hi.array.shape
         assert np.array_equal(dm.array, hm.array) and np.allclose(di.origin, hi.origin) and di.spacing == hi.spacing
-        if interp == "sitkBSpline" and min(shape) == 1 or dtype == np.float32 and interp == "sitkBSpline":
-            np.testing.assert_allclose(di.array, hi.array, rtol=1e-6, atol=1e-4)     # pow() of the short-line sum / f32 cast
-        else:
-            assert np.array_equal(di.array, hi.array), (interp, shape, np.abs(di.array.astype(float) - hi.array).max())
+        # float32 and the (1, 33, 30) slab included: an axis of length 1 is not filtered at all (no pow()), and float32 is one
+        # rounding of the same float64 value on both routes.  tests/test_gpu_resample_limits.py holds both routes to a
+        # long-double reference on these shapes.
+        assert np.array_equal(di.array, hi.array), (interp, shape, np.abs(di.array.astype(float) - hi.array).max())
 
 
 @pytest.mark.gpu
