@@ -195,6 +195,23 @@ __device__ __forceinline__ void lds_bump(int lds_addr) {  // bare ds_add_u32 on 
   __hip_atomic_fetch_add((lds_u32 *)(size_t)(unsigned)lds_addr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// 16-byte accesses to GLOBAL memory through a 64-bit byte address kept as an integer (the pack side jobs of the walks pin their
+// addresses in VGPRs that way).  A plain cast of such an integer to a pointer loses the address space and the access becomes
+// a FLAT one: it is issued to the LDS queue as well, counts in lgkmcnt as well as in vmcnt -- so every wait behind it is a
+// wait for zero, of both counters -- and drains the wave's ds_adds in flight.  NT: non-temporal (streaming) load.
+typedef int g_v4i __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) g_v4i global_v4i;
+template <bool NT = false>
+__device__ __forceinline__ g_v4i global_load16(unsigned long long addr) {
+  const global_v4i *p = (const global_v4i *)addr;
+  return NT ? __builtin_nontemporal_load(p) : *p;
+}
+__device__ __forceinline__ void global_store16(unsigned long long addr, u32 a, u32 b, u32 c, u32 d) {
+  g_v4i v;
+  v.x = (int)a; v.y = (int)b; v.z = (int)c; v.w = (int)d;
+  *(global_v4i *)addr = v;
+}
+
 // Per-line walk state + the branch-free step, separate-table flavour.  All LDS positions are absolute LDS
 // BYTE addresses:  GLCM byte = prev*4Ng + cur*4 + cG,  GLRLM byte = len*4Ng + prev*4 + cR.
 template <bool DO_GLCM, bool DO_GLRLM, bool LONG, bool FUSED>
@@ -926,9 +943,12 @@ __global__ void finalize_glrlm_kernel(const u32 *__restrict__ acc, const int *__
 // exact "some line of the angle holds >= 2 masked voxels", by all threads of one workgroup: a lane per line START (a voxel
 // whose predecessor lies outside the box), enumerated face by face -- the plane z == z0 when dz != 0, then y == y0 without
 // that plane, then x == x0 without both -- so that nobody scans the voxels inside.  Steps go in batches of 8 loads in flight.
+// `hit` is a word of the workgroup's LDS scratch and is named as one: through a generic pointer the volatile accesses to it were
+// the only FLAT operations of the kernels that carry this work.
+typedef __attribute__((address_space(3))) int lds_i32;
 template <typename T>
 __device__ void lines_hold_two(const T *__restrict__ L, int Nz, int Ny, int Nx, int pitch, int dz, int dy, int dx,
-                               volatile int *hit) {
+                               volatile lds_i32 *hit) {
   const int z0 = dz > 0 ? 0 : Nz - 1, y0 = dy > 0 ? 0 : Ny - 1, x0 = dx > 0 ? 0 : Nx - 1;
   const long long NzR = Nz - (dz != 0), NyR = Ny - (dy != 0);
   const long long SZ = dz ? (long long)Ny * Nx : 0, SY = dy ? NzR * Nx : 0, SX = dx ? NzR * NyR : 0;
@@ -1050,7 +1070,7 @@ __device__ __forceinline__ void finalize_angle_work(FinScratch *S, int a, int dz
   __syncthreads();
   int m = S->found;   // uniform: nobody writes it behind the barrier
   if (!m) {   // every masked voxel isolated along the angle (rare): the exact test of multi_check_kernel
-    lines_hold_two<T>(L, Nz, Ny, Nx, pitch, dz, dy, dx, &S->hit);
+    lines_hold_two<T>(L, Nz, Ny, Nx, pitch, dz, dy, dx, (volatile lds_i32 *)&S->hit);
     __syncthreads();
     m = S->hit;
   }

@@ -107,6 +107,12 @@ struct FwSet {
 // its VALU instructions remain (a pure pack kernel of its own takes 0.15 ms per 512^3 volume and cannot share a CU's
 // issue slots with the sweep without slowing it down by as much; packing whole units BETWEEN the chunks of a walk costs
 // twice what the interleaved form does -- a wave that waits for HBM is missed by its SIMD: profiles/r03_probes.md).
+// The unit's five loads and its store are GLOBAL accesses (kernels_sweep.h global_load16 / global_store16).  As flat ones --
+// which a plain cast of the pinned integer addresses made them -- each also took a place in the LDS queue (3.67 M cycles of
+// SQ_LDS_IDX_ACTIVE per 512^3 launch), drained the wave's ds_adds twice per unit (lgkmcnt(0)) and turned the group's counted
+// row waits into one wait for everything, HBM loads included.  What the side job costs now, 512^3 x 32 levels: the launch
+// 0.434 ms against 0.441 with flat accesses; a wave's life 2.3 % longer than in the launch without a pack (3.0 % before):
+// profiles/pack_global_measurements.md.
 // Needs the linear layout (pitch == NX, hence NX % 16 == 0) and 16-byte aligned arrays; n16 == 0: nothing to pack.
 struct PackJob {
   const int *image;
@@ -356,6 +362,7 @@ __device__ __forceinline__ void fw_load(const uint8_t *p, u32 (&v)[KW]) {
 // the loop is at the limit of its scalar registers, and wave-uniform pack state left to the compiler went into SGPRs and
 // pushed loop scalars out -- v_readlane inside the plain groups, the walk alone 7 % slower); the kernel has 50 to spare.
 struct PackWave {
+  // (global memory, all three: they are only ever used through global_load16 / global_store16)
   unsigned long long img, msk, lev;   // this lane's next piece: image + 64 t, mask + 16 t, levels + 16 t (byte addresses)
   unsigned long long step16;          // pieces between two units of this wave
   int units_left;                     // units this wave still owns
@@ -388,12 +395,13 @@ struct PackWave {
     q0 = q1 = q2 = q3 = make_int4(0, 0, 0, 0);
     m = make_uint4(0, 0, 0, 0);
     if (units_left > 1 || lane < last_lanes) {
-      const int4 *im4 = reinterpret_cast<const int4 *>((size_t)img);
-      m = *reinterpret_cast<const uint4 *>((size_t)msk);
-      q0 = im4[0];
-      q1 = im4[1];
-      q2 = im4[2];
-      q3 = im4[3];
+      const g_v4i mv = global_load16(msk), a0 = global_load16(img), a1 = global_load16(img + 16), a2 = global_load16(img + 32),
+                  a3 = global_load16(img + 48);
+      m = make_uint4((u32)mv.x, (u32)mv.y, (u32)mv.z, (u32)mv.w);
+      q0 = make_int4(a0.x, a0.y, a0.z, a0.w);
+      q1 = make_int4(a1.x, a1.y, a1.z, a1.w);
+      q2 = make_int4(a2.x, a2.y, a2.z, a2.w);
+      q3 = make_int4(a3.x, a3.y, a3.z, a3.w);
     }
     loaded = 1;
     pin(loaded);
@@ -478,7 +486,7 @@ struct PackWave {
           J.rowzero[(e0 + 15u) / (unsigned)J.NX] = 1;
         }
       }
-      *reinterpret_cast<uint4 *>((size_t)lev) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
+      global_store16(lev, ow[0], ow[1], ow[2], ow[3]);
     }
     img += 64ull * step16;
     msk += 16ull * step16;
@@ -593,9 +601,13 @@ struct FwWave {
     for (int w = 0; w < KW; w++) P[w] = C[w];
   }
   // U plain steps with renamed registers (no line dead, no run near the end of the table)
-  // pk_late (PRAD_FW_PACK_LATE): the pack unit's loads go out behind the FIRST step of the group instead of in front of the
-  // group, so that the wait for the group's level rows (vmcnt(0): the compiler cannot count across the conditional) does not
-  // also wait for the pack's HBM loads
+  // The group waits for its level rows one at a time (vmcnt(7) ... vmcnt(0), with or without a pack unit's loads behind them:
+  // those are younger than the rows, so a count that lets the rows through never waits for them before the last steps).  Until
+  // the pack's accesses were made global ones (kernels_sweep.h global_load16) they were FLAT, which count in vmcnt AND lgkmcnt
+  // and may return out of order: the only wait the compiler may emit behind one is a wait for zero, and the group with the pack
+  // began with vmcnt(0) -- rows and the unit's HBM loads -- in front of step 0.
+  // pk_late (PRAD_FW_PACK_LATE, an experiment from that time): the pack unit's loads go out behind the FIRST step of the
+  // group instead of in front of the group.  Measured again on the counted waits: profiles/pack_global_measurements.md.
   __device__ __forceinline__ void plain_group(const u32 (&v)[U][KW], PackWave *pk_late = nullptr) {
 #pragma unroll
     for (int k = 0; k < U; k++) {
@@ -679,9 +691,22 @@ struct FwWave {
     for (int j = 0; j < K; j++) a = a || (pl[j] >= T.alive0 && FW_BYTE(X, j) != 0);
     return __ballot(a) != 0;
   }
-  __device__ __forceinline__ void run(const FwDesc &D, int NX, int pitch, long long nrows, const uint8_t *__restrict__ L,
+  template <typename S>
+  static __device__ __forceinline__ S keep_scalar(S x) {
+    asm volatile("" : "+s"(x));
+    return x;
+  }
+  __device__ __forceinline__ void run(const FwDesc &Dk, int NX, int pitch, long long nrows, const uint8_t *__restrict__ L,
                                       const uint8_t *__restrict__ rowzero, bool anyzero, int *work, int bx, int nblocks,
                                       PackWave &pk, const PackJob &pj, bool xcd, FwClock &clk) {
+    // The role's constants, read ONCE from the kernel-argument segment and made opaque: left to itself the compiler reloads
+    // them (s_load + s_waitcnt lgkmcnt(0): a drain of the ds_adds in flight) at every chunk set-up and on the slow single-step
+    // path instead of keeping them in the lanes of the SGPR spill registers the kernel has anyway (v_readlane: no counter).
+    FwDesc D;
+    D.slot = Dk.slot;
+    D.NM = keep_scalar(Dk.NM); D.NU = keep_scalar(Dk.NU); D.du = keep_scalar(Dk.du); D.dx = Dk.dx;
+    D.sM = keep_scalar(Dk.sM); D.sU = keep_scalar(Dk.sU);
+    D.CL = keep_scalar(Dk.CL); D.pieces = keep_scalar(Dk.pieces); D.chunks = keep_scalar(Dk.chunks); D.dom_kind = keep_scalar(Dk.dom_kind);
     const int NM = D.NM, NU = D.NU, du = D.du;
     const long long delta = D.sM + (long long)du * D.sU;
     // row numbers of the packed volume (rowzero[r] != 0: row r holds a voxel outside the ROI), wave-uniform like `off`

@@ -193,6 +193,7 @@ __device__ __forceinline__ void fw2_make_x(const u32 (&P)[K / 2], u32 (&X)[K / 2
 // mask bytes of its piece into 16 16-bit elements (level*4: two 16-byte stores into J.levels16) and, when J.levels != NULL, 16
 // plain level bytes (one 16-byte store: only plans whose x angle still takes the rows kernel of kernels_sweep.h read them).  Needs the linear layouts (pitch16 == 2 NX, pitch == NX: NX % 16 == 0)
 // and 16-byte aligned arrays.  Same results as pack_levels16_kernel for every input (tests/test_gpu_fw2_pack.py).
+// Loads and stores are GLOBAL accesses (kernels_sweep.h global_load16 / global_store16; PackJob has what the flat ones cost).
 struct PackWave16 {
   unsigned long long img, msk;   // this lane's next piece: image + 64 t, mask + 16 t (byte addresses)
   unsigned long long step16;     // pieces between two units of this wave
@@ -225,26 +226,18 @@ struct PackWave16 {
     q0 = q1 = q2 = q3 = make_int4(0, 0, 0, 0);
     m = make_uint4(0, 0, 0, 0);
     if (units_left > 1 || lane < last_lanes) {
-      const int4 *im4 = reinterpret_cast<const int4 *>((size_t)img);
 #ifdef PRAD_PACK16_NT     // A/B build: the image and the mask stream past the caches the walk's re-reads live in
-      typedef int v4i __attribute__((ext_vector_type(4)));
-      const v4i *iv = reinterpret_cast<const v4i *>((size_t)img);
-      const v4i mv = __builtin_nontemporal_load(reinterpret_cast<const v4i *>((size_t)msk));
-      const v4i a0 = __builtin_nontemporal_load(iv), a1 = __builtin_nontemporal_load(iv + 1),
-                a2 = __builtin_nontemporal_load(iv + 2), a3 = __builtin_nontemporal_load(iv + 3);
+      constexpr bool NT = true;
+#else
+      constexpr bool NT = false;
+#endif
+      const g_v4i mv = global_load16<NT>(msk), a0 = global_load16<NT>(img), a1 = global_load16<NT>(img + 16),
+                  a2 = global_load16<NT>(img + 32), a3 = global_load16<NT>(img + 48);
       m = make_uint4((u32)mv.x, (u32)mv.y, (u32)mv.z, (u32)mv.w);
       q0 = make_int4(a0.x, a0.y, a0.z, a0.w);
       q1 = make_int4(a1.x, a1.y, a1.z, a1.w);
       q2 = make_int4(a2.x, a2.y, a2.z, a2.w);
       q3 = make_int4(a3.x, a3.y, a3.z, a3.w);
-      (void)im4;
-#else
-      m = *reinterpret_cast<const uint4 *>((size_t)msk);
-      q0 = im4[0];
-      q1 = im4[1];
-      q2 = im4[2];
-      q3 = im4[3];
-#endif
     }
     loaded = 1;
     pin(loaded);
@@ -318,10 +311,10 @@ struct PackWave16 {
           o8[b >> 2] |= el << (8 * (b & 3));
         }
       }
-      uint4 *d16 = reinterpret_cast<uint4 *>(J.levels16 + 2ull * e);
-      d16[0] = make_uint4(o16[0], o16[1], o16[2], o16[3]);
-      d16[1] = make_uint4(o16[4], o16[5], o16[6], o16[7]);
-      if (want8) *reinterpret_cast<uint4 *>(J.levels + e) = make_uint4(o8[0], o8[1], o8[2], o8[3]);
+      const unsigned long long d16 = (unsigned long long)(size_t)J.levels16 + 2ull * e;
+      global_store16(d16, o16[0], o16[1], o16[2], o16[3]);
+      global_store16(d16 + 16, o16[4], o16[5], o16[6], o16[7]);
+      if (want8) global_store16((unsigned long long)(size_t)J.levels + e, o8[0], o8[1], o8[2], o8[3]);
     }
     img += 64ull * step16;
     msk += 16ull * step16;
