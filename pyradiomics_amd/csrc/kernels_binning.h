@@ -196,7 +196,9 @@ __global__ void __launch_bounds__(256) digitize_kernel(const T *__restrict__ x, 
 // binCount edges on the device: np.histogram(x, bins=N)[1] is np.linspace(min, max, N + 1) --
 // step = (max - min) / N, edge_i = i * step + min (two roundings, no fused multiply-add), edge_N = max -- and
 // getBinEdges moves the last edge up by 1 (imageoperations.py:122-126).  info[0] = 1 when the ROI is constant / not finite /
-// the step underflows (np.histogram and np.linspace then take other branches: the host route handles those).
+// the step underflows (np.histogram and np.linspace then take other branches: the host route handles those), or two
+// neighbouring edges are not strictly ascending (a range of a few ulps cut into many bins: np.histogram refuses such edges where
+// it checks them, so the installed NumPy decides on the host route).
 // F32: a float32 image -- numpy then does all of it in float32 (np.histogram's bin_type, np.linspace's dt); integer images take the
 // float64 arithmetic on their exact extremes.
 template <bool F32>
@@ -209,6 +211,14 @@ __global__ void bincount_edges_kernel(const unsigned long long *__restrict__ key
     const float lof = (float)lo, hif = (float)hi;
     const float delta = hif - lof, step = delta / (float)N;
     bad = bad || !isfinite(delta) || step == 0.0f;
+    int tie = 0;
+    for (int i = threadIdx.x; i < N && !bad; i += blockDim.x) {
+      float e = (float)i * step, e2 = (float)(i + 1) * step;
+      e = e + lof;
+      e2 = i + 1 == N ? hif : e2 + lof;
+      tie |= e >= e2;
+    }
+    bad = __syncthreads_or(tie) || bad;
     if (threadIdx.x == 0) info[0] = bad ? 1 : 0;
     for (int i = threadIdx.x; i <= N; i += blockDim.x) {
       float e = (float)i * step;
@@ -219,6 +229,14 @@ __global__ void bincount_edges_kernel(const unsigned long long *__restrict__ key
   } else {
     const double delta = hi - lo, step = delta / (double)N;
     bad = bad || !isfinite(delta) || step == 0.0;
+    int tie = 0;
+    for (int i = threadIdx.x; i < N && !bad; i += blockDim.x) {
+      double e = (double)i * step, e2 = (double)(i + 1) * step;
+      e = e + lo;
+      e2 = i + 1 == N ? hi : e2 + lo;
+      tie |= e >= e2;
+    }
+    bad = __syncthreads_or(tie) || bad;
     if (threadIdx.x == 0) info[0] = bad ? 1 : 0;
     for (int i = threadIdx.x; i <= N; i += blockDim.x) {
       double e = (double)i * step;

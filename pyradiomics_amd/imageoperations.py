@@ -40,6 +40,10 @@ def getBinEdges(parameterValues, **kwargs):
         return edges
     lo = min(values)
     hi = max(values)
+    if values.dtype.kind in "biu":
+        # NumPy scalars of an integer pixel type wrap in `hi + 2 * binWidth` (uint8 250 + 50 -> 44) and in `lo - lo % binWidth`
+        # (int16 -32768): Python integers give the same edges wherever nothing wraps, and the intended ones where it does
+        lo, hi = int(lo), int(hi)
     first = lo - (lo % binWidth)
     edges = np.arange(first, hi + 2 * binWidth, binWidth)
     if len(edges) == 1:
