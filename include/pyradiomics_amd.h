@@ -215,6 +215,41 @@ int prad_build_angles(const int *size, const int *distances, int Nd, int Ndist, 
 int prad_debug_sweep_plan(const int *size, int Nd, const int *angles, int Na, int Ng, int Nr, int want_glcm, int want_glrlm,
                           int cus, int *out, int cap);
 
+/* ---- debug: the launches the deferred GLCM + GLRLM pipeline plans for a script of events (no device call, no launch) ----
+ * Replays `nevents` events through a FRESH planner (csrc/prad_pipe_plan.h), not the calling thread's live one, as the
+ * executor runs deferred calls through its own.  Writes one record of 13 ints per planned launch to out[0 .. cap) and returns
+ * how many ints it wrote; -(the count needed) when cap is too small; 0 when nothing is launched or for NULL arguments.
+ * An event is 14 int64:
+ *   [0]  type            0 a flush (prad_deferred_join / _status / _mark), 1 a deferred whole-volume call,
+ *                        2 the workspace is released (a flush, then nothing is known to be zero any more),
+ *                        3 a deferred call that fails behind the choice of its set (arguments no call accepts): it takes a set
+ *                          (reads [1], [5], [13] as a call does) and launches nothing of its own
+ *   [9]  fin_ride        the switch PRAD_FIN_RIDE as the call or the flush reads it (0 / 1)      -- every type; the rest: calls
+ *   [1]  voxels          of the volume (automatic twin from 2^27)
+ *   [2]  rows            Nz * Ny: a fused-table volume uses (rows + 3) / 4 words of row flags, a two-table volume none
+ *   [3]  acc_words       accumulators + control words of the volume
+ *   [4]  kind            0 fused table, 1 two tables, 2 a volume the pipeline does not take (both instances are flushed)
+ *   [5]  twin            the switch PRAD_PIPE_TWIN: 1, 0, or -1 = by the voxel count
+ *   [6]  stream          the caller's stream, any id (a twin call runs on the instance's internal stream instead)
+ *   [7]  rz_id  [8] rz_cap   the row-flag buffer the volume's set has at this call: an opaque non-zero id and its capacity in
+ *                        bytes (the caller of the replay decides when the buffer "grows" or is allocated anew)
+ *   [10] can_ride        the volume's finalize can ride in a walk launch (plan, PRAD_FINALIZE_ONE, PRAD_FW_XROLE: fin_can_ride)
+ *   [11] host_plan_ok    the volume's walk launch can carry a riding job as far as its plan goes (fin_host_ok)
+ *   [12] pack_inline_ok  the volume's pack can ride in a walk launch of its kind (pack_inline_ok, PRAD_NO_INLINE_PACK)
+ *   [13] outs_overlap    the call's outputs overlap outputs the other instance has in flight (it is flushed first)
+ * A record:
+ *   event                index of the event that launches it
+ *   kind                 0 zero3_kernel, 1 a stand-alone finalize, 2 a walk launch, 3 a stand-alone pack
+ *   instance             0 / 1
+ *   walk  pack  fin      workspace sets (-1: none).  walk launch: the set it walks, the set whose pack rides in it, the set
+ *                        whose finalize rides in it; finalize / pack launch: the set it finishes / packs
+ *   job                  walk launch: 1 if it may carry a riding job at all
+ *   acc_set acc_words  rz_set rz_words  fl_set fl_words
+ *                        the word ranges (accumulators + control words, row flags, flag words; set -1: none) that a
+ *                        zero3_kernel launch zeroes, or that the riding job of a walk launch zeroes
+ * (word counts are narrowed to int.)  tests/test_pipe_plan.py checks these records against a model of the workspace. */
+int prad_debug_pipe_plan(const long long *events, int nevents, int *out, int cap);
+
 /* ---- GLCM: calculate_glcm (cmatrices.c:4-92) ---------------------------------------------------- */
 /* glcm: float64 [Nvox][Ng][Ng][Na] */
 int prad_calculate_glcm(const int32_t *image, const uint8_t *mask, const int *size, int Nd,

@@ -132,7 +132,7 @@ struct PackJob {
 // walks in the pipeline); an empty job (no zero words, Na == 0) costs a few scalar compares.  Three parts,
 // none of which reads anything another workgroup of the same launch writes:
 //   zero     up to three word ranges, stores only, dealt over all threads of the line workgroups.  The host names only words
-//            that no workgroup of THIS launch reads or writes otherwise (prad_api.hip, "workspace sets").
+//            that no workgroup of THIS launch reads or writes otherwise (prad_pipe_plan.h pipe_step, "workspace sets").
 //   convert  the element-wise part of finalize_volume_kernel for volume N-2 (run counts without column r == 0, off-diagonal
 //            pair counts -> float64), dealt over the same threads; a thread's first load goes out in front of the LDS
 //            zero-init of its workgroup and is stored behind it.

@@ -21,6 +21,7 @@
 #include "kernels_mcc.h"
 #include "kernels_voxtex.h"
 #include "prad_sweep_plan.h"
+#include "prad_pipe_plan.h"
 #include "prad_internal.h"
 
 #include <algorithm>
@@ -431,68 +432,11 @@ __global__ void __launch_bounds__(256) zero3_kernel(u32 *__restrict__ a, size_t 
   for (size_t i = t; i < nc; i += nt) c3[i] = 0;
 }
 
-// One packed volume between its pack and its finalize: device pointers of ONE workspace set (Context::lane) and the plan.
-struct VolState {
-  bool valid = false;
-  SweepPlan p;
-  int Ng = 0, Nr = 0, Na = 0;
-  double *glcm = nullptr, *glrlm = nullptr;   // outputs (device), either may be NULL
-  uint8_t *levels = nullptr, *rowzero = nullptr;
-  uint8_t *levels16 = nullptr;   // 16-bit level*4 elements (two-table fixed-window kernel)
-  u32 *acc = nullptr, *glcm_acc = nullptr, *glrlm_acc = nullptr;
-  int *multi = nullptr;
-  int *flags_d = nullptr;
-  bool packed_inline = false;   // the pack rides in the previous volume's sweep launch (PackJob)
-  int lane = -1;                // workspace set of the volume (pipeline mode)
-};
+#include "prad_pipeline.h"   // VolState, ZeroNeed, launch_zero3 and the deferred pipeline
 
-// PRAD_FIN_RIDE=0: the finalize of a pipeline volume as a launch of its own behind its walk launch, and zero3_kernel in front of
-// every pack (A/B, and the checker of the riding job); the knob record is read afresh on every call and every flush so that a
-// test can flip it
-bool fin_ride(const SweepKnobs &kn) { return kn.fin_ride; }
-
-// What a volume needs zeroed: accumulators + control words (before its WALKS), row flags and flag words (before its PACK).
-struct ZeroNeed {
-  u32 *acc = nullptr, *rz = nullptr, *fl = nullptr;
-  size_t acc_w = 0, rz_w = 0, fl_w = 0;
-};
-// What is known about the row flags and the flag words of one of the pipeline's workspace sets.  A walk launch that carries a
-// FinJob re-zeroes what the set's last occupant used; the next occupant then launches no zero3_kernel if it needs no more than
-// that and the buffers are still the same allocations.
-struct SetZero {
-  u32 *rz = nullptr, *fl = nullptr;
-  size_t rz_cap = 0;       // capacity of the row-flag allocation the record describes (a reallocation always grows it)
-  size_t rz_used = 0;      // words the last occupant's pack may have written
-  size_t rz_zero = 0;      // leading words known to be zero
-  bool fl_zero = false;
-};
-constexpr int kPipeSets = 4;   // workspace sets of ONE pipeline: packed, walked, being finalized, and one that is re-zeroed
-constexpr int kPipes = 2;      // pipeline instances (twin: volumes are dealt alternately onto both); instance p owns sets p * kPipeSets ...
-constexpr int kAllPipeSets = kPipes * kPipeSets;   // (the lanes' sets lie behind them)
-inline bool pipe_set(int lane) { return lane >= 0 && lane < kAllPipeSets; }
-inline int next_pipe_set(int lane) { return lane - lane % kPipeSets + (lane + 1) % kPipeSets; }   // the next set of the same instance
-SetZero *set_zero_book() {
-  static thread_local SetZero book[kAllPipeSets];
-  return book;
-}
-void set_zero_forget() {
-  for (int i = 0; i < kAllPipeSets; i++) set_zero_book()[i] = SetZero();
-}
-int launch_zero3(hipStream_t s, const ZeroNeed &z) {
-  const size_t total_w = z.acc_w + z.rz_w + z.fl_w;
-  if (total_w == 0) return PRAD_OK;
-  const unsigned gx = (unsigned)std::max<size_t>(1, std::min<size_t>((total_w / 4 + 255) / 256, 1024));
-  hipLaunchKernelGGL(zero3_kernel, dim3(gx), dim3(256), 0, s, z.acc, z.acc_w, z.rz, z.rz_w, z.fl, z.fl_w);
-  return check_launch("zero3_kernel");
-}
-
-// workspace of a volume + the zeroing that must precede its pack and its sweeps.  `defer`: the caller launches (or lets a walk
-// launch carry) what *defer names; without it the volume's zero3_kernel is launched here.
-int vol_prepare(Call &k, const SweepKnobs &kn, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm, VolState &v,
-                ZeroNeed *defer = nullptr) {
+// workspace of a volume (the set Context::lane) and, in z, what must be zero before its pack and its sweeps
+int vol_prepare(Call &k, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm, VolState &v, ZeroNeed &z) {
   Context &c = *k.c;
-  v.lane = c.lane;
-  v.valid = true;
   v.p = p;
   v.Ng = Ng;
   v.Nr = Nr;
@@ -521,75 +465,14 @@ int vol_prepare(Call &k, const SweepKnobs &kn, const SweepPlan &p, int Ng, int N
   v.multi = (int *)(v.acc + nglcm + nglrlm);
   v.rowzero = nullptr;
   if (p.fw) PRAD_TRY(c.get<uint8_t>("rowzero", (size_t)nrows + 64, &v.rowzero));
-  // accumulators + control words, row flags and the volume's flag words start from zero: ONE launch
-  // (three hipMemsetAsync calls are three launches, each with its dependent-launch gap on the stream)
-  ZeroNeed z;
-  z.acc = v.acc;
-  z.acc_w = nglcm + nglrlm + nctl;
-  z.rz = reinterpret_cast<u32 *>(v.rowzero);
-  z.rz_w = v.rowzero ? ((size_t)nrows + 3) / 4 : 0;
-  z.fl = reinterpret_cast<u32 *>(v.flags_d);
-  z.fl_w = 4;
-  if (pipe_set(c.lane)) {   // a set of a pipeline: what an earlier walk launch re-zeroed need not be zeroed again
-    SetZero &S = set_zero_book()[c.lane];
-    const size_t cap = v.rowzero ? c.bufs[c.key("rowzero")].cap : 0;
-    if (fin_ride(kn)) {
-      if (S.rz == z.rz && S.rz_cap == cap && z.rz_w <= S.rz_zero) z.rz_w = 0;
-      if (S.fl == z.fl && S.fl_zero) z.fl_w = 0;
-    }
-    S.rz = z.rz;       // the set is this volume's now: its pack dirties both
-    S.rz_cap = cap;
-    S.rz_used = v.rowzero ? ((size_t)nrows + 3) / 4 : 0;
-    S.rz_zero = 0;
-    S.fl = z.fl;
-    S.fl_zero = false;
-  }
-  if (defer) {
-    *defer = z;
-    return PRAD_OK;
-  }
-  return launch_zero3(k.s, z);
-}
-
-// can this volume's pack ride in another volume's sweep launch?  (linear layout, vector loads)
-bool pipeline_volume(const SweepPlan &p, bool glcm, bool glrlm) {   // a volume the two-stage deferred pipeline takes
-  if (!(p.ok && p.lines.count > 0 && glcm && glrlm)) return false;
-  return (p.fw && p.fused) || p.fw2;
-}
-bool pack_inline_ok(const Call &k, const VolState &v) {
-  if (!(v.glcm && v.glrlm && v.p.pitch == v.p.Nx && v.p.padw == 0 && (k.g.n % 16) == 0 &&
-        ((((uintptr_t)k.image) | ((uintptr_t)k.mask) | ((uintptr_t)v.levels)) & 15) == 0))
-    return false;
-  // (PackWave16 keeps its piece's voxel index in 32 bits, PackWave its row-flag index: side-job packs stay below 2^31 voxels --
-  //  ADVICE r5; a larger volume packs in a launch of its own)
-  if (k.g.n >= (1LL << 31)) return false;
-  if (v.p.fw2) return v.levels16 && v.p.pitch16 == 2 * v.p.Nx && (((uintptr_t)v.levels16) & 15) == 0;
-  return v.p.fw && v.p.fused;
-}
-
-PackJob make_pack_job(const Call &k, const SweepKnobs &kn, const VolState &v, const VolState *host) {
-  PackJob j;
-  memset(&j, 0, sizeof(j));
-  j.image = k.image;
-  j.mask = k.mask;
-  j.levels = v.levels;
-  j.levels16 = v.p.fw2 ? v.levels16 : nullptr;
-  j.rowzero = v.rowzero;
-  j.flags = v.flags_d;
-  j.n16 = k.g.n / 16;
-  j.NX = v.p.Nx;
-  j.Ng = v.Ng;
-  // cadence: spread a wave's units over the plain groups of its walk (both per wave); what is left drains behind the walk
-  double groups = 0;
-  if (host)
-    for (int i = 0; i < host->p.fwset.count; i++) groups += (double)host->p.fwset.d[i].NM * host->p.fwset.d[i].NU / PRAD_FW_U;
-  const double units = (double)j.n16 / 64.0;
-  // (two-table walk: a unit every 3rd group instead of every 2nd at 512^3 -- 0.707 -> 0.698 ms per volume, smooth inside its run-to-run spread of 0.75 - 0.78;
-  //  the fused-table walk measures best at 2: 0.490 against 0.496 at 3, profiles/r05b_probes.md)
-  const double slack = v.p.fw2 ? 1.05 : 0.92;
-  j.every = (int)std::max(1.0, std::min(64.0, std::floor(slack * groups / std::max(1.0, units))));
-  if (kn.pack_every.set) j.every = std::max(1, (int)kn.pack_every.v);
-  return j;
+  // accumulators + control words, row flags and the volume's flag words start from zero
+  z.p[kZeroAcc] = v.acc;
+  z.w[kZeroAcc] = nglcm + nglrlm + nctl;
+  z.p[kZeroRz] = reinterpret_cast<u32 *>(v.rowzero);
+  z.w[kZeroRz] = v.rowzero ? ((size_t)nrows + 3) / 4 : 0;
+  z.p[kZeroFl] = reinterpret_cast<u32 *>(v.flags_d);
+  z.w[kZeroFl] = kFlagWords;
+  return PRAD_OK;
 }
 
 int vol_pack_standalone(Call &k, VolState &v) {
@@ -657,7 +540,6 @@ int launch_sweeps(Call &k, const SweepKnobs &kn, const VolState &v, const PackJo
 }
 
 // the sweeps of volume v; `pj` (n16 > 0) = the pack of another volume as a side job of the fixed-window launch
-bool fin_job_empty(const FinJob &fj);
 int vol_sweep(Call &k, const SweepKnobs &kn, const VolState &v, const PackJob &pj, const FinJob &fj) {
   if (pj.n16 > 0 && !pipeline_volume(v.p, v.glcm != nullptr, v.glrlm != nullptr))
     return fail(PRAD_E_ARG, "internal: a pack job needs a fixed-window host launch");
@@ -691,10 +573,6 @@ int latch_neigh(Context &c, Call &k) {
   return check_launch("latch_any_flag_kernel");
 }
 
-// PRAD_FINALIZE_ONE=0: the three finalize launches of a GLCM + GLRLM volume instead of finalize_volume_kernel (A/B, and the
-// checker of that kernel); like fin_ride(), from the knob record that every call and every flush reads afresh
-bool finalize_one(const SweepKnobs &kn) { return kn.finalize_one; }
-
 // u32 accumulators -> float64 matrices in the reference layouts; `sticky` (deferred calls): latch the levels verdict
 int vol_finalize(Call &k, const SweepKnobs &kn, const VolState &v, int *sticky) {
   Context &c = *k.c;
@@ -709,7 +587,7 @@ int vol_finalize(Call &k, const SweepKnobs &kn, const VolState &v, int *sticky) 
     // matrices and the x angle's complete run table (plans with skip1 always carry them: plan_sweep clears the flag otherwise)
     if (p.fw2 && p.skip1 && p.lines.count > 0 && !(glcm && glrlm && p.row_slot >= 0))
       return fail(PRAD_E_UNSUPPORTED, "sweep plan derives runs of length 1 but the call cannot restore them");
-    if (glcm && glrlm && runs_diag && finalize_one(kn) && (long long)Ng * Nr < (1LL << 30)) {
+    if (glcm && glrlm && runs_diag && kn.finalize_one && (long long)Ng * Nr < (1LL << 30)) {
       // ONE launch (finalize_volume_kernel): Na angle workgroups, then the two element-wise conversions
       const int nbR = (int)blocks_for((long long)Ng * Nr * Na, 1024), nbG = (int)blocks_for((long long)Ng * Ng * Na, 1024);
       const int restore_from = (p.fw2 && p.skip1 && p.lines.count > 0) ? p.row_slot : -1;
@@ -767,7 +645,9 @@ int vol_finalize(Call &k, const SweepKnobs &kn, const VolState &v, int *sticky) 
 int sweep_glcm_glrlm(Call &k, const SweepKnobs &kn, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm, bool *used) {
   Context &c = *k.c;
   VolState v;
-  PRAD_TRY(vol_prepare(k, kn, p, Ng, Nr, glcm, glrlm, v));
+  ZeroNeed z;
+  PRAD_TRY(vol_prepare(k, p, Ng, Nr, glcm, glrlm, v, z));
+  PRAD_TRY(launch_zero3(k.s, z));
   PRAD_TRY(vol_pack_standalone(k, v));
   PackJob pj;
   memset(&pj, 0, sizeof(pj));
@@ -783,337 +663,6 @@ int sweep_glcm_glrlm(Call &k, const SweepKnobs &kn, const SweepPlan &p, int Ng, 
   // flags[2]: the fused walker found its table away from LDS address 0 and did nothing (cannot happen with the current
   // toolchain: the dynamic array is the kernels' only LDS object) -- let the generic kernels redo the call
   *used = (k.flags_h[0] == 0 && k.flags_h[2] == 0);
-  return PRAD_OK;
-}
-
-// ---- deferred calls as a pipeline (the default deferred mode; PRAD_DEFERRED_MODE=lanes selects the lanes) ----------------
-// A deferred whole-volume call N launches { walks of volume N-1 + pack of volume N } as ONE fixed-window launch (the pack
-// is a side job of the walking waves: kernels_sweepfw.h PackJob).  Volume N itself stays PENDING (packed, not yet walked) until
-// the next deferred call or until prad_deferred_status / prad_deferred_join / prad_deferred_mark flush it.
-//
-// Fused-table volumes (<= 44 levels) go one stage further: volume N-1 is not finalized behind its walk launch but stays WALKED,
-// and the NEXT walk launch -- the one of call N+1, which walks N and packs N+1 -- carries its finalize and the zeroing for the
-// volumes to come as a riding job (FinJob), so a steady step is ONE launch: no zero3_kernel, no finalize_volume_kernel.  The
-// job rides only in a fused-table launch on the same stream; otherwise (a two-table volume, another stream,
-// PRAD_FW_XROLE=0, PRAD_FINALIZE_ONE=0, PRAD_FIN_RIDE=0, any flush) the stand-alone finalize of the walked volume is launched
-// FIRST, as before.  Every path that drains the pipeline (pipeline_flush) finishes the walked volume too, so the contract is
-// unchanged: outputs are valid after prad_deferred_status, prad_deferred_join or a mark.  The two-table route (45 - 160 levels)
-// is untouched: its volumes are finalized behind their walk launch.
-//
-// Workspace sets.  Three volumes are in flight -- packed, walked, being finalized (whose LEVELS the rare exact test reads) -- so
-// FOUR sets alternate (Context::lane = base + seq % 4; the stream is the caller's, or the instance's own: "Twin" below).  Launch N walks N-1 (set N-1), packs N (set N),
-// finalizes N-2 (set N-2) and zeroes
-//   * the accumulators and control words of set N: used by the walks of N in launch N+1, last read by the finalize of N-4;
-//   * the row flags and the four flag words of set N+1 = set N-3: written by the pack of N+1 in launch N+1, last read in
-//     launches N-2 (row flags, walks of N-3) and N-1 (flag words, finalize of N-3).
-// INVARIANT: no launch contains a word that one workgroup zeroes and any other workgroup of that launch reads or writes.
-// It holds by construction: make_fin_job names a range only after comparing its SET with the sets of the three volumes the
-// launch works on, and everything earlier is ordered by the stream.  A set remembers what is known to be zero (SetZero):
-// vol_prepare launches zero3_kernel only for the rest (the first volumes of a run, a grown buffer, more rows than were re-zeroed).
-//
-// Twin (PRAD_PIPE_TWIN; automatic from kTwinMinVoxels voxels).  All of the above is ONE instance (PipeState).  There are two per
-// thread.  A twin call n -- n counts the twin calls of the thread -- goes to instance n % 2, which runs on internal stream n % 2
-// (Context::lane_stream; the stream first waits for an event recorded on the caller's stream at the call) and owns the workspace
-// sets (n % 2) * 4 ... + 3.  Its launch { walk n-2, pack n, finalize n-4, zeroing } depends on launch n-2 only, so launches n and
-// n+1 are unordered on the device and the line workgroups of n+1 take the CUs that come free at the uneven end of n.  "N-1" above
-// reads "the instance's previous call".  The sets of the two instances are disjoint, no launch names a set of the other instance
-// (make_fin_job and vol_prepare stay inside next_pipe_set's instance), so the INVARIANT holds per instance, by construction, and
-// across instances there is nothing shared to order -- except
-//   * the sticky verdict word, which every writer only ever SETS (the finalize kernels, the latch kernels); only
-//     prad_deferred_status clears it, after it has synchronised both streams;
-//   * output buffers a caller hands to calls on BOTH instances: each instance remembers the output ranges of what it has in flight
-//     (PipeState::outs); a call whose outputs overlap a range of the other instance first flushes that instance and lets its own
-//     stream wait for it (an event), so the later call's values stand last, as on one stream.
-// A call that is not twin runs on instance 0 on the caller's stream, as ever; a change of kind is a change of the instance's
-// stream, which pipeline_step orders with an event.  Every drain (join, status, mark, mode / lanes / device changes, workspace
-// release, a volume the pipeline does not take) covers both instances.
-// automatic twin from this many voxels (512^3): the smallest size of the sweep 128^3 ... 512^3 from which twin was faster in EVERY
-// pair; the smaller sizes gained more on average (26 % at 128^3) but one pair of eight at 384^3 was slower
-// (profiles/twin_pipeline_measurements.md section 3).  Never below 2^21: tests count the launches of the single pipeline on small volumes.
-constexpr long long kTwinMinVoxels = 1LL << 27;
-struct OutRange {
-  const char *lo, *hi;
-};
-struct PipeState {
-  VolState pending;
-  VolState walked;              // walked, not finalized: its finalize rides in the next walk launch or runs stand-alone first
-  hipStream_t s = nullptr;      // stream the pending volume's pack was enqueued on
-  unsigned long long seq = 0;
-  hipEvent_t ev = nullptr;
-  int base = 0;                 // first workspace set of the instance
-  std::vector<OutRange> outs;   // outputs of calls enqueued since the instance was last waited for by the host or by the other one
-};
-struct PipeShared {
-  int mode = -1;                // 1 pipeline, 0 lanes
-  unsigned long long twin_calls = 0;
-};
-PipeState &pipe_state(int i) {
-  static thread_local PipeState p[kPipes];
-  p[i].base = i * kPipeSets;
-  return p[i];
-}
-PipeShared &pipe_shared() {
-  static thread_local PipeShared p;
-  return p;
-}
-bool pipeline_mode(const SweepKnobs &kn) {
-  PipeShared &ps = pipe_shared();
-  if (ps.mode < 0) ps.mode = kn.lanes_mode ? 0 : 1;
-  return ps.mode == 1;
-}
-bool pipelines_busy() {
-  for (int i = 0; i < kPipes; i++)
-    if (pipe_state(i).pending.valid || pipe_state(i).walked.valid) return true;
-  return false;
-}
-// `s` waits (on the device) for everything the instance has enqueued on a stream of its own
-int pipeline_order(PipeState &ps, hipStream_t s) {
-  if (!ps.s || ps.s == s) return PRAD_OK;
-  if (!ps.ev) PRAD_HIP(hipEventCreateWithFlags(&ps.ev, hipEventDisableTiming));
-  PRAD_HIP(hipEventRecord(ps.ev, ps.s));
-  PRAD_HIP(hipStreamWaitEvent(s, ps.ev, 0));
-  return PRAD_OK;
-}
-void out_ranges_add(PipeState &ps, const double *glcm, size_t nglcm, const double *glrlm, size_t nglrlm) {
-  const OutRange r[2] = {{(const char *)glcm, (const char *)(glcm + nglcm)}, {(const char *)glrlm, (const char *)(glrlm + nglrlm)}};
-  for (int i = 0; i < 2; i++) {
-    if (!r[i].lo) continue;
-    bool known = false;
-    for (OutRange &o : ps.outs)
-      if (o.lo <= r[i].lo && r[i].hi <= o.hi) known = true;
-    if (known) continue;
-    if (ps.outs.size() >= 64) {   // (a caller with ever new buffers: one range that covers them all -- overlaps may be reported that are none)
-      for (const OutRange &o : ps.outs) {
-        ps.outs[0].lo = std::min(ps.outs[0].lo, o.lo);
-        ps.outs[0].hi = std::max(ps.outs[0].hi, o.hi);
-      }
-      ps.outs.resize(1);
-    }
-    ps.outs.push_back(r[i]);
-  }
-}
-bool out_ranges_overlap(const PipeState &ps, const double *glcm, size_t nglcm, const double *glrlm, size_t nglrlm) {
-  const OutRange r[2] = {{(const char *)glcm, (const char *)(glcm + nglcm)}, {(const char *)glrlm, (const char *)(glrlm + nglrlm)}};
-  for (int i = 0; i < 2; i++)
-    for (const OutRange &o : ps.outs)
-      if (r[i].lo && r[i].lo < o.hi && o.lo < r[i].hi) return true;
-  return false;
-}
-int pipeline_sticky(Context &c, int **sticky) { return c.get<int>("deferred_sticky", 16, sticky); }
-
-bool fin_job_empty(const FinJob &fj) { return fj.Na == 0 && fj.zn[0] + fj.zn[1] + fj.zn[2] == 0; }
-
-// can the finalize of v ride in a walk launch?  (the conditions of the one-launch finalize, a walk launch that is the volume's
-// last, and the job's 32-bit element indices)
-bool fin_can_ride(const SweepKnobs &kn, const VolState &v) {
-  const SweepPlan &p = v.p;
-  if (!(v.glcm && v.glrlm && p.fw && p.fused && p.lines.count > 0 && v.levels && pipe_set(v.lane))) return false;
-  if (p.row_slot >= 0 && p.fw_xblocks == 0) return false;   // (PRAD_FW_XROLE=0: the x angle is a launch behind the walk launch)
-  if (!finalize_one(kn) || (long long)v.Ng * v.Nr >= (1LL << 30) || v.Ng > 255 || v.Na > PRAD_MAX_SWEEP || v.Na != p.aset.count) return false;
-  return ((long long)v.Ng * v.Nr + (long long)v.Ng * v.Ng) * v.Na < (1LL << 31);
-}
-// can the walk launch of `host` on stream s carry a FinJob?  (with or without a pack job pj)
-bool fin_host_ok(const SweepKnobs &kn, const PipeState &ps, const VolState &host, const PackJob &pj, hipStream_t s) {
-  const SweepPlan &p = host.p;
-  if (!(fin_ride(kn) && ps.s == s && host.glcm && host.glrlm && p.fw && p.fused && p.lines.count > 0)) return false;
-  const size_t lds = p.fw_xblocks > 0 ? std::max(p.lds_fw, p.lds_fw_rows) : p.lds_fw;   // (as launch_fw_kpp)
-  return lds >= (size_t)PRAD_FIN_SCRATCH_BYTES && p.fw_blocks >= 1 && p.fw_blocks < 32768;
-}
-
-// The riding job of the launch that walks `host` and packs the volume of set `new_lane`: the finalize of `walked` (or none) and
-// the zeroing of `need` (the new volume's accumulators; or none) and of the NEXT set's row flags and flag words.  Each range is
-// named only if its set is one of instance ps and none of the sets this launch works on (see the invariant above).
-FinJob make_fin_job(const PipeState &ps, const VolState &host, const VolState *walked, const ZeroNeed *need, int new_lane) {
-  FinJob j;
-  memset(&j, 0, sizeof(j));
-  const int nline = host.p.fw_blocks;
-  if (walked) {
-    const VolState &w = *walked;
-    j.Na = w.Na;
-    j.Ng = w.Ng;
-    j.Nr = w.Nr;
-    j.Nz = w.p.Nz;
-    j.Ny = w.p.Ny;
-    j.Nx = w.p.Nx;
-    j.pitch = w.p.pitch;
-    j.L = w.levels;
-    j.glcm_acc = w.glcm_acc;
-    j.glrlm_acc = w.glrlm_acc;
-    j.glcm_out = w.glcm;
-    j.glrlm_out = w.glrlm;
-    j.multi = w.multi;
-    j.flags = w.flags_d;
-    // Placement of the 13 angle workgroups (each starts its walk ~7 us late; the role's chunk hand-out makes up for it):
-    // angle a on workgroup a / count of role a % count
-    const FwSet &fs = host.p.fwset;
-    for (int a = 0; a < w.Na; a++) {
-      for (int d = 0; d < 3; d++) j.off[a][d] = (signed char)w.p.aset.off[a][d];
-      const int role = a % fs.count, idx = a / fs.count;
-      const int b = (fs.first_block[role] + idx < fs.first_block[role + 1]) ? fs.first_block[role] + idx : a % nline;
-      j.ablock[a] = (short)b;
-    }
-  }
-  const int wl = walked ? walked->lane : -1;
-  const bool mine = new_lane >= ps.base && new_lane < ps.base + kPipeSets;
-  if (need && need->acc_w > 0 && mine && new_lane != host.lane && new_lane != wl) {
-    j.z[0] = need->acc;
-    j.zn[0] = (unsigned)need->acc_w;
-  }
-  if (mine) {
-    const int t = next_pipe_set(new_lane);
-    SetZero &S = set_zero_book()[t];
-    if (t != host.lane && t != wl && t != new_lane && S.rz_zero < S.rz_used && S.rz) {
-      j.z[1] = S.rz;
-      j.zn[1] = (unsigned)S.rz_used;
-      S.rz_zero = S.rz_used;
-    }
-    if (t != host.lane && t != wl && t != new_lane && S.fl && !S.fl_zero) {
-      j.z[2] = S.fl;
-      j.zn[2] = 4;
-      S.fl_zero = true;
-    }
-  }
-  return j;
-}
-
-// the stand-alone finalize of the walked volume on stream s (ordered behind its walk launch by the caller)
-int pipeline_finish_walked(Context &c, const SweepKnobs &kn, PipeState &ps, hipStream_t s) {
-  if (!ps.walked.valid) return PRAD_OK;
-  Call k;
-  k.c = &c;
-  k.s = s;
-  k.Na = ps.walked.Na;
-  k.flags_d = ps.walked.flags_d;
-  int *sticky = nullptr;
-  PRAD_TRY(pipeline_sticky(c, &sticky));
-  PRAD_TRY(vol_finalize(k, kn, ps.walked, sticky));
-  ps.walked.valid = false;
-  return PRAD_OK;
-}
-
-// walks of the pending volume on stream s (pj: the next volume's pack as a side job, or n16 == 0) and its finalize -- at once, or,
-// with `keep`, left to the next walk launch (the volume becomes `walked`).  The finalize of the volume walked BEFORE rides in
-// this launch if it can, else it is launched first.  need / new_lane: the zeroing the next volume still asks for and its set.
-int pipeline_retire(Context &c, const SweepKnobs &kn, PipeState &ps, hipStream_t s, const PackJob &pj, bool keep = false,
-                    const ZeroNeed *need = nullptr, int new_lane = -1) {
-  const bool host_ok = fin_host_ok(kn, ps, ps.pending, pj, s);   // (before ps.s moves)
-  PRAD_TRY(pipeline_order(ps, s));   // the pack ran on another stream: order the two on the device
-  Call k;
-  k.c = &c;
-  k.s = s;
-  k.Na = ps.pending.Na;
-  k.flags_d = ps.pending.flags_d;
-  int *sticky = nullptr;
-  PRAD_TRY(pipeline_sticky(c, &sticky));
-  FinJob fj;
-  memset(&fj, 0, sizeof(fj));
-  if (host_ok) {
-    const bool rides = ps.walked.valid && fin_can_ride(kn, ps.walked) && ps.walked.lane != ps.pending.lane && ps.walked.lane != new_lane;
-    if (ps.walked.valid && !rides) PRAD_TRY(pipeline_finish_walked(c, kn, ps, s));
-    fj = make_fin_job(ps, ps.pending, rides ? &ps.walked : nullptr, need, new_lane);
-    fj.sticky = sticky;
-    ps.walked.valid = false;   // (enqueued with the launch below)
-  } else {
-    PRAD_TRY(pipeline_finish_walked(c, kn, ps, s));
-  }
-  if (need && need->acc_w > 0 && fj.zn[0] == 0) {   // (the job did not take the accumulators: their set is one the launch works on)
-    ZeroNeed acc;
-    acc.acc = need->acc;
-    acc.acc_w = need->acc_w;
-    PRAD_TRY(launch_zero3(s, acc));
-  }
-  PRAD_TRY(vol_sweep(k, kn, ps.pending, pj, fj));
-  if (keep && fin_ride(kn) && fin_can_ride(kn, ps.pending)) {
-    ps.walked = ps.pending;
-    ps.pending.valid = false;
-    return PRAD_OK;
-  }
-  PRAD_TRY(vol_finalize(k, kn, ps.pending, sticky));
-  ps.pending.valid = false;
-  return PRAD_OK;
-}
-
-// nothing pending or walked in the instance afterwards (kernels enqueued on the pending volume's own stream; no host
-// synchronisation).  A failure leaves the instance empty: what could not be enqueued is not tried again.
-int pipeline_flush(Context &c, const SweepKnobs &kn, PipeState &ps) {
-  if (!ps.pending.valid && !ps.walked.valid) return PRAD_OK;
-  PackJob none;
-  memset(&none, 0, sizeof(none));
-  const size_t before = c.times.size();
-  const int rc = ps.pending.valid ? pipeline_retire(c, kn, ps, ps.s, none) : pipeline_finish_walked(c, kn, ps, ps.s);
-  if (rc != PRAD_OK) ps.pending.valid = ps.walked.valid = false;
-  if (c.timing_accumulate) c.all_times.insert(c.all_times.end(), c.times.begin() + (long)before, c.times.end());
-  return rc;
-}
-// ... both instances (every drain does; the first failure is reported, the other instance is flushed all the same)
-int pipeline_flush(Context &c, const SweepKnobs &kn) {
-  int rc = PRAD_OK;
-  for (int i = 0; i < kPipes; i++) {
-    const int r = pipeline_flush(c, kn, pipe_state(i));
-    if (rc == PRAD_OK) rc = r;
-  }
-  return rc;
-}
-// ... from an entry point that is no GLCM / GLRLM call (join, mark, status, set_device, ...): it reads the switches itself, and
-// only when there is a volume to flush
-int pipeline_flush(Context &c) {
-  if (!pipelines_busy()) return PRAD_OK;
-  return pipeline_flush(c, sweep_knobs_from_env());
-}
-// `s` waits (on the device) for what both instances have enqueued on streams of their own
-int pipelines_order(hipStream_t s) {
-  for (int i = 0; i < kPipes; i++) PRAD_TRY(pipeline_order(pipe_state(i), s));
-  return PRAD_OK;
-}
-// the host waits for both instances; afterwards none of their outputs is in flight
-int pipelines_sync() {
-  for (int i = 0; i < kPipes; i++) {
-    PipeState &ps = pipe_state(i);
-    if (ps.s) PRAD_HIP(hipStreamSynchronize(ps.s));
-    ps.outs.clear();
-  }
-  return PRAD_OK;
-}
-
-// one deferred call in pipeline mode; *handled = false: the volume is not a fixed-window one, the caller takes the
-// ordinary deferred route (the pipeline has been drained)
-int pipeline_step(Call &k, const SweepKnobs &kn, PipeState &ps, const SweepPlan &p, int Ng, int Nr, double *glcm, double *glrlm,
-                  bool *handled) {
-  Context &c = *k.c;
-  *handled = false;
-  if (!pipeline_volume(p, glcm != nullptr, glrlm != nullptr)) return pipeline_flush(c, kn);
-  // the instance changes its stream (a twin call behind one that was not, or the reverse; a caller with two streams): the new
-  // stream waits for the old one before anything of this call -- its zeroing included -- is enqueued
-  PRAD_TRY(pipeline_order(ps, k.s));
-  VolState v;
-  ZeroNeed need;
-  PRAD_TRY(vol_prepare(k, kn, p, Ng, Nr, glcm, glrlm, v, &need));
-  PackJob pj;
-  memset(&pj, 0, sizeof(pj));
-  bool inl = false;
-  if (ps.pending.valid) {
-    // (the side job writes the layout of the launch it rides in: fused-table and two-table volumes do not mix)
-    inl = pack_inline_ok(k, v) && ps.pending.p.fw2 == v.p.fw2 && !kn.no_inline_pack;
-    if (inl) pj = make_pack_job(k, kn, v, &ps.pending);
-    // the walk launch zeroes the accumulators of this volume itself if it carries a job; what the pack needs zeroed goes first
-    const bool ride = fin_host_ok(kn, ps, ps.pending, pj, k.s) && need.acc_w + need.rz_w + need.fl_w < ((size_t)1 << 30);
-    ZeroNeed now = need;
-    if (ride) {
-      now.acc_w = 0;
-      need.rz_w = need.fl_w = 0;
-    }
-    PRAD_TRY(launch_zero3(k.s, now));
-    PRAD_TRY(pipeline_retire(c, kn, ps, k.s, pj, true, ride ? &need : nullptr, v.lane));
-  } else {
-    PRAD_TRY(pipeline_finish_walked(c, kn, ps, ps.s));   // (a walked volume without a pending one: only after a failed call)
-    PRAD_TRY(launch_zero3(k.s, need));
-  }
-  if (!inl) PRAD_TRY(vol_pack_standalone(k, v));
-  v.packed_inline = inl;
-  ps.pending = v;
-  ps.s = k.s;
-  out_ranges_add(ps, glcm, (size_t)k.Na * Ng * Ng, glrlm, (size_t)k.Na * Ng * Nr);
-  *handled = true;
   return PRAD_OK;
 }
 
@@ -1228,6 +777,16 @@ int pairs_glcm_glrlm(Call &k, const SweepKnobs &kn, int Ng, int Nr, double *glcm
   return PRAD_OK;
 }
 
+// lanes: a whole-volume deferred call goes onto the next lane -- its stream, which waits for `user`, and a workspace set of its
+// own (#0 .. #7 belong to the pipelines' alternating volumes)
+int lanes_deal(Context &c, hipStream_t user, hipStream_t *s) {
+  c.lane = -1;
+  *s = user;
+  PRAD_TRY(c.lane_begin(user, s));
+  if (c.lane >= 0) c.lane += kAllPipeSets;
+  return PRAD_OK;
+}
+
 }  // namespace
 namespace prad {   // (prad_internal.h)
 int texture_pairs_runs(const int32_t *image, const uint8_t *mask, const int *size, int Nd, const int *angles,
@@ -1244,36 +803,9 @@ int texture_pairs_runs(const int32_t *image, const uint8_t *mask, const int *siz
   } lane_guard{c};
   bool pipe = c.deferred && !voxels && pipeline_mode(kn);
   const hipStream_t user = s;
-  if (c.deferred && !voxels && !pipe) {   // lanes mode: whole-volume deferred calls alternate between lanes
-    PRAD_TRY(c.lane_begin(s, &s));
-    if (c.lane >= 0) c.lane += kAllPipeSets;   // (workspace sets of their own: #0 .. #7 belong to the pipelines)
-  }
   int inst = 0;
-  if (pipe) {
-    // twin: the call goes to one of two pipelines on internal streams (see the pipeline's header); else instance 0 on the caller's stream
-    bool twin = kn.pipe_twin == 1;
-    if (kn.pipe_twin < 0 && size && Nd >= 1 && Nd <= PRAD_MAX_ND) {
-      long long n = 1;
-      for (int d = 0; d < Nd; d++) n *= std::max(size[d], 1);
-      twin = n >= kTwinMinVoxels;
-    }
-    if (twin) {
-      inst = (int)(pipe_shared().twin_calls++ % (unsigned)kPipes);
-      PRAD_TRY(c.twin_streams());
-      PRAD_TRY(c.lane_enter(inst, user, &s));
-    } else {
-      PRAD_TRY(pipeline_flush(c, kn, pipe_state(1)));   // (instance 1 holds volumes of twin calls only)
-    }
-    // an output buffer that the other instance still writes: that instance finishes first, and this call's stream waits for it
-    PipeState &other = pipe_state(1 - inst);
-    if (Na >= 1 && out_ranges_overlap(other, glcm, glcm ? (size_t)Na * Ng * Ng : 0, glrlm, glrlm ? (size_t)Na * Ng * Nr : 0)) {
-      PRAD_TRY(pipeline_flush(c, kn, other));
-      PRAD_TRY(pipeline_order(other, s));
-      other.outs.clear();
-    }
-    PipeState &ps = pipe_state(inst);
-    c.lane = ps.base + (int)(ps.seq++ % (unsigned)kPipeSets);   // four workspace sets of the instance alternate
-  }
+  if (pipe) PRAD_TRY(pipeline_enter(c, kn, size, Nd, Na, Ng, Nr, glcm, glrlm, &s, &inst));
+  else if (c.deferred && !voxels) PRAD_TRY(lanes_deal(c, user, &s));   // lanes mode
   Call k;
   PRAD_TRY(setup_call(k, image, mask, size, Nd, angles, Na, Nvox, voxels, kernelRadius, force2Ddim, s, false));
   SweepPlan p = plan_sweep(k, kn, Ng, Nr, glcm != nullptr, glrlm != nullptr);
@@ -1283,10 +815,7 @@ int texture_pairs_runs(const int32_t *image, const uint8_t *mask, const int *siz
     PRAD_TRY(pipeline_flush(c, kn));
     PRAD_TRY(pipelines_order(user));   // (twin volumes sit on internal streams: the lane's stream waits for `user`, so for them too)
     pipe = false;
-    c.lane = -1;
-    s = user;
-    PRAD_TRY(c.lane_begin(user, &s));
-    if (c.lane >= 0) c.lane += kAllPipeSets;   // (workspace sets of their own: #0 .. #7 belong to the pipelines' alternating volumes)
+    PRAD_TRY(lanes_deal(c, user, &s));
     PRAD_TRY(setup_call(k, image, mask, size, Nd, angles, Na, Nvox, voxels, kernelRadius, force2Ddim, s, false));
     p = plan_sweep(k, kn, Ng, Nr, glcm != nullptr, glrlm != nullptr);
   }
@@ -1295,8 +824,9 @@ int texture_pairs_runs(const int32_t *image, const uint8_t *mask, const int *siz
   bool done = false;
   c.last_variant = !p.ok ? "none" : (p.fw2 ? "fw2" : (p.fw && glcm && glrlm ? "fw" : "lines"));
   if (pipe) {
-    PRAD_TRY(pipeline_step(k, kn, pipe_state(inst), p, Ng, Nr, glcm, glrlm, &done));
-    if (done) c.last_path = "sweep";
+    PRAD_TRY(pipeline_step(k, kn, inst, p, Ng, Nr, glcm, glrlm));   // (a pipeline volume: the other ones left for the lanes above)
+    done = true;
+    c.last_path = "sweep";
   }
   if (!done && p.ok) {
     PRAD_TRY(sweep_glcm_glrlm(k, kn, p, Ng, Nr, glcm, glrlm, &done));
@@ -1860,15 +1390,7 @@ int prad_set_device(int device) {
       (void)pipeline_flush(c);   // volumes still pending or walked on the old device, in either instance: retire them there
       (void)pipelines_sync();
     }
-    for (int i = 0; i < kPipes; i++) {
-      PipeState &ps = pipe_state(i);
-      ps.pending.valid = false;
-      ps.walked.valid = false;
-      ps.s = nullptr;
-      ps.ev = nullptr;
-      ps.outs.clear();
-    }
-    set_zero_forget();
+    pipelines_forget(true);
     c.own_stream = nullptr;  // streams belong to a device; new ones are created lazily
     for (int l = 0; l < PRAD_MAX_LANES; l++) {
       if (c.lane_stream[l]) (void)hipStreamSynchronize(c.lane_stream[l]);
@@ -1895,9 +1417,8 @@ int prad_release_workspace(void) {
   if (pipelines_busy()) {   // their buffers are about to go away: retire them first, in both instances
     (void)pipeline_flush(c);
     (void)pipelines_sync();
-    for (int i = 0; i < kPipes; i++) pipe_state(i).pending.valid = pipe_state(i).walked.valid = false;
   }
-  set_zero_forget();                      // (what was known to be zero lived in the workspace)
+  pipelines_forget(false);                // (what was known to be zero lived in the workspace)
   glszm_state().valid = false;            // its zone list lives in the workspace
   for (auto &kv : c.bufs) {
     if (kv.second.p) (void)hipFree(kv.second.p);
@@ -2008,7 +1529,7 @@ int prad_set_deferred_mode(int mode) {
   PRAD_TRY(pipeline_flush(c));
   PRAD_TRY(pipelines_sync());
   PRAD_TRY(c.lanes_sync());
-  pipe_shared().mode = mode;
+  pipelines().mode = mode;
   return PRAD_OK;
 }
 int prad_set_workspace(int id) {
@@ -2143,6 +1664,17 @@ int prad_debug_sweep_plan(const int *size, int Nd, const int *angles, int Na, in
       }
     }
   }
+  if ((int)r.size() > cap) return -(int)r.size();
+  std::copy(r.begin(), r.end(), out);
+  return (int)r.size();
+}
+
+// The launches the deferred pipeline plans for a script of events, replayed through a fresh planner (the layouts of an event and
+// of a record: include/pyradiomics_amd.h).  Host only.
+int prad_debug_pipe_plan(const long long *events, int nevents, int *out, int cap) {
+  if (!events || nevents < 1 || !out || cap < 1) return 0;
+  std::vector<int> r;
+  pipe_replay(events, nevents, r);
   if ((int)r.size() > cap) return -(int)r.size();
   std::copy(r.begin(), r.end(), out);
   return (int)r.size();

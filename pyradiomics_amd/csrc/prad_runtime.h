@@ -153,7 +153,7 @@ struct Context {
     return rc;
   }
   // internal stream l (created on first use) waits for everything queued on `user` so far; neither `lane` nor the lanes'
-  // round-robin moves (the twin deferred pipelines of prad_api.hip run on streams 0 and 1 and name their workspace sets themselves)
+  // round-robin moves (the twin deferred pipelines of prad_pipeline.h run on streams 0 and 1 and name their workspace sets themselves)
   int lane_enter(int l, hipStream_t user, hipStream_t *s) {
     if (!lane_stream[l]) {   // (twin_streams() has created both for the twin pipelines)
       PRAD_HIP(hipStreamCreateWithFlags(&lane_stream[l], hipStreamNonBlocking));

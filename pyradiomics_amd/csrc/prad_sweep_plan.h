@@ -40,7 +40,7 @@ struct SweepKnobs {
   bool no_pairs = false;       // PRAD_NO_PAIRS: no pairs tier between the sweeps and the exact kernels (baseline)
   bool lanes_mode = false;     // PRAD_DEFERRED_MODE=lanes
   int pipe_twin = -1;          // PRAD_PIPE_TWIN: 1 = deal pipeline volumes onto two pipelines on two internal streams, 0 = one
-                               // pipeline on the caller's stream, unset (-1) = by volume size (prad_api.hip kTwinMinVoxels)
+                               // pipeline on the caller's stream, unset (-1) = by volume size (prad_pipe_plan.h kTwinMinVoxels)
 };
 
 inline Knob env_knob(const char *name, bool wide = false) {

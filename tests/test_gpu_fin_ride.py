@@ -1,5 +1,5 @@
 """The finalize of a deferred fused-table volume and the zeroing for the next ones as a riding job of the NEXT walk launch
-(csrc/kernels_sweepfw.h FinJob; csrc/prad_api.hip: the pipeline's `walked` slot and its four workspace sets): a steady step of
+(csrc/kernels_sweepfw.h FinJob; csrc/prad_pipeline.h, csrc/prad_pipe_plan.h: the pipeline's `walked` slot and its four workspace sets): a steady step of
 same-shaped volumes is one launch.
 
 Every result is compared bit for bit with the CPU checker AND with the same sequence under PRAD_FIN_RIDE=0 (the stand-alone
@@ -105,6 +105,54 @@ def test_runs_of_one_shape(engine, checker, monkeypatch, shape, kind, mkind):
     n1, n0 = _both(engine, monkeypatch, vols, timing=True)
     assert n0 == 6
     assert n1 <= 2, "the finalize of a steady step did not ride: %d stand-alone launches in a run of 6" % n1
+
+
+# ---- the replayed planner is the live one: it names the stand-alone finalize launches that the device then counts ---------------
+def _pipe_event(lib, v):
+    """the deferred call of volume v as an event of prad_debug_pipe_plan: what the executor reads off the sweep plan (fin_can_ride,
+    fin_host_ok of csrc/prad_pipeline.h) restated on the record of prad_debug_sweep_plan, planned for the device's compute units"""
+    import ctypes as C
+    from test_pipe_plan import call
+    shape, Ng, Nr = tuple(v[0].shape), v[2], v[3]
+    angles = np.ascontiguousarray(v[6], dtype=np.int32)
+    out = np.zeros(4096, np.int32)
+    n = lib.prad_debug_sweep_plan((C.c_int * 3)(*shape), 3, angles.ctypes.data_as(C.POINTER(C.c_int)), len(angles), Ng, Nr, 1, 1, 0,
+                                  out.ctypes.data_as(C.POINTER(C.c_int)), len(out))
+    assert n > 42 and out[0] == 1
+    fused, fw, lds_fw, lds_fw_rows, fw_blocks, row_slot, fw_xblocks, nlines = (int(out[i]) for i in (4, 5, 21, 22, 29, 39, 40, 41))
+    Na = int(out[42 + 10 * nlines])
+    assert fused and fw and nlines > 0 and Na == len(angles)
+    can_ride = not (row_slot >= 0 and fw_xblocks == 0) and Ng <= 255 and Na <= 16 and (Ng * Nr + Ng * Ng) * Na < 2 ** 31
+    lds = max(lds_fw, lds_fw_rows) if fw_xblocks > 0 else lds_fw
+    host_plan_ok = lds >= 7176 and 1 <= fw_blocks < 32768      # (sizeof(FinScratch), csrc/kernels_sweep.h)
+    # (whether the pack rides is not counted below: a stand-alone pack is timed as "pack")
+    return call(shape, Ng, can_ride=int(can_ride), host_plan_ok=int(host_plan_ok), inline=0, acc=len(angles) * Ng * (Ng + Nr) + 2000)
+
+
+@pytest.mark.parametrize("run", ["six of one shape", "large first"])
+def test_replayed_plan_counts_the_live_launches(engine, checker, monkeypatch, run):
+    """Six (9, 40, 130) volumes, and the `large first` sequence of test_zero_extents: the stand-alone finalize launches that
+    prad_debug_pipe_plan plans for the sequence are exactly the ones the "finalize" timing family counts on the device, with the
+    route on and with PRAD_FIN_RIDE=0.  (zero3_kernel is timed under no family: its launches are pinned on the host alone,
+    tests/test_pipe_plan.py.)"""
+    from pyradiomics_amd import _lib
+    from test_pipe_plan import FINALIZE, flush, kinds, plan
+    lib = _lib.load()
+    if run == "large first":
+        vols = [_vol(checker, 300 + i, (9, 40, 130), 32, "uniform", "random") for i in range(5)]
+        vols += [_vol(checker, 310 + i, (2, 2, 65), 32, "uniform", "full") for i in range(5)]
+    else:
+        vols = [_vol(checker, 100 + i, (9, 40, 130), 32, "uniform", "full") for i in range(6)]
+    for ride in (1, 0):
+        monkeypatch.delenv("PRAD_FIN_RIDE", raising=False)
+        if not ride:
+            monkeypatch.setenv("PRAD_FIN_RIDE", "0")
+        records, _ = plan(lib, [dict(_pipe_event(lib, v), fin_ride=ride) for v in vols] + [flush(ride)])
+        got, nfin, raised, _ = _run(engine, vols, timing=True)
+        assert not raised
+        _assert_equal(got, vols)
+        assert nfin == kinds(records, FINALIZE), (run, ride, nfin, records)
+    monkeypatch.delenv("PRAD_FIN_RIDE")
 
 
 # ---- the job carries the geometry of volume N-2, not the launch's -------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""Two interleaved deferred pipelines (csrc/prad_api.hip, "Twin"): with PRAD_PIPE_TWIN=1 deferred whole-volume calls are dealt
+"""Two interleaved deferred pipelines (csrc/prad_pipe_plan.h, "Twin"; csrc/prad_pipeline.h): with PRAD_PIPE_TWIN=1 deferred whole-volume calls are dealt
 alternately onto two instances of the pipeline, each on an internal stream of its own with four workspace sets of its own, so
 that consecutive walk launches are unordered on the device.
 
