@@ -578,6 +578,45 @@ struct FwWave {
     }
     r = (int)(DX > 0 ? fw_shr1((u32)r) : fw_shl1((u32)r));
   }
+  // The plain groups of a window-filling row close the U lines that leave the row with ONE ds_add of U lanes behind the
+  // group's last step, instead of a one-lane ds_add in every step (a ds_add costs the LDS pipe a full slot whatever its
+  // exec mask: profiles/r06_probes.md section 1).  The table adds are the same U adds at the same U addresses: atomic adds
+  // commute, nothing reads the table before the workgroup's flush, and nothing is carried from one group to the next.
+  // -DPRAD_FW_EDGE_EACH restores the close in every step (the A/B build); an instantiation whose K is beyond
+  // PRAD_FW_EDGE_BATCH_KMAX keeps it too (none does: no instantiation gained a register).  profiles/edge_batch_measurements.md.
+#ifndef PRAD_FW_EDGE_BATCH_KMAX
+#define PRAD_FW_EDGE_BATCH_KMAX 16
+#endif
+#if defined(PRAD_FW_EDGE_EACH) || defined(PRAD_DBG_NOEDGE)
+  static constexpr bool edge_batch = false;
+#else
+  static constexpr bool edge_batch = !HASPAD && DX != 0 && K <= PRAD_FW_EDGE_BATCH_KMAX;
+#endif
+  static_assert(PRAD_FW_U <= 32, "the group's edge addresses sit in U lanes of one register");
+  // Step k of a plain group: the edge lane's state (the address of its close: cur = 0) joins the group's buffer, then the
+  // register moves on by one lane as in rotate_reg.  One DPP move: the buffer shifts one lane AWAY from the edge lane, which
+  // has no source lane and keeps `old` = r.  Behind step U - 1 the U lanes next to the edge hold the U addresses.
+  __device__ __forceinline__ void capture_reg(int &buf, int &r, int k) {
+    if (DX > 0) {
+      // r was written by the last VALU instruction of the step's inline assembly (column K - 1 is always its last column),
+      // which the compiler's hazard recognizer does not look into: a DPP read needs two wait states behind a VALU write.
+      // (The per-step close had its three instructions there.)  For DX < 0 the register is column 0's: 18 instructions ago.
+      asm volatile("s_nop 1" : "+v"(r));
+    }
+    buf = k == 0 ? r : __builtin_amdgcn_update_dpp(r, buf, DX > 0 ? 0x130 : 0x138, 0xf, 0xf, false);
+    r = (int)(DX > 0 ? fw_shr1((u32)r) : fw_shl1((u32)r));
+  }
+  __device__ __forceinline__ void close_captured(int buf) {
+#if !defined(PRAD_FW_NOASM)
+    if (DX > 0)   // lanes 63 .. 64 - U
+      asm volatile("s_mov_b32 exec_lo, 0\n\ts_mov_b32 exec_hi, %[m]\n\tds_add_u32 %[b], %[one]\n\ts_mov_b64 exec, -1" ::[m] "n"(0xffffffffu << (32 - U)),
+                   [b] "v"(buf), [one] "v"(one) : "memory");
+    else          // lanes 0 .. U - 1
+      asm volatile("s_mov_b64 exec, %[m]\n\tds_add_u32 %[b], %[one]\n\ts_mov_b64 exec, -1" ::[m] "n"((1 << U) - 1), [b] "v"(buf), [one] "v"(one) : "memory");
+#else
+    lds_bump((DX > 0 ? lane >= 64 - U : lane < U) ? buf : dummy);
+#endif
+  }
   // one march step on the canonical register assignment (register j = column j), all cases handled
   __device__ __forceinline__ void single_step(const u32 (&C)[KW], bool tail) {
     u32 X[KW];
@@ -609,6 +648,7 @@ struct FwWave {
   // pk_late (PRAD_FW_PACK_LATE, an experiment from that time): the pack unit's loads go out behind the FIRST step of the
   // group instead of in front of the group.  Measured again on the counted waits: profiles/pack_global_measurements.md.
   __device__ __forceinline__ void plain_group(const u32 (&v)[U][KW], PackWave *pk_late = nullptr) {
+    int ebuf = 0;   // edge_batch: the addresses of the group's edge closes, one per lane
 #pragma unroll
     for (int k = 0; k < U; k++) {
       if (k == 1 && pk_late) pk_late->begin();
@@ -622,11 +662,17 @@ struct FwWave {
         const int r2 = (((4 * w + 2 - k * DX) % K) + K) % K, r3 = (((4 * w + 3 - k * DX) % K) + K) % K;
         fw_plain_word(T, dummy, one, pl[r0], pl[r1], pl[r2], pl[r3], v[k][w], X[w]);
       }
-      if (DX > 0) rotate_reg<true>(pl[(((K - 1 - k) % K) + K) % K], FW_BYTE(v[k], K - 1));
-      if (DX < 0) rotate_reg<true>(pl[k % K], FW_BYTE(v[k], 0));
+      if (edge_batch) {   // (indexed by the step, not the register: K = 4 meets every register twice, K = 16 half of them)
+        if (DX > 0) capture_reg(ebuf, pl[(((K - 1 - k) % K) + K) % K], k);
+        if (DX < 0) capture_reg(ebuf, pl[k % K], k);
+      } else {
+        if (DX > 0) rotate_reg<true>(pl[(((K - 1 - k) % K) + K) % K], FW_BYTE(v[k], K - 1));
+        if (DX < 0) rotate_reg<true>(pl[k % K], FW_BYTE(v[k], 0));
+      }
 #pragma unroll
       for (int w = 0; w < KW; w++) P[w] = v[k][w];
     }
+    if (edge_batch) close_captured(ebuf);
     if (DX != 0 && (U % K) != 0) {   // K = 16: U steps leave the assignment rotated by U registers -- back to register j = column j
       int tmp[K];
 #pragma unroll
