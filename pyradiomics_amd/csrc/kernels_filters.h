@@ -3,8 +3,10 @@
 //
 //   swt_axis_kernel      one level-1 undecimated, periodised analysis step along one axis:
 //                        lo[o] = sum_k dec_lo[k] * x[(o + F/2 - k) mod N],  hi likewise   (float64, taps in
-//                        ascending k, unfused multiply/add so that rounding follows the CPU restatement of
-//                        PyWavelets' downsampling_convolution_periodization; imageoperations.py:921-935)
+//                        ascending k from 0.0, as PyWavelets' downsampling_convolution_periodization; imageoperations.py:
+//                        921-935.  The compiler contracts each multiply / add pair into one fused multiply-add, the
+//                        __d*_rn spelling notwithstanding: one rounding per tap, within the derived bound of
+//                        tests/filters_reference.py, not bit for bit the unfused CPU restatement)
 //   rgauss_line_kernel   ITK RecursiveGaussianImageFilter along one axis: one lane per line, 4th-order causal +
 //                        anti-causal recursion with edge-replicating boundary initialisation, float64 inside the
 //                        line, float32 images between passes (imageoperations.py:824-830)
@@ -93,8 +95,8 @@ __global__ void __launch_bounds__(256) swt_axis2_kernel(const double *__restrict
 // a column of 8 x 32 (y, x) outputs and streams along z: each input plane of the column (with its F - 1 halo rows and columns,
 // periodic) is staged in LDS, the x pass leaves lo / hi rows in LDS, every lane runs the y pass for its own (y, x) and keeps
 // the four y-bands of the last F planes in REGISTERS, from which the z pass produces the eight outputs of a finished
-// plane.  72 B per voxel reach HBM.  Every 1-D sum is the one of swt_axis_kernel -- taps in ascending k from 0.0, unfused
-// multiply / add, float64 intermediates -- so the sub-bands are the same bits (tests/test_gpu_filters.py).
+// plane.  72 B per voxel reach HBM.  Every 1-D sum is the one of swt_axis_kernel -- taps in ascending k from 0.0, the same
+// (contracted) multiply / add, float64 intermediates -- so the sub-bands are the same bits (tests/test_gpu_filters.py).
 // Output order as swt_level1_dev builds it for axes (2, 1, 0): band index = (bx * 2 + by) * 2 + bz.
 #define PRAD_SWT3_TY 8
 #define PRAD_SWT3_TX 32

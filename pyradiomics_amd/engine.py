@@ -1081,17 +1081,29 @@ def wavelet_images(image: torch.Tensor, wavelet="coif1"):
     return out
 
 
-def _log_real(image: torch.Tensor) -> torch.Tensor:
-    """the type the filter reads and returns: float64 inputs stay float64, everything else is float32 (SimpleITK's real type
-    of the input, imageoperations.py:824-830).  Between the passes every image is float32 (ITK's InternalRealType)."""
-    return image.contiguous() if image.dtype == torch.float64 else image.to(torch.float32).contiguous()
+# integer types whose values float32 cannot hold: ITK's derivative pass reads the image in its own type
+_LOG_WIDE_INTEGERS = tuple(getattr(torch, n) for n in ("int32", "int64", "uint32", "uint64") if hasattr(torch, n))
+
+
+def _log_real(image: torch.Tensor):
+    """-> (the image in the type the filter reads, the type it returns).  float64 inputs stay float64 and return float64;
+    everything else returns float32 (SimpleITK's real type of the input, imageoperations.py:824-830).  The derivative pass
+    of every term reads the input in its OWN type, widened to float64 (oracle/filters_oracle.py: recursive_gaussian): int16,
+    uint8, float32 ... are exact in float32 and go in as float32; 32- and 64-bit integers are not above 2^24 and go in as
+    float64 (exact up to 2^53), the result -- float32 values, the cumulative image is float32 -- cast back to float32.
+    Between the passes every image is float32 (ITK's InternalRealType)."""
+    if image.dtype == torch.float64:
+        return image.contiguous(), torch.float64
+    if image.dtype in _LOG_WIDE_INTEGERS:
+        return image.to(torch.float64).contiguous(), torch.float32
+    return image.to(torch.float32).contiguous(), torch.float32
 
 
 def log_images(image: torch.Tensor, spacing_xyz, sigmas, normalize: bool = True) -> list:
     """log_image for a list of sigmas, up to 8 per launch sequence (prad_log_multi_dev[_f64]): the same bits per sigma, the
     sigmas share the GPU.  float64 images in -> float64 out, otherwise float32."""
     lib = _lib.load()
-    x = _log_real(image)
+    x, out_type = _log_real(image)
     fn = lib.prad_log_multi_dev_f64 if x.dtype == torch.float64 else lib.prad_log_multi_dev
     lib.prad_set_device(x.device.index or 0)
     size = np.array(x.shape, dtype=np.intc)
@@ -1105,14 +1117,14 @@ def log_images(image: torch.Tensor, spacing_xyz, sigmas, normalize: bool = True)
         rc = fn(C.c_void_p(x.data_ptr()), _iptr(size), x.dim(), C.c_void_p(sp.ctypes.data),
                 C.c_void_p(part.ctypes.data), len(res), 1 if normalize else 0, ptrs, _stream_ptr())
         _lib.raise_for(rc, "LoG")
-        outs.extend(res)
+        outs.extend(r.to(out_type) for r in res)
     return outs
 
 
 def log_image(image: torch.Tensor, spacing_xyz, sigma: float, normalize: bool = True) -> torch.Tensor:
     """sitk.LaplacianRecursiveGaussianImageFilter on the device: float32 tensor (float64 for a float64 input)"""
     lib = _lib.load()
-    x = _log_real(image)
+    x, out_type = _log_real(image)
     fn = lib.prad_log_dev_f64 if x.dtype == torch.float64 else lib.prad_log_dev
     lib.prad_set_device(x.device.index or 0)
     size = np.array(x.shape, dtype=np.intc)
@@ -1121,7 +1133,7 @@ def log_image(image: torch.Tensor, spacing_xyz, sigma: float, normalize: bool = 
     rc = fn(C.c_void_p(x.data_ptr()), _iptr(size), x.dim(), C.c_void_p(sp.ctypes.data), float(sigma),
             1 if normalize else 0, C.c_void_p(out.data_ptr()), _stream_ptr())
     _lib.raise_for(rc, "LoG")
-    return out
+    return out.to(out_type)
 
 
 # ---- many small ROIs in a few launches: the batch route lives in roi_batch.py; its public names are bound here too ----------

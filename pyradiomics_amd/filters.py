@@ -160,8 +160,11 @@ def laplacian_recursive_gaussian(array, spacing_xyz, sigma, normalize=True):
     """sitk.LaplacianRecursiveGaussianImageFilter (NormalizeAcrossScale) on the device, host arrays in and out: float32,
     or float64 for a float64 input (the filter keeps the input's pixel type, imageoperations.py:824-830; its internal images
     are float32 either way, as in ITK)"""
-    f64 = np.asarray(array).dtype == np.float64
-    a = np.ascontiguousarray(array, dtype=np.float64 if f64 else np.float32)
+    src = np.asarray(array)
+    # 32- and 64-bit integers hold values that float32 cannot: the derivative pass reads them as float64 (engine._log_real)
+    wide = src.dtype.kind in "iu" and src.dtype.itemsize >= 4
+    f64 = src.dtype == np.float64 or wide
+    a = np.ascontiguousarray(src, dtype=np.float64 if f64 else np.float32)
     size = np.array(a.shape, dtype=np.intc)
     sp = np.array([float(s) for s in spacing_xyz][::-1], dtype=np.float64)
     out = np.empty(a.shape, dtype=a.dtype)
@@ -169,7 +172,7 @@ def laplacian_recursive_gaussian(array, spacing_xyz, sigma, normalize=True):
     rc = fn(C.c_void_p(a.ctypes.data), size.ctypes.data_as(C.POINTER(C.c_int)), a.ndim,
             C.c_void_p(sp.ctypes.data), float(sigma), 1 if normalize else 0, C.c_void_p(out.ctypes.data))
     _lib.raise_for(rc, "LoG")
-    return out
+    return out.astype(np.float32) if wide else out
 
 
 def getLoGImage(inputImage, inputMask, **kwargs):

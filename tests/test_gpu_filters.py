@@ -22,9 +22,20 @@ def test_wavelet_matches_restatement(shape, wavelet):
     want = {"wavelet-" + k: v for k, v in ret[0].items()}
     want["wavelet-" + "L" * len(axes)] = ap
     assert list(got) == list(want)                      # names AND yield order (LLH ... HHH, then LLL)
+    # held to the long-double reference within the derived rounding bound of the float64 passes (tests/filters_reference.py:
+    # 1.6e-11 for coif1 here, where 1e-10 was allowed)
+    import filters_reference as fr
+    assert fr.AVAILABLE, fr.SKIP_REASON
+    lo, hi = fo.wavelet_filters(wavelet)
+    ref_ap, ref_ret = fr.swt3(x, (lo, hi), axes=axes)
+    ref = {"wavelet-" + k: v for k, v in ref_ret[0].items()}
+    ref["wavelet-" + "L" * len(axes)] = ref_ap
+    bound = fr.wavelet_bound(lo, hi, len(axes), float(np.abs(x.astype(np.float64)).max()))
+    assert bound < 2e-11
     for k in want:
         assert got[k].dtype == np.float64 and got[k].shape == x.shape
-        np.testing.assert_allclose(got[k], want[k], rtol=1e-13, atol=1e-10)
+        assert np.abs(got[k] - ref[k]).max() <= bound, (k, float(np.abs(got[k] - ref[k]).max()), bound)
+        assert np.abs(want[k] - ref[k]).max() <= bound
     # energy identity of an orthogonal undecimated transform: sum of sub-band energies = 2^naxes * ||x||^2
     if all(s % 2 == 0 for s in np.array(shape)[list(axes)]):
         e = sum(float((v.astype(np.float64) ** 2).sum()) for v in got.values())
@@ -57,8 +68,7 @@ def test_log_matches_restatement(spacing, sigma):
         return
     im, name, _ = out[0]
     assert name == "log-sigma-%s-mm-3D" % str(sigma).replace(".", "-") and im.array.dtype == np.float32
-    scale = np.abs(want).max()
-    assert np.abs(im.array - want).max() <= 2e-6 * scale     # float32 images, identical operation order
+    assert np.array_equal(im.array, want)                    # float32 images, identical operation order: the same bits
 
 
 def test_log_properties():
@@ -360,10 +370,9 @@ def test_log_float64_matches_restatement(shape, spacing, sigma):
     x = rng.standard_normal(shape) * 100.0
     want = fo.laplacian_recursive_gaussian(x, spacing, sigma)
     assert want.dtype == np.float64 and np.array_equal(want, want.astype(np.float32))
-    scale = np.abs(want).max()
     got = engine.log_image(torch.from_numpy(x).cuda(), spacing, sigma).cpu().numpy()
     assert got.dtype == np.float64 and np.array_equal(got, got.astype(np.float32))      # float32 values in a float64 image
-    assert np.abs(got - want).max() <= 2e-6 * scale
+    assert np.array_equal(got, want)
     host = filters.laplacian_recursive_gaussian(x, spacing, sigma)
     assert host.dtype == np.float64 and np.array_equal(host, got)
     multi = engine.log_images(torch.from_numpy(x).cuda(), spacing, [sigma, 2.0])
@@ -392,7 +401,7 @@ def test_log_after_normalize_is_float64_through_the_extractor():
     (derived, name, _), = list(filters.getLoGImage(norm, None, sigma=[3.0]))
     assert derived.array.dtype == np.float64 and name == "log-sigma-3-0-mm-3D"
     want = fo.laplacian_recursive_gaussian(norm.array, image.GetSpacing(), 3.0)
-    assert np.abs(derived.array - want).max() <= 2e-6 * np.abs(want).max()
+    assert np.array_equal(derived.array, want)
 
 
 @pytest.mark.parametrize("shape", [(64, 64, 64), (18, 40, 44), (6, 8, 10), (70, 12, 130), (8, 6, 34)])
