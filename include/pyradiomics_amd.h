@@ -61,8 +61,8 @@ int prad_release_workspace(void);
 /* name of the code path taken by this thread's last calculate_* call ("sweep", "generic", ...);
  * lets tests assert that the fast kernels (not a fallback) produced a result. */
 const char *prad_last_path(void);
-/* which sweep kernels the plan of this thread's last GLCM / GLRLM call chose: "fw" (fixed window, fused table: <= 44 grey
- * levels, rows of 65..512 voxels), "fw2" (fixed window, two tables, 16-bit levels: 45+ levels), "lines" (wrapped lines);
+/* which sweep kernels the plan of this thread's last GLCM / GLRLM call chose: "fw" (fixed window, fused table: <= 36 grey
+ * levels, rows of 65..1024 voxels), "fw2" (fixed window, two tables, 16-bit levels: 40 .. 170 levels, rows of 65..512), "lines" (wrapped lines);
  * after prad_label_census*: "census-lds" or "census-global". */
 const char *prad_last_variant(void);
 /* Total device time (ms, HIP events on the work stream) of this thread's last calculate_* call, and
@@ -101,7 +101,7 @@ int prad_timing_end(void);
  * HBM-bound, the walk issue-bound: the pack's memory time disappears), then finalizes volume N-1.  Volume N is walked by
  * the next deferred call, or by prad_deferred_join / prad_deferred_status, which flush the pipeline.  As with the lanes,
  * inputs and outputs of a deferred call belong to the library until one of those two returns.  The pipeline takes the
- * volumes of the fixed-window kernels -- fused table (up to 44 levels) and, since round 5, two tables (45 .. 160 levels;
+ * volumes of the fixed-window kernels -- fused table (up to 36 levels) and, since round 5, two tables (40 .. 170 levels;
  * a volume of the other kind than the one before it packs in a launch of its own) -- every other whole-volume call is
  * dealt onto the lanes.
  * Twin pipelines: large volumes (from 2^27 voxels, 512^3; PRAD_PIPE_TWIN=1 forces it for every pipeline volume,

@@ -287,10 +287,11 @@ struct Walker {
 
 // Fused flavour: H byte = prev*P + min(len-1, RS)*Q + cur*4 with Q = 4(Ng+1), P = (RS+1)*Q.
 // State is ONE running LDS address pl = prev*P + (len-1)*Q (the bin row of the open run, relative to the table) plus prev.
-// The fused table only fits for Ng <= 44, so the packed volume holds level*4 (PRAD_FUSED_SHIFT) and `prev` / `cur`
-// below are those pre-scaled bytes: the bin offset cur*4 is the byte itself and prev*P = byte * (P/4), which lets
-// the compiler read the byte lanes of the packed word directly in v_add / v_mul_u32_u24 / v_cmp (SDWA) instead of
-// extracting them first.
+// The planner takes the fused table only while the rows kernel's 36 KB hold four length slots of it (prad_sweep_plan.h
+// plan_tables: Ng <= 36 for Nr >= 4; never beyond 255 >> PRAD_FUSED_SHIFT = 63), so the packed volume holds level*4
+// (PRAD_FUSED_SHIFT) and `prev` / `cur` below are those pre-scaled bytes: the bin offset cur*4 is the byte itself and
+// prev*P = byte * (P/4), which lets the compiler read the byte lanes of the packed word directly in v_add /
+// v_mul_u32_u24 / v_cmp (SDWA) instead of extracting them first.
 // Whether a line held >= 2 masked voxels is NOT tracked here (it would cost mask logic on every step); it is
 // recovered after the sweeps by resolve_multi_kernel / multi_check_kernel.
 #define PRAD_FUSED_SHIFT 2

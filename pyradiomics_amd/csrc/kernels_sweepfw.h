@@ -429,7 +429,7 @@ struct PackWave {
       // v_perm.  FAST PATH, decided once for the 16 voxels of the piece: every voxel lies inside the mask and every level
       // is regular (1..Ng, no bits beyond the low byte) -- then the packed bytes are the levels and nothing is outside the
       // ROI.  With q = pk - 0x01010101 and r = q + (0x80 - Ng) * 0x01010101, bit 7 of some byte of pk | q | r is set iff
-      // some byte of pk is 0 or > Ng (the lowest irregular byte sees no borrow / carry from below; Ng <= 44 on this path).
+      // some byte of pk is 0 or > Ng (the lowest irregular byte sees no borrow / carry from below; Ng <= 36 on this path: the fused table).
       const u32 K80 = 0x80808080u, K7F = 0x7f7f7f7fu, K01 = 0x01010101u;
       const u32 radd = (0x80u - (u32)J.Ng) * K01;
       u32 pk[4], nzw[4], badbits = 0, wideall = 0, nzall = K80;

@@ -1,7 +1,8 @@
-// kernels_sweepfw2.h -- the fixed-window line sweeps for 44 .. ~160 grey levels (binWidth 25 on CT gives 60 - 160), gfx950.
+// kernels_sweepfw2.h -- the fixed-window line sweeps for 40 .. 170 grey levels (binWidth 25 on CT gives 60 - 160), gfx950.
 //
-// The fused table H[prev][len][cur] of kernels_sweepfw.h grows with (Ng+1)^2 x length slots: beyond 44 levels the 160 KB
-// of LDS no longer hold the 16+ slots the plain path needs, and level*4 no longer fits the byte lanes the step reads.
+// The fused table H[prev][len][cur] of kernels_sweepfw.h grows with (Ng+1)^2 x length slots: beyond 36 levels the 36 KB
+// of its rows kernel no longer hold four slots (prad_sweep_plan.h plan_tables), beyond 44 the 160 KB of LDS no longer hold the
+// 16+ slots the plain path needs, and beyond 63 level*4 no longer fits the byte lanes the step reads.
 // Same geometry here (a wave owns a window of 64*K columns that covers whole rows, lines with dx != 0 drift through
 // renamed registers, pieces / dead lines / tails exactly as there), different accumulation:
 //   * levels are 16-bit elements (level*4; 0 outside the ROI), two columns per dword, SDWA word selects;

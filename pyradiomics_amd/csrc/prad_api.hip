@@ -487,7 +487,7 @@ int vol_pack_standalone(Call &k, VolState &v) {
   }
   const int vec_ok = p.vec_rows && ((((uintptr_t)k.image) | ((uintptr_t)k.mask) | ((uintptr_t)v.levels)) & 15) == 0;
   const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((k.g.n / 16 + 255) / 256, 4096));
-  // the fused walker reads level*4 bytes (see Walker<true, true, LONG, true>); it only exists for Ng <= 44
+  // the fused walker reads level*4 bytes (see Walker<true, true, LONG, true>); the planner takes it for Ng <= 36
   const int shift = (v.glcm && v.glrlm && p.fused) ? PRAD_FUSED_SHIFT : 0;
   hipLaunchKernelGGL(pack_levels_kernel, dim3(gx), dim3(256), 0, k.s, k.image, k.mask, k.g.n, p.Nx, p.pitch, p.padw,
                      v.Ng, v.levels, v.flags_d, vec_ok, shift, v.rowzero);

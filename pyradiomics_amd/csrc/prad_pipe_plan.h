@@ -8,13 +8,13 @@
 // pack is a side job of the walking waves: kernels_sweepfw.h PackJob).  Volume N itself stays PENDING (packed, not yet walked)
 // until the next deferred call or until prad_deferred_status / prad_deferred_join / prad_deferred_mark flush it.
 //
-// Fused-table volumes (<= 44 levels) go one stage further: volume N-1 is not finalized behind its walk launch but stays WALKED,
+// Fused-table volumes (<= 36 levels) go one stage further: volume N-1 is not finalized behind its walk launch but stays WALKED,
 // and the NEXT walk launch -- the one of call N+1, which walks N and packs N+1 -- carries its finalize and the zeroing for the
 // volumes to come as a riding job (FinJob), so a steady step is ONE launch: no zero3_kernel, no finalize_volume_kernel.  The
 // job rides only in a fused-table launch on the same stream; otherwise (a two-table volume, another stream,
 // PRAD_FW_XROLE=0, PRAD_FINALIZE_ONE=0, PRAD_FIN_RIDE=0, any flush) the stand-alone finalize of the walked volume is launched
 // FIRST.  Every flush finishes the walked volume too, so the contract stands: outputs are valid after prad_deferred_status,
-// prad_deferred_join or a mark.  The two-table route (45 - 160 levels) is finalized behind its walk launch.
+// prad_deferred_join or a mark.  The two-table route (40 - 170 levels) is finalized behind its walk launch.
 //
 // Workspace sets.  Three volumes are in flight -- packed, walked, being finalized (whose LEVELS the rare exact test reads) -- so
 // FOUR sets alternate (set = first set of the instance + seq % 4).  Launch N walks N-1 (set N-1), packs N (set N), finalizes N-2

@@ -132,7 +132,7 @@ struct SweepPlan {
   int RSfw_rows = 0;           // length slots of the rows role's table (it shares the LDS with 16 staging tiles)
   size_t lds_fw_rows = 0;      // the x angle as a launch of its own (sweep_fw_rows_kernel)
   int fw_xblocks = 0;          // > 0: the x angle is the trailing role of the fixed-window launch, this many workgroups behind fw_blocks
-  // two-table fixed-window kernel (kernels_sweepfw2.h): 45+ grey levels
+  // two-table fixed-window kernel (kernels_sweepfw2.h): 40 .. 170 grey levels
   bool fw2 = false;
   int RS2 = 0;                 // run-length slots per level row
   int fw2_copies = 1;          // copies of the run-length slots in a row (lane l uses copy l mod copies)
@@ -189,7 +189,7 @@ inline int bank_stride_rs(int rs, int Ng, int Nr) {
   return rs;
 }
 
-// Table choice: the fused [prev][len][cur] table, the two tables of the fixed-window kernel for 45+ levels, or separate GLCM /
+// Table choice: the fused [prev][len][cur] table, the two tables of the fixed-window kernel for 40+ levels, or separate GLCM /
 // GLRLM tables -- and the shape of the lines and rows kernels of kernels_sweep.h that follows from it.  false: no table fits.
 inline bool plan_tables(SweepPlan &p, const PlanInput &in, const SweepKnobs &kn, int Nr) {
   const int Ng = in.Ng;
@@ -204,7 +204,7 @@ inline bool plan_tables(SweepPlan &p, const PlanInput &in, const SweepKnobs &kn,
       p.RSr = rsr;
     }
   }
-  // Two-table fixed-window kernel for the line angles when the fused table does not fit (45+ levels): rows that one wave
+  // Two-table fixed-window kernel for the line angles when the fused table does not fit (40+ levels): rows that one wave
   // window covers, a level row [Ng + 1 pairs | RS2 lengths] table within the LDS, and the rows kernel (separate tables, here
   // with up to 100 KB for them) for the angle along x
   if (want_glcm && want_glrlm && !p.fused && Ng >= 40 && p.Nx > 64 && p.Nx <= 512 && !kn.no_fw2) {

@@ -5,11 +5,14 @@
 Host only (prad_debug_sweep_plan makes no device call).  Per case the fixture keeps the case and an 8-byte digest of its record;
 for the named cases the whole record.
 
-The committed fixture is the planner's behaviour BEFORE it was taken apart into csrc/prad_sweep_plan.h, and
-tests/test_sweep_plan.py holds every later planner to it.  It was recorded from the commit before that change (b5d5949,
-"Finalize and zero inside the next walk launch: one launch per volume"), whose plan_sweep was left untouched, plus
-tests/golden/sweep_plan_recorder.patch: the patch adds prad_debug_sweep_plan there (with a thread-local override of cu_count()
-for `cus`) and nothing else.  To record it again from that planner, from the repository root:
+The committed fixture has two origins, and tests/test_sweep_plan.py holds every later planner to both.  The 14 890 cases whose Ng
+is not one of those named below are the planner's behaviour BEFORE it was taken apart into csrc/prad_sweep_plan.h: they were
+recorded from the commit before that change (b5d5949, "Finalize and zero inside the next walk launch: one launch per volume"),
+whose plan_sweep was left untouched, plus tests/golden/sweep_plan_recorder.patch: the patch adds prad_debug_sweep_plan there (with
+a thread-local override of cu_count() for `cus`) and nothing else.  The cases with Ng = 36, 37, 95, 96, 125, 126, 157, 158, 170 and
+171 (the counts at which the planner changes its table regime) were added later and come from the CURRENT planner: the whole file
+was recorded again here, every one of the older cases kept its digest, and the switch list and the named records stayed equal
+(profiles/sweep_limits_measurements.md).  To record the grid from the old planner, from the repository root:
 
     git worktree add ../prad_parent b5d5949
     git -C ../prad_parent apply "$PWD/tests/golden/sweep_plan_recorder.patch"

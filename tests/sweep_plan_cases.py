@@ -13,7 +13,8 @@ import numpy as np
 
 NX = [1, 2, 47, 48, 64, 65, 95, 96, 191, 192, 256, 257, 512, 513, 1024, 1025]
 ZY = [(1, 1), (1, 5), (3, 3), (40, 9), (130, 64)]
-NG = [1, 7, 8, 32, 39, 40, 44, 45, 63, 64, 100, 160, 161, 255, 256]
+# (36|37, 39|40, 95|96, 125|126, 157|158 and 170|171 are where the planner changes its table regime: tests/sweep_limits_cases.py)
+NG = [1, 7, 8, 32, 36, 37, 39, 40, 44, 45, 63, 64, 95, 96, 100, 125, 126, 157, 158, 160, 161, 170, 171, 255, 256]
 WANTS = [3, 1, 2]
 CUS = [256, 250, 12]
 ANGLE_LISTS = ["unit", "unit_no_x", "x_only", "bidirectional", "distance2", "two_x", "too_many"]

@@ -1,5 +1,5 @@
 """Seeded random sweep over the configuration space of the matrix calls: shapes (odd sizes, unit dimensions, rows
-around the 16-byte pitch steps), grey-level counts on both sides of every kernel-path threshold (fused table <= 44,
+around the 16-byte pitch steps), grey-level counts on both sides of every kernel-path threshold (fused table <= 36,
 byte levels <= 255, generic above), mask densities, smooth and random levels, force2D, distances.  Every case
 compares the HIP path with the CPU oracle through the operator module, bit-exact (NGTDM float column: 1e-12 on these small volumes)."""
 import numpy as np

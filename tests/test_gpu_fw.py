@@ -96,11 +96,16 @@ def test_fw_short_pieces(cm, checker, shape, cl, monkeypatch):
         _check(cm, checker, _levels(8, shape, 24, kind), _mask(4, shape, mkind), 24)
 
 
-@pytest.mark.parametrize("Ng", [2, 7, 40])
+@pytest.mark.parametrize("Ng", [2, 7, 36, 40])
 def test_fw_levels(cm, checker, Ng):
+    """few levels and the fused table's last: 36 is the highest count whose [prev][len][cur] table the planner still takes
+    (the rows kernel's 36 KB must hold four length slots), so 2, 7 and 36 run the fused fixed-window kernel.  40 levels are
+    past it: that call takes the two-table fixed-window kernel (kernels_sweepfw2.h), which starts there"""
+    from pyradiomics_amd import _lib
     shape = (21, 22, 320)
     _check(cm, checker, _levels(6, shape, Ng, "uniform"), _mask(5, shape, "random"), Ng)
     _check(cm, checker, _levels(6, shape, Ng, "smooth"), _mask(5, shape, "full"), Ng)
+    assert _lib.last_variant() == ("fw2" if Ng == 40 else "fw")
 
 
 def test_fw_empty_planes_and_rows(cm, checker):
@@ -342,7 +347,7 @@ def test_side_job_pack_handles_odd_level_words(cm, checker, odd):
         engine.set_deferred_mode(-1)
 
 
-# ---- the two-table fixed-window kernel (csrc/kernels_sweepfw2.h): 45+ grey levels ------------------------------------------
+# ---- the two-table fixed-window kernel (csrc/kernels_sweepfw2.h): 40+ grey levels ------------------------------------------
 def _check2(cm, checker, img, mask, Ng):
     from pyradiomics_amd import _lib
     _check(cm, checker, img, mask, Ng)
@@ -352,7 +357,7 @@ def _check2(cm, checker, img, mask, Ng):
 @pytest.mark.parametrize("Ng", [44, 64, 100, 128, 160])
 @pytest.mark.parametrize("shape", [(20, 24, 512), (24, 20, 256), (18, 30, 300), (30, 18, 130), (9, 40, 66)])
 def test_fw2_levels_and_shapes(cm, checker, Ng, shape):
-    """Ng 45 .. 160 on the fixed-window kernel with two tables and 16-bit level elements: rows that fill the window (256
+    """Ng 44 .. 160 (of the 40 .. 170 it takes) on the fixed-window kernel with two tables and 16-bit level elements: rows that fill the window (256
     with 4 columns per lane, 512 with 8) and ragged ones, iid and smooth levels, bit-exact against the reference C"""
     for kind in ("uniform", "smooth"):
         _check2(cm, checker, _levels(hash(shape) % 991 + Ng, shape, Ng, kind), _mask(1, shape, "full"), Ng)

@@ -88,7 +88,7 @@ JUNK = np.array([0, -5, 255, 256, 1 << 20, -(1 << 30), 65535, 65536, 32768], dty
 
 @pytest.mark.parametrize("seed", [0, 1, 2, 3, 4, 5])
 def test_fw_long_marches(seed, checker):
-    """the fixed-window walks (fused table <= 44 levels, two tables above) on marches long enough to be cut into pieces"""
+    """the fixed-window walks (fused table <= 36 levels, two tables from 40) on marches long enough to be cut into pieces"""
     from pyradiomics_amd import cmatrices as cm, _lib
     rng = np.random.default_rng(600 + seed)
     deep = 0
