@@ -597,6 +597,20 @@ int prad_batch_plan_f2d(const int *sizes, int B, int Ng, int families, const int
 int prad_calculate_batch_f2d_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B,
                                  int Ng, int families, const int *distances, int Ndist, int alpha, int force2Ddim, double *glcm,
                                  double *glrlm, double *gldm, double *ngtdm, int *status, void *stream);
+/* A grey-level count PER ROI.  The *_ng entry points of the batched texture route take `const int *Ng`, a HOST vector [B], where
+ * the calls above and below take `int Ng`; ROI b then has Ng[b] levels: its matrices are [Ng[b]][...] in every layout, its
+ * masked levels must lie in [1, Ng[b]] (status PRAD_INDEX_ERROR otherwise, whatever the counts of the other ROIs) and a plan's
+ * offsets advance by its own shapes.  This is what a fixed bin width gives a table of lesions.  The scalar entry points are these
+ * with the same count for every ROI -- one implementation --, so everything said of them holds: layouts, status, domain,
+ * synchronisation, kernel family, prad_last_path / prad_last_variant.  Domain: any Ng[b] < 1 is PRAD_E_ARG; any Ng[b] > 64 is
+ * PRAD_E_UNSUPPORTED for the whole batch before anything is launched or written (a plan fills its outputs all the same): the
+ * caller partitions the batch.  A NULL vector with B > 0 is PRAD_E_ARG.  The LDS tables of the matrix launch are sized by the
+ * most any ROI asks for with its own count, within the budget, and never below the smallest whole table of every ROI. */
+int prad_batch_plan_ng(const int *sizes, int B, const int *Ng, int families, const int *distances, int Ndist, int force2Ddim,
+                       long long *out_offsets, int *Na);
+int prad_calculate_batch_ng_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B,
+                                const int *Ng, int families, const int *distances, int Ndist, int alpha, int force2Ddim,
+                                double *glcm, double *glrlm, double *gldm, double *ngtdm, int *status, void *stream);
 
 /* ---- GLSZM of many small ROIs (csrc/kernels_batch_glszm.h) -------------------------------------------------------------
  * The same batch layout (levels / mask DEVICE, sizes [B][3] / off HOST).  One workgroup per ROI packs the box into LDS and
@@ -636,6 +650,13 @@ int prad_batch_glszm_fill_dev(const int *zones, const int *summary_host, const l
  *   "-f2d2" otherwise.  A force2Ddim outside [-1, 2] is PRAD_E_ARG. */
 int prad_batch_glszm_f2d_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B, int Ng,
                              int force2Ddim, int *zones, int *summary, int *status, void *stream);
+/* The same two calls with a grey-level count per ROI (HOST int [B], see prad_batch_plan_ng): the labelling launch checks ROI b's
+ * levels against Ng[b]; the fill writes float64 [Ng[b]][cols_b] at out + out_offsets[b]. */
+int prad_batch_glszm_ng_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B,
+                            const int *Ng, int force2Ddim, int *zones, int *summary, int *status, void *stream);
+int prad_batch_glszm_fill_ng_dev(const int *zones, const int *summary_host, const long long *off, int B, const int *Ng,
+                                 int compact, double *out, const long long *out_offsets, int *sizes_out,
+                                 const long long *sizes_offsets, void *stream);
 
 /* ---- feature formulas of many small ROIs (csrc/kernels_batch_features.h) -------------------------------------------------
  * The formulas of prad_glcm_features_dev, prad_glcm_mcc_dev, prad_zone_matrix_features_dev and prad_ngtdm_features_dev on the
@@ -675,6 +696,16 @@ int prad_batch_features_dev(const int *sizes, int B, int Ng, int families, const
                             const long long *offsets, const double *glszm, const long long *glszm_offsets,
                             const int *glszm_sizes, const long long *glszm_sizes_offsets, int symmetric, int want_mcc,
                             double *out, int *empty, void *stream);
+/* The same two calls with a grey-level count per ROI (HOST int [B], see prad_batch_plan_ng): the matrices of ROI b have Ng[b]
+ * rows (GLCM: and columns), as prad_calculate_batch_ng_dev and prad_batch_glszm_fill_ng_dev write them.  The row layout of `out`
+ * does not depend on the counts; the scratch in nrec[2] does. */
+int prad_batch_features_plan_ng(const int *sizes, int B, const int *Ng, int families, const int *Na, const int *glszm_cols,
+                                long long *out_offsets, long long *nrec);
+int prad_batch_features_ng_dev(const int *sizes, int B, const int *Ng, int families, const int *Na, const int *glszm_cols,
+                               const double *glcm, const double *glrlm, const double *gldm, const double *ngtdm,
+                               const long long *offsets, const double *glszm, const long long *glszm_offsets,
+                               const int *glszm_sizes, const long long *glszm_sizes_offsets, int symmetric, int want_mcc,
+                               double *out, int *empty, void *stream);
 
 /* ---- weighted angle merge of many small ROIs: weightingNorm (csrc/kernels_batch_merge.h) --------------------------------------
  * One launch for the whole batch turns the per-angle GLCM and GLRLM buffers of prad_calculate_batch[_f2d]_dev into ONE matrix
@@ -700,6 +731,12 @@ int prad_batch_merge_plan(const int *sizes, int B, int Ng, int families, const i
 int prad_batch_merge_angles_dev(const int *sizes, int B, int Ng, int families, const int *Na, const double *glcm,
                                 const double *glrlm, const long long *offsets, const double *weights, const int *status,
                                 int symmetric, double *glcm_w, double *glrlm_w, void *stream);
+/* The same two calls with a grey-level count per ROI (HOST int [B], see prad_batch_plan_ng): glcm_w of ROI b is [Ng[b]][Ng[b]][1],
+ * glrlm_w [Ng[b]][Nr][1].  The merge has no upper bound on the counts. */
+int prad_batch_merge_plan_ng(const int *sizes, int B, const int *Ng, int families, const int *Na, long long *out_offsets);
+int prad_batch_merge_angles_ng_dev(const int *sizes, int B, const int *Ng, int families, const int *Na, const double *glcm,
+                                   const double *glrlm, const long long *offsets, const double *weights, const int *status,
+                                   int symmetric, double *glcm_w, double *glrlm_w, void *stream);
 
 /* ---- first-order statistics and discretisation of many small ROIs (csrc/kernels_batch_firstorder.h) --------------------
  * The front end of the batched route: raw intensity boxes in, the statistics of prad_firstorder_dev and the levels and level

@@ -117,11 +117,25 @@ SYMBOLS = {
     "prad_batch_plan_f2d": (C.c_int, [_ip, C.c_int, C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.POINTER(C.c_longlong), _ip]),
     "prad_calculate_batch_f2d_dev": (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_longlong), C.c_int, C.c_int, C.c_int, _ip, C.c_int,
                                                C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "prad_batch_plan_ng": (C.c_int, [_ip, C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_int, C.POINTER(C.c_longlong), _ip]),
+    "prad_calculate_batch_ng_dev": (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_longlong), C.c_int, _ip, C.c_int, _ip, C.c_int,
+                                              C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "prad_batch_glszm_max_vox": (C.c_int, []),
     "prad_batch_glszm_dev": (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_longlong), C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "prad_batch_glszm_fill_dev": (C.c_int, [_vp, _ip, C.POINTER(C.c_longlong), C.c_int, C.c_int, C.c_int, _vp,
                                             C.POINTER(C.c_longlong), _vp, C.POINTER(C.c_longlong), _vp]),
     "prad_batch_glszm_f2d_dev": (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_longlong), C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "prad_batch_glszm_ng_dev": (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_longlong), C.c_int, _ip, C.c_int, _vp, _vp, _vp, _vp]),
+    "prad_batch_glszm_fill_ng_dev": (C.c_int, [_vp, _ip, C.POINTER(C.c_longlong), C.c_int, _ip, C.c_int, _vp,
+                                               C.POINTER(C.c_longlong), _vp, C.POINTER(C.c_longlong), _vp]),
+    "prad_batch_merge_plan_ng": (C.c_int, [_ip, C.c_int, _ip, C.c_int, _ip, C.POINTER(C.c_longlong)]),
+    "prad_batch_merge_angles_ng_dev": (C.c_int, [_ip, C.c_int, _ip, C.c_int, _ip, _vp, _vp, C.POINTER(C.c_longlong),
+                                                 C.POINTER(C.c_double), _vp, C.c_int, _vp, _vp, _vp]),
+    "prad_batch_features_plan_ng": (C.c_int, [_ip, C.c_int, _ip, C.c_int, _ip, _ip, C.POINTER(C.c_longlong),
+                                              C.POINTER(C.c_longlong)]),
+    "prad_batch_features_ng_dev": (C.c_int, [_ip, C.c_int, _ip, C.c_int, _ip, _ip, _vp, _vp, _vp, _vp, C.POINTER(C.c_longlong),
+                                             _vp, C.POINTER(C.c_longlong), _vp, C.POINTER(C.c_longlong), C.c_int, C.c_int, _vp,
+                                             _vp, _vp]),
     "prad_batch_merge_plan": (C.c_int, [_ip, C.c_int, C.c_int, C.c_int, _ip, C.POINTER(C.c_longlong)]),
     "prad_batch_merge_angles_dev": (C.c_int, [_ip, C.c_int, C.c_int, C.c_int, _ip, _vp, _vp, C.POINTER(C.c_longlong),
                                               C.POINTER(C.c_double), _vp, C.c_int, _vp, _vp, _vp]),

@@ -346,8 +346,42 @@ def batch_forced_dim(force2D, force2Ddimension) -> int:
     return d
 
 
+# the entry points that take `int Ng` -> their twins that take a host vector `const int *Ng` [B]
+_NG_TWIN = {"prad_batch_plan_f2d": "prad_batch_plan_ng", "prad_calculate_batch_f2d_dev": "prad_calculate_batch_ng_dev",
+            "prad_batch_glszm_f2d_dev": "prad_batch_glszm_ng_dev", "prad_batch_glszm_fill_dev": "prad_batch_glszm_fill_ng_dev",
+            "prad_batch_merge_plan": "prad_batch_merge_plan_ng", "prad_batch_merge_angles_dev": "prad_batch_merge_angles_ng_dev",
+            "prad_batch_features_plan": "prad_batch_features_plan_ng", "prad_batch_features_dev": "prad_batch_features_ng_dev"}
+BATCH_MAX_NG = 64          # levels per ROI the batched texture kernels take (PRAD_BATCH_MAX_NG)
+
+
+def batch_levels(Ng, B):
+    """`Ng` of the batched calls, normalised: an int stays an int (one count for the whole batch, the calls as they always
+    were); an int sequence becomes an intc array [B], one count per ROI (anything but B entries is a ValueError)"""
+    if np.ndim(Ng) == 0:
+        return int(Ng)
+    v = np.asarray(Ng)
+    if v.ndim != 1 or v.shape[0] != int(B) or not np.issubdtype(v.dtype, np.integer):
+        raise ValueError("Ng must be an int or an int sequence with one entry per ROI (%d), got shape %s %s"
+                         % (int(B), v.shape, v.dtype))
+    return np.ascontiguousarray(v.astype(np.intc))
+
+
+def batch_levels_vector(Ng, B):
+    """intc [B] whichever form `Ng` has (for the arithmetic of the Python layer)"""
+    Ng = batch_levels(Ng, B)
+    return Ng if isinstance(Ng, np.ndarray) else np.full(int(B), Ng, dtype=np.intc)
+
+
+def batch_levels_call(lib, name, Ng):
+    """`Ng` as batch_levels returns it -> (the entry point `name` for an int, its _ng twin for a vector; the C argument)"""
+    if isinstance(Ng, np.ndarray):
+        return getattr(lib, _NG_TWIN[name]), _iptr(Ng)
+    return getattr(lib, name), int(Ng)
+
+
 def batch_plan(sizes, Ng, families=BATCH_FAMILIES, distances=(1,), force2D=False, force2Ddimension=0):
-    """Host-side layout of a batch (prad_batch_plan_f2d; needs no device).  sizes: int [B, 3].  -> (covered, offsets int64
+    """Host-side layout of a batch (prad_batch_plan_f2d, or prad_batch_plan_ng for an int sequence Ng [B]: every ROI laid out
+    with its own count; needs no device).  sizes: int [B, 3].  -> (covered, offsets int64
     [4, B + 1], Na int32 [2, B]): covered = the native call takes the batch; offsets[f] = first double of every ROI in the
     flat buffer of family BATCH_FAMILIES[f] (last entry: its length); Na[0] = unidirectional angle count of `distances`
     (GLCM; GLDM rows hold 2 * (2 * Na) + 1 columns), Na[1] = that of distance 1 (GLRLM) -- with force2D the counts of
@@ -357,9 +391,9 @@ def batch_plan(sizes, Ng, families=BATCH_FAMILIES, distances=(1,), force2D=False
     B = int(sizes.shape[0])
     offsets = np.zeros((4, B + 1), dtype=np.int64)
     Na = np.zeros((2, B), dtype=np.intc)
-    rc = _lib.load().prad_batch_plan_f2d(_iptr(sizes), B, int(Ng), batch_family_bits(families), _iptr(dist), int(dist.shape[0]),
-                                         batch_forced_dim(force2D, force2Ddimension),
-                                         offsets.ctypes.data_as(C.POINTER(C.c_longlong)), _iptr(Na))
+    plan, ng = batch_levels_call(_lib.load(), "prad_batch_plan_f2d", batch_levels(Ng, B))
+    rc = plan(_iptr(sizes), B, ng, batch_family_bits(families), _iptr(dist), int(dist.shape[0]),
+              batch_forced_dim(force2D, force2Ddimension), offsets.ctypes.data_as(C.POINTER(C.c_longlong)), _iptr(Na))
     if rc != _lib.PRAD_OK and rc != _lib.PRAD_E_UNSUPPORTED:
         _lib.raise_for(rc, "batch plan")
     return rc == _lib.PRAD_OK, offsets, Na
@@ -370,7 +404,7 @@ MERGE_FAMILIES = ("glcm", "glrlm")       # the families weightingNorm merges: bi
 
 def batch_merge_plan(sizes, Ng, Na, families=MERGE_FAMILIES):
     """Host-side layout of the weighted angle merge (prad_batch_merge_plan; needs no device).  Na: the int [2, B] of
-    batch_plan.  -> offsets int64 [3, B + 1]: rows 0 / 1 = first double of every ROI's merged GLCM [Ng, Ng, 1] / GLRLM [Ng,
+    batch_plan; Ng: an int or an int sequence [B].  -> offsets int64 [3, B + 1]: rows 0 / 1 = first double of every ROI's merged GLCM [Ng, Ng, 1] / GLRLM [Ng,
     max(size), 1] in its flat buffer (zeros for a family not asked for), row 2 = first weight of every ROI in the flat weight
     table (Na[0, b] GLCM weights, then Na[1, b] GLRLM weights); last entries: the lengths."""
     sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
@@ -379,8 +413,9 @@ def batch_merge_plan(sizes, Ng, Na, families=MERGE_FAMILIES):
     if Na.shape[1] != B or not families or any(f not in MERGE_FAMILIES for f in families):
         raise ValueError("batch_merge_plan: Na must be [2, B], families a non-empty subset of %s" % (MERGE_FAMILIES,))
     offsets = np.zeros((3, B + 1), dtype=np.int64)
-    rc = _lib.load().prad_batch_merge_plan(_iptr(sizes), B, int(Ng), sum(1 << MERGE_FAMILIES.index(f) for f in set(families)),
-                                           _iptr(Na), offsets.ctypes.data_as(C.POINTER(C.c_longlong)))
+    plan, ng = batch_levels_call(_lib.load(), "prad_batch_merge_plan", batch_levels(Ng, B))
+    rc = plan(_iptr(sizes), B, ng, sum(1 << MERGE_FAMILIES.index(f) for f in set(families)), _iptr(Na),
+              offsets.ctypes.data_as(C.POINTER(C.c_longlong)))
     _lib.raise_for(rc, "batch merge plan")
     return offsets
 
@@ -430,12 +465,13 @@ def batch_weights(sizes, Na, distances, weightingNorm, spacing=(1.0, 1.0, 1.0), 
 
 
 def batch_shapes(sizes, Ng, Na):
-    """{family: [shape of ROI b]} for the plan's Na"""
+    """{family: [shape of ROI b]} for the plan's Na; Ng: an int or an int sequence [B]"""
     sizes = np.asarray(sizes).reshape(-1, 3)
-    return {"glcm": [(Ng, Ng, int(a)) for a in Na[0]],
-            "glrlm": [(Ng, int(max(s)), int(a)) for s, a in zip(sizes, Na[1])],
-            "gldm": [(Ng, 4 * int(a) + 1) for a in Na[0]],
-            "ngtdm": [(Ng, 3) for _ in Na[0]]}
+    ng = [int(g) for g in batch_levels_vector(Ng, len(sizes))]
+    return {"glcm": [(g, g, int(a)) for g, a in zip(ng, Na[0])],
+            "glrlm": [(g, int(max(s)), int(a)) for g, s, a in zip(ng, sizes, Na[1])],
+            "gldm": [(g, 4 * int(a) + 1) for g, a in zip(ng, Na[0])],
+            "ngtdm": [(g, 3) for g in ng]}
 
 
 def _host_box(image, mask):
@@ -592,31 +628,45 @@ def calculate_matrices_batch(images, masks, Ng, families=BATCH_FAMILIES, distanc
     adds the merged "glcm_w" [Ng, Ng, 1] / "glrlm_w" [Ng, max(size), 1]).
     Where the native call does not cover the batch (Ng > 64, a box above prad_batch_max_vox() voxels, > 127 angles) or no
     device is visible, the single calls are looped ROI by ROI (and raise as they do without a device); last_batch_route()
-    tells which.  GLSZM: calculate_glszm_batch."""
+    tells which.  GLSZM: calculate_glszm_batch.
+    Ng: an int, or an int sequence [B] -- every ROI with its own count, as engine.texture_matrices_batch takes it: the ROIs of
+    at most 64 levels inside the box caps share one native call, the others take the single calls ("mixed")."""
     families = tuple(families)
     batch_family_bits(families)
     imgs, msks, sizes, upload = _host_roi_batch(images, masks, "matrices", loops=True)
     dist = [int(d) for d in np.asarray(distances).ravel()]
     f2, fd = bool(force2D), int(force2Ddimension)
-    covered, offsets, Na = batch_plan(sizes, Ng, families, dist, f2, fd)
-    shapes = batch_shapes(sizes, int(Ng), Na)
     B = len(imgs)
+    Ng = batch_levels(Ng, B)
+    covered, offsets, Na = batch_plan(sizes, Ng, families, dist, f2, fd)
+    shapes = batch_shapes(sizes, Ng, Na)
     batch_weighting_norm(weightingNorm)
-    if weightingNorm is not None and upload is not None:      # the merge is a device launch: the device route serves it
-        mats, status = _engine().texture_matrices_batch(*upload(), sizes, int(Ng), families, dist, int(gldm_a), f2, fd,
+    # the merge is a device launch and a batch of mixed counts is partitioned there: the device route serves both
+    if (weightingNorm is not None or isinstance(Ng, np.ndarray)) and upload is not None:
+        mats, status = _engine().texture_matrices_batch(*upload(), sizes, Ng, families, dist, int(gldm_a), f2, fd,
                                                         weightingNorm, spacing, symmetricalGLCM)
         return {f: [m.cpu().numpy() for m in mats[f]] for f in mats}, status
     if not covered or upload is None:
-        single = {"glcm": lambda i, m: calculate_glcm(i, m, dist, int(Ng), f2, fd)[0][0],
-                  "glrlm": lambda i, m: calculate_glrlm(i, m, int(Ng), int(max(i.shape)), f2, fd)[0][0],
-                  "gldm": lambda i, m: calculate_gldm(i, m, dist, int(Ng), int(gldm_a), f2, fd)[0],
-                  "ngtdm": lambda i, m: calculate_ngtdm(i, m, dist, int(Ng), f2, fd)[0]}
-        mats, status = _looped_matrices(zip(imgs, msks), int(Ng), families, shapes, single)
+        def single(ng):
+            return {"glcm": lambda i, m: calculate_glcm(i, m, dist, ng, f2, fd)[0][0],
+                    "glrlm": lambda i, m: calculate_glrlm(i, m, ng, int(max(i.shape)), f2, fd)[0][0],
+                    "gldm": lambda i, m: calculate_gldm(i, m, dist, ng, int(gldm_a), f2, fd)[0],
+                    "ngtdm": lambda i, m: calculate_ngtdm(i, m, dist, ng, f2, fd)[0]}
+        if isinstance(Ng, np.ndarray):          # (no device: ROI by ROI, each with its own count)
+            mats, status = {f: [] for f in families}, []
+            for b in range(B):
+                one, st = _looped_matrices([(imgs[b], msks[b])], int(Ng[b]), families, {f: [shapes[f][b]] for f in shapes},
+                                           single(int(Ng[b])))
+                status += st
+                for f in families:
+                    mats[f] += one[f]
+        else:
+            mats, status = _looped_matrices(zip(imgs, msks), Ng, families, shapes, single(Ng))
         if weightingNorm is not None:
             merge_looped(mats, sizes, Na, dist, weightingNorm, spacing, f2, fd, symmetricalGLCM)
         return mats, status
     flat_l, flat_m = upload()
-    flat, status = _engine().texture_matrices_batch_flat(flat_l, flat_m, sizes, int(Ng), families, dist, int(gldm_a), f2, fd)
+    flat, status = _engine().texture_matrices_batch_flat(flat_l, flat_m, sizes, Ng, families, dist, int(gldm_a), f2, fd)
     mats = {}
     for f in families:
         host = flat[f].cpu().numpy()
@@ -633,19 +683,29 @@ def calculate_glszm_batch(images, masks, Ng, compact=False, force2D=False, force
     max(maxRegion, 1)] of calculate_glszm (without its leading axis); compact=True: (P [Ng, k], sizes int32 [k]) as
     calculate_glszm_compact.  With no device visible the single calls are looped ROI by ROI (and raise as they do without a
     device); last_batch_route() tells which route ran.  force2D / force2Ddimension: zones join only in the plane across that
-    axis; weightingNorm / spacing are accepted and ignored, as the class ignores them."""
+    axis; weightingNorm / spacing are accepted and ignored, as the class ignores them.  Ng: an int, or an int sequence [B]
+    (every ROI with its own count, as engine.glszm_batch takes it)."""
     imgs, msks, sizes, upload = _host_roi_batch(images, masks, "GLSZM", loops=True)
-    Ng = int(Ng)
+    Ng = batch_levels(Ng, len(imgs))
     f2, fd = bool(force2D), int(force2Ddimension)
     f2d = batch_forced_dim(f2, fd)
     batch_weighting_norm(weightingNorm)
     if upload is None:
-        def single(img, msk, Ns):
-            P = calculate_glszm(img, msk, Ng, Ns, f2, fd)[0]
-            cols = np.flatnonzero(P.any(0))
-            return (np.ascontiguousarray(P[:, cols]), (cols + 1).astype(np.intc)) if compact else P
+        def single(ng):
+            def one(img, msk, Ns):
+                P = calculate_glszm(img, msk, ng, Ns, f2, fd)[0]
+                cols = np.flatnonzero(P.any(0))
+                return (np.ascontiguousarray(P[:, cols]), (cols + 1).astype(np.intc)) if compact else P
+            return one
         _set_batch_route("looped")
-        return _looped_glszm(zip(imgs, msks), Ng, compact, single, f2d=f2d)
+        if not isinstance(Ng, np.ndarray):
+            return _looped_glszm(zip(imgs, msks), Ng, compact, single(Ng), f2d=f2d)
+        results, status = [], []
+        for img, msk, ng in zip(imgs, msks, Ng):
+            one, st = _looped_glszm([(img, msk)], int(ng), compact, single(int(ng)), f2d=f2d)
+            results += one
+            status += st
+        return results, status
     flat_l, flat_m = upload()
     results, status = _engine().glszm_batch(flat_l, flat_m, sizes, Ng, compact=compact, force2D=f2, force2Ddimension=fd)
     if compact:
@@ -665,9 +725,10 @@ def calculate_features_batch(images, masks, Ng, classes=("glcm", "glrlm", "glszm
     calls and the batched formulas of engine.texture_features_batch.  -> {class: {feature name: float64 [B]}}; a ROI with a masked level
     outside [1, Ng] (the single calls' IndexError) has NaN everywhere, the others are not affected.  The names are those of the feature classes
     (VOXEL_*_FEATURES, plus "MCC").  Needs a device (RuntimeError without one); last_batch_route() tells which route ran.
-    force2D / force2Ddimension / weightingNorm / spacing: as engine.texture_features_batch."""
+    force2D / force2Ddimension / weightingNorm / spacing: as engine.texture_features_batch; so is Ng: an int, or an int sequence
+    [B] that gives every ROI its own count."""
     _, _, sizes, upload = _host_roi_batch(images, masks, "features")
-    table, _ = _engine().texture_features_batch(*upload(), sizes, int(Ng), tuple(classes),
+    table, _ = _engine().texture_features_batch(*upload(), sizes, batch_levels(Ng, len(sizes)), tuple(classes),
                                                 [int(d) for d in np.asarray(distances).ravel()], int(gldm_a),
                                                 bool(symmetricalGLCM), bool(mcc), False, bool(force2D), int(force2Ddimension),
                                                 weightingNorm, spacing)

@@ -20,7 +20,8 @@
 //   + PRAD_BATCH_TABLE_BYTES 16384  the largest table that must exist whole: one GLCM angle at 64 levels = 64 * 64 * 4
 //   + the ROI's bytes
 //   => PRAD_BATCH_MAX_VOX = 81920 - 16384 - 256 = 65280 voxels (a multiple of 16; 40^3 = 64000 fits).
-// Smaller batches ask for less (largest ROI of the batch, tables of its Ng), so small ROIs run many workgroups per CU.
+// Smaller batches ask for less (largest ROI of the batch, the largest table any ROI asks for with its own Ng), so small ROIs
+// run many workgroups per CU.  Every ROI carries its own Ng (BatchRoi.Ng): a workgroup sizes its passes from table_words / Ng.
 // Table counts stay below 2^32: a count is at most the voxels of the ROI; an NGTDM slot adds at most Nb * 63 per voxel,
 // 65280 * 254 * 63 < 2^30 -- hence PRAD_BATCH_MAX_NA (unidirectional angles; Nb = 2 Na neighbours).
 #pragma once
@@ -48,7 +49,7 @@ struct BatchRoi {
   int na, na_run;      // unidirectional angles of the requested distances (GLCM; GLDM / NGTDM use them in both directions)
                        // and of distance 1 (GLRLM)
   int ang, ang_run;    // their first row in the angle table (rows of 3 ints: dz, dy, dx)
-  int pad;
+  int Ng;              // the ROI's own grey-level count: its matrices have Ng rows and its masked levels lie in [1, Ng]
 };
 
 struct BatchArgs {
@@ -56,9 +57,10 @@ struct BatchArgs {
   const uint8_t *mask;
   const BatchRoi *rois;
   const int *angles;
-  int Ng, alpha;
+  int alpha;
   int groups_glcm, groups_glrlm, neigh;   // jobs per ROI: GLCM angle groups, GLRLM angle groups, 0 / 1 neighbourhood job
-  int table_words;                        // u32 words of the table region (<= PRAD_BATCH_TABLE_BYTES / 4)
+  int table_words;                        // u32 words of the table region (<= PRAD_BATCH_TABLE_BYTES / 4; at least Ng * Ng and
+                                          // 2 * (2 na + 1) of every ROI: its smallest whole table)
   double *glcm, *glrlm, *gldm, *ngtdm;    // NULL: family not asked for
   int *status;
 };
@@ -78,7 +80,7 @@ __global__ void __launch_bounds__(PRAD_BATCH_THREADS) batch_rois_kernel(BatchArg
   const int jobs = A.groups_glcm + A.groups_glrlm + A.neigh;
   const int b = (int)(blockIdx.x / (unsigned)jobs), job = (int)(blockIdx.x % (unsigned)jobs);
   const BatchRoi R = A.rois[b];
-  const int Ng = A.Ng, nx = R.nx, ny = R.ny, nz = R.nz;
+  const int Ng = R.Ng, nx = R.nx, ny = R.ny, nz = R.nz;   // (all from the workgroup's one record: uniform, so the pass splits are)
   const int plane = ny * nx, nvox = nz * plane;
 
   // ---- pack: one byte per voxel, 0 outside the mask; a masked level outside [1, Ng] is the reference's IndexError ----------

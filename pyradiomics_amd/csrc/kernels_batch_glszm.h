@@ -49,8 +49,8 @@
 // of the roots, and only then are the (level, size) pairs written to ints 0 .. 2 nzones - 1 of the region.  The tail of
 // the region beyond the pairs holds scratch values.  The distinct sizes are counted in a bitmap that reuses the level bytes.
 //
-// batch_glszm_fill_kernel histograms a ROI's zone list into float64, dense [Ng][max(maxRegion, 1)] or compact
-// [Ng][max(k, 1)] + the k distinct sizes ascending; every element of the slice is written by the ROI's workgroup.
+// batch_glszm_fill_kernel histograms a ROI's zone list into float64, Ng the ROI's own count, dense [Ng][max(maxRegion, 1)] or
+// compact [Ng][max(k, 1)] + the k distinct sizes ascending; every element of the slice is written by the ROI's workgroup.
 #pragma once
 #include "prad_runtime.h"
 
@@ -76,14 +76,13 @@ typedef __attribute__((address_space(3))) unsigned bz_lds_u32;
 struct BatchZoneRoi {
   long long off;       // first element of the ROI in the level / mask buffers; its zone list starts at int 2 * off
   int nz, ny, nx;
-  int pad;
+  int Ng;              // the ROI's own grey-level count: its masked levels lie in [1, Ng]
 };
 
 struct BatchZoneArgs {
   const int32_t *levels;
   const uint8_t *mask;
   const BatchZoneRoi *rois;
-  int Ng;
   int vox_bytes;       // voxels of the largest ROI, rounded up to 16: bytes of the level region, half the bytes of the labels
   int *zones, *summary, *status;
 };
@@ -129,7 +128,7 @@ __global__ void __launch_bounds__(PRAD_BZ_THREADS) batch_glszm_kernel(BatchZoneA
   const int tid = threadIdx.x, nthr = PRAD_BZ_THREADS;
   const int b = (int)blockIdx.x;
   const BatchZoneRoi R = A.rois[b];
-  const int Ng = A.Ng, nx = R.nx, ny = R.ny, nz = R.nz;
+  const int Ng = R.Ng, nx = R.nx, ny = R.ny, nz = R.nz;
   const int plane = ny * nx, nvox = nz * plane;
   int *zl = A.zones + 2 * R.off;      // the ROI's region: 2 * nvox ints
   int *scr = zl + nvox;               // zone sizes by root voxel, until the pairs are written
@@ -291,20 +290,22 @@ struct BatchFillRoi {
   long long zones;     // first int of the ROI's zone list
   long long out;       // first double of its matrix
   long long sizes;     // first int of its distinct sizes (compact)
-  int nzones, max_region, nsizes, pad;
+  int nzones, max_region, nsizes;
+  int Ng;              // rows of the ROI's matrix
 };
 
 // One workgroup per ROI.  A pair outside [1, Ng] x [1, max_region], or a size beyond the nsizes columns, is skipped: the
 // records come from the summary the labelling launch wrote, a caller that passes another cannot make the kernel write
 // outside the ROI's slice.
 __global__ void __launch_bounds__(PRAD_BZ_THREADS) batch_glszm_fill_kernel(const int *__restrict__ zones,
-                                                                              const BatchFillRoi *__restrict__ rois, int Ng,
-                                                                              int compact, double *out, int *sizes_out) {
+                                                                              const BatchFillRoi *__restrict__ rois, int compact,
+                                                                              double *out, int *sizes_out) {
   __shared__ unsigned bitmap[PRAD_BATCH_GLSZM_BITMAP_WORDS];
   __shared__ unsigned before[PRAD_BATCH_GLSZM_BITMAP_WORDS];      // set bits in the words below
   __shared__ unsigned waves[4];
   const int tid = threadIdx.x, nthr = PRAD_BZ_THREADS;
   const BatchFillRoi R = rois[blockIdx.x];
+  const int Ng = R.Ng;
   const int *zl = zones + R.zones;
   const int cols = max(compact ? R.nsizes : R.max_region, 1);
   double *o = out + R.out;

@@ -1,7 +1,8 @@
-// prad_batch.hip -- C ABI of the batched small-ROI texture matrices (include/pyradiomics_amd.h: prad_batch_plan[_f2d],
-// prad_calculate_batch[_f2d]_dev); translation unit of libpyradiomics_amd.so.  The kernel consumes an arbitrary angle table per
-// ROI, so the forced dimension (force2D) lives here alone: the counts and tables come from prad_get_angle_count /
-// prad_build_angles with it, the very functions the single calls use.
+// prad_batch.hip -- C ABI of the batched small-ROI texture matrices (include/pyradiomics_amd.h: prad_batch_plan[_f2d | _ng],
+// prad_calculate_batch[_f2d | _ng]_dev); translation unit of libpyradiomics_amd.so.  One implementation, on a grey-level count per
+// ROI (RoiLevels): the _ng entry points hand it their vector, the scalar ones one count for all.  The kernel consumes an
+// arbitrary angle table per ROI, so the forced dimension (force2D) lives here alone: the counts and tables come from
+// prad_get_angle_count / prad_build_angles with it, the very functions the single calls use.
 #include "kernels_batch.h"
 #include "prad_batch_common.h"
 
@@ -22,11 +23,11 @@ struct BatchLayout {
 
 // Shapes of the per-ROI outputs, the same arithmetic the single calls use: Na = prad_get_angle_count (unidirectional, forced
 // dimension f2d: -1 none, 0 / 1 / 2 the axis no angle may leave),
-// GLCM [Ng][Ng][Na], GLRLM [Ng][max(size)][Na1] (distance 1), GLDM [Ng][2 Nb + 1] with Nb = 2 Na, NGTDM [Ng][3].
+// GLCM [Ng][Ng][Na], GLRLM [Ng][max(size)][Na1] (distance 1), GLDM [Ng][2 Nb + 1] with Nb = 2 Na, NGTDM [Ng][3], Ng the ROI's own.
 // Host only: no device is touched.
-int batch_layout(const int *sizes, int B, int Ng, int families, const int *distances, int Ndist, int f2d, BatchLayout *lay) {
+int batch_layout(const int *sizes, int B, const RoiLevels &Ng, int families, const int *distances, int Ndist, int f2d, BatchLayout *lay) {
   PRAD_TRY(roi_count_check("batch", sizes, B, 0));
-  if (Ng < 1) return fail(PRAD_E_ARG, "batch: Ng=%d < 1", Ng);
+  PRAD_TRY(roi_levels_check("batch", Ng, B));
   if (!distances || Ndist < 1) return fail(PRAD_E_ARG, "batch: no distances");
   if (families < 1 || families > PRAD_BATCH_ALL) return fail(PRAD_E_ARG, "batch: families=%d outside [1, %d]", families, PRAD_BATCH_ALL);
   for (int k = 0; k < Ndist; k++)
@@ -35,10 +36,7 @@ int batch_layout(const int *sizes, int B, int Ng, int families, const int *dista
   PRAD_TRY(roi_sizes_check("batch", sizes, B, nullptr));
   lay->offsets.assign((size_t)4 * (B + 1), 0);
   lay->na.assign((size_t)2 * B, 0);
-  if (Ng > PRAD_BATCH_MAX_NG) {
-    lay->in_domain = false;
-    snprintf(lay->why, sizeof(lay->why), "Ng=%d above %d", Ng, PRAD_BATCH_MAX_NG);
-  }
+  if (roi_levels_above(Ng, B, PRAD_BATCH_MAX_NG, lay->why, sizeof(lay->why))) lay->in_domain = false;
   long long *o = lay->offsets.data();
   for (int b = 0; b < B; b++) {
     const int *sz = sizes + 3 * b;
@@ -55,13 +53,28 @@ int batch_layout(const int *sizes, int B, int Ng, int families, const int *dista
       lay->in_domain = false;
       snprintf(lay->why, sizeof(lay->why), "ROI %d has %d angles, above %d", b, na, PRAD_BATCH_MAX_NA);
     }
-    const long long Nr = std::max(sz[0], std::max(sz[1], sz[2]));
-    const long long per[4] = {(long long)Ng * Ng * na, (long long)Ng * Nr * na1, (long long)Ng * (4 * na + 1), (long long)Ng * 3};
+    const long long Nr = std::max(sz[0], std::max(sz[1], sz[2])), ng = Ng[b];
+    const long long per[4] = {ng * ng * na, ng * Nr * na1, ng * (4 * na + 1), ng * 3};
     for (int f = 0; f < 4; f++)
       o[(size_t)f * (B + 1) + b + 1] = o[(size_t)f * (B + 1) + b] + ((families >> f) & 1 ? per[f] : 0);
   }
   return PRAD_OK;
 }
+
+int batch_plan(const int *sizes, int B, const RoiLevels &Ng, int families, const int *distances, int Ndist, int force2Ddim,
+               long long *out_offsets, int *Na) {
+  if (!out_offsets || !Na) return fail(PRAD_E_ARG, "batch plan: NULL output");
+  BatchLayout lay;
+  PRAD_TRY(batch_layout(sizes, B, Ng, families, distances, Ndist, force2Ddim, &lay));
+  std::copy(lay.offsets.begin(), lay.offsets.end(), out_offsets);
+  std::copy(lay.na.begin(), lay.na.end(), Na);
+  if (!lay.in_domain) return fail(PRAD_E_UNSUPPORTED, "batch: %s (use the single calls per ROI)", lay.why);
+  return PRAD_OK;
+}
+
+int calculate_batch(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B, const RoiLevels &Ng,
+                    int families, const int *distances, int Ndist, int alpha, int force2Ddim, double *glcm, double *glrlm,
+                    double *gldm, double *ngtdm, int *status, void *stream);
 
 }  // namespace
 
@@ -74,13 +87,13 @@ extern "C" int prad_batch_plan(const int *sizes, int B, int Ng, int families, co
 
 extern "C" int prad_batch_plan_f2d(const int *sizes, int B, int Ng, int families, const int *distances, int Ndist,
                                    int force2Ddim, long long *out_offsets, int *Na) {
-  if (!out_offsets || !Na) return fail(PRAD_E_ARG, "batch plan: NULL output");
-  BatchLayout lay;
-  PRAD_TRY(batch_layout(sizes, B, Ng, families, distances, Ndist, force2Ddim, &lay));
-  std::copy(lay.offsets.begin(), lay.offsets.end(), out_offsets);
-  std::copy(lay.na.begin(), lay.na.end(), Na);
-  if (!lay.in_domain) return fail(PRAD_E_UNSUPPORTED, "batch: %s (use the single calls per ROI)", lay.why);
-  return PRAD_OK;
+  return batch_plan(sizes, B, RoiLevels{nullptr, Ng}, families, distances, Ndist, force2Ddim, out_offsets, Na);
+}
+
+extern "C" int prad_batch_plan_ng(const int *sizes, int B, const int *Ng, int families, const int *distances, int Ndist,
+                                  int force2Ddim, long long *out_offsets, int *Na) {
+  if (B > 0 && !Ng) return fail(PRAD_E_ARG, "batch plan: Ng is NULL");
+  return batch_plan(sizes, B, RoiLevels{Ng, 1}, families, distances, Ndist, force2Ddim, out_offsets, Na);
 }
 
 extern "C" int prad_calculate_batch_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off,
@@ -95,6 +108,24 @@ extern "C" int prad_calculate_batch_f2d_dev(const int32_t *levels, const uint8_t
                                             int B, int Ng, int families, const int *distances, int Ndist, int alpha,
                                             int force2Ddim, double *glcm, double *glrlm, double *gldm, double *ngtdm,
                                             int *status, void *stream) {
+  return calculate_batch(levels, mask, sizes, off, B, RoiLevels{nullptr, Ng}, families, distances, Ndist, alpha, force2Ddim, glcm,
+                         glrlm, gldm, ngtdm, status, stream);
+}
+
+extern "C" int prad_calculate_batch_ng_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off,
+                                           int B, const int *Ng, int families, const int *distances, int Ndist, int alpha,
+                                           int force2Ddim, double *glcm, double *glrlm, double *gldm, double *ngtdm,
+                                           int *status, void *stream) {
+  if (B > 0 && !Ng) return fail(PRAD_E_ARG, "batch: Ng is NULL");
+  return calculate_batch(levels, mask, sizes, off, B, RoiLevels{Ng, 1}, families, distances, Ndist, alpha, force2Ddim, glcm, glrlm,
+                         gldm, ngtdm, status, stream);
+}
+
+namespace {
+
+int calculate_batch(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B, const RoiLevels &Ng,
+                    int families, const int *distances, int Ndist, int alpha, int force2Ddim, double *glcm, double *glrlm,
+                    double *gldm, double *ngtdm, int *status, void *stream) {
   BatchLayout lay;
   PRAD_TRY(batch_layout(sizes, B, Ng, families, distances, Ndist, force2Ddim, &lay));
   if (!lay.in_domain) return fail(PRAD_E_UNSUPPORTED, "batch: %s (use the single calls per ROI)", lay.why);   // nothing launched
@@ -120,7 +151,10 @@ extern "C" int prad_calculate_batch_f2d_dev(const int32_t *levels, const uint8_t
   BatchRoi *rois = table.host;
   int *angles = (int *)table.host_tail();
   long long max_vox = 1;
-  int max_na = 0, max_nr = 1;
+  // table region, the most any ROI asks for with its own Ng: up to PRAD_BATCH_ANGLES_AT_ONCE angles of GLCM / GLRLM at once,
+  // every level of GLDM + NGTDM; and the least every ROI needs: one GLCM angle (hence one GLRLM column per level), one level
+  // of GLDM + NGTDM
+  long long want[3] = {0, 0, 0}, floor_words = 1;
   size_t row = 0;
   for (int b = 0; b < B; b++) {
     const int *sz = sizes + 3 * b;
@@ -130,7 +164,7 @@ extern "C" int prad_calculate_batch_f2d_dev(const int32_t *levels, const uint8_t
     r.nz = sz[0], r.ny = sz[1], r.nx = sz[2];
     r.na = lay.na[b];
     r.na_run = lay.na[(size_t)B + b];
-    r.pad = 0;
+    r.Ng = Ng[b];
     r.ang = (int)row;
     if (r.na > 0 && prad_build_angles(sz, distances, 3, Ndist, force2Ddim, r.na, angles + 3 * row) != 0)
       return fail(PRAD_E_ARG, "batch: angles of ROI %d", b);
@@ -143,8 +177,11 @@ extern "C" int prad_calculate_batch_f2d_dev(const int32_t *levels, const uint8_t
       row += (size_t)r.na_run;
     }
     max_vox = std::max(max_vox, roi_nvox(sizes, b));
-    max_na = std::max(max_na, r.na);
-    max_nr = std::max(max_nr, std::max(sz[0], std::max(sz[1], sz[2])));
+    const long long ng = r.Ng, nr = std::max(sz[0], std::max(sz[1], sz[2])), W = 2LL * r.na + 1;
+    want[0] = std::max(want[0], PRAD_BATCH_ANGLES_AT_ONCE * ng * ng);
+    want[1] = std::max(want[1], PRAD_BATCH_ANGLES_AT_ONCE * ng * nr);
+    want[2] = std::max(want[2], 2 * W * ng);
+    floor_words = std::max(floor_words, std::max(ng * ng, 2 * W));
   }
 
   // ---- launch geometry ------------------------------------------------------------------------------------------------------
@@ -153,7 +190,6 @@ extern "C" int prad_calculate_batch_f2d_dev(const int32_t *levels, const uint8_t
   A.mask = mask;
   A.rois = table.dev;
   A.angles = (const int *)table.dev_tail();
-  A.Ng = Ng;
   A.alpha = alpha;
   A.glcm = outs[0], A.glrlm = outs[1], A.gldm = outs[2], A.ngtdm = outs[3];
   A.status = status;
@@ -167,15 +203,12 @@ extern "C" int prad_calculate_batch_f2d_dev(const int32_t *levels, const uint8_t
   A.groups_glrlm = outs[1] ? groups : 0;
   A.neigh = (outs[2] || outs[3]) ? 1 : 0;
   if (!A.groups_glcm && !A.groups_glrlm) A.neigh = 1;   // (only empty matrices asked for: a job per ROI still gives its status)
-  // table region: up to PRAD_BATCH_ANGLES_AT_ONCE angles of GLCM / GLRLM at once, every level of GLDM + NGTDM, within the
-  // budget; never below one GLCM angle, one GLRLM column per level, one level of GLDM + NGTDM
-  const long long W = 2LL * max_na + 1;
   long long words = 64;
-  if (outs[0]) words = std::max(words, (long long)PRAD_BATCH_ANGLES_AT_ONCE * Ng * Ng);
-  if (outs[1]) words = std::max(words, (long long)PRAD_BATCH_ANGLES_AT_ONCE * Ng * max_nr);
-  if (A.neigh) words = std::max(words, 2 * W * Ng);
+  if (outs[0]) words = std::max(words, want[0]);
+  if (outs[1]) words = std::max(words, want[1]);
+  if (A.neigh) words = std::max(words, want[2]);
   words = std::min<long long>(words, PRAD_BATCH_TABLE_BYTES / 4);
-  words = std::max<long long>(words, std::max<long long>((long long)Ng * Ng, 2 * W));   // (both below the budget: Ng <= 64, Na <= 127)
+  words = std::max<long long>(words, floor_words);   // (below the budget: Ng <= 64, Na <= 127)
   A.table_words = (int)words;
   const size_t lds = PRAD_BATCH_MISC_BYTES + 4 * (size_t)words + (((size_t)max_vox + 15) & ~(size_t)15);
   if (lds > 160 * 1024 / 2) return fail(PRAD_E_HIP, "batch: %zu bytes of LDS per workgroup", lds);
@@ -189,3 +222,5 @@ extern "C" int prad_calculate_batch_f2d_dev(const int32_t *levels, const uint8_t
     return check_launch("batch_rois_kernel");
   });
 }
+
+}  // namespace

@@ -34,6 +34,42 @@ static inline int roi_offsets_check(const char *what, const long long *off, int 
   return PRAD_OK;
 }
 
+// The grey-level count of every ROI of a call: the host vector [B] of the *_ng entry points, or -- v == NULL -- one count for
+// all of them (the scalar entry points, which so share the implementation without building a vector).
+struct RoiLevels {
+  const int *v;
+  int all;
+  int operator[](int b) const { return v ? v[b] : all; }
+  int most(int B) const {
+    if (!v) return all;
+    int m = 1;
+    for (int b = 0; b < B; b++) m = v[b] > m ? v[b] : m;
+    return m;
+  }
+};
+
+// every count is >= 1
+static inline int roi_levels_check(const char *what, const RoiLevels &Ng, int B) {
+  if (!Ng.v) return Ng.all < 1 ? fail(PRAD_E_ARG, "%s: Ng=%d < 1", what, Ng.all) : (int)PRAD_OK;
+  for (int b = 0; b < B; b++)
+    if (Ng.v[b] < 1) return fail(PRAD_E_ARG, "%s: ROI %d has Ng=%d < 1", what, b, Ng.v[b]);
+  return PRAD_OK;
+}
+
+// true when a count lies above `cap`; `why` (of `n` bytes) then says which
+static inline bool roi_levels_above(const RoiLevels &Ng, int B, int cap, char *why, size_t n) {
+  if (!Ng.v) {
+    if (Ng.all > cap) snprintf(why, n, "Ng=%d above %d", Ng.all, cap);
+    return Ng.all > cap;
+  }
+  for (int b = 0; b < B; b++)
+    if (Ng.v[b] > cap) {
+      snprintf(why, n, "ROI %d has Ng=%d above %d", b, Ng.v[b], cap);
+      return true;
+    }
+  return false;
+}
+
 // The per-ROI records of one call: a pinned host block the entry point fills and the device block the kernel reads, both kept
 // under the workspace name `slot`; `tail` more bytes (16-byte aligned) follow the records in the same upload.
 template <typename Rec>

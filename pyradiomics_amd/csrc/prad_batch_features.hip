@@ -1,5 +1,6 @@
 // prad_batch_features.hip -- C ABI of the batched feature formulas (include/pyradiomics_amd.h: prad_batch_features_plan,
-// prad_batch_features_dev); translation unit of libpyradiomics_amd.so.
+// prad_batch_features_plan_ng, prad_batch_features[_ng]_dev); translation unit of libpyradiomics_amd.so.  One implementation, on a
+// grey-level count per ROI (RoiLevels): the _ng entry points hand it their vector, the scalar ones one count for all.
 #include "kernels_batch_features.h"
 #include "prad_batch_common.h"
 
@@ -15,6 +16,7 @@ struct FeatLayout {
   std::vector<long long> offsets;   // [2][5][B + 1]: first double of out, first row (= empty flag)
   long long nrec = 0, nglcm = 0, scratch = 0;
   bool in_domain = true;
+  char why[96] = {0};
 };
 
 // rows of ROI b in family f
@@ -22,9 +24,9 @@ inline int rows_of(int f, int b, int B, const int *Na) { return f == BF_GLCM ? N
 inline bool has_glszm(const int *glszm_cols, int b) { return glszm_cols[b] >= 1; }
 
 // Host only: no device is touched.
-int features_layout(const int *sizes, int B, int Ng, int families, const int *Na, const int *glszm_cols, FeatLayout *lay) {
+int features_layout(const int *sizes, int B, const RoiLevels &Ng, int families, const int *Na, const int *glszm_cols, FeatLayout *lay) {
   if (B < 0 || (B > 0 && (!sizes || !Na))) return fail(PRAD_E_ARG, "batch features: B=%d, sizes=%p, Na=%p", B, (const void *)sizes, (const void *)Na);
-  if (Ng < 1) return fail(PRAD_E_ARG, "batch features: Ng=%d < 1", Ng);
+  PRAD_TRY(roi_levels_check("batch features", Ng, B));
   if (families < 1 || families > PRAD_BATCH_FEATURES_ALL) return fail(PRAD_E_ARG, "batch features: families=%d outside [1, %d]", families, PRAD_BATCH_FEATURES_ALL);
   if ((families & PRAD_BATCH_GLSZM) && B > 0 && !glszm_cols) return fail(PRAD_E_ARG, "batch features: GLSZM without its column counts");
   for (int b = 0; b < B; b++) {
@@ -32,7 +34,7 @@ int features_layout(const int *sizes, int B, int Ng, int families, const int *Na
       if (sizes[3 * b + d] < 1) return fail(PRAD_E_ARG, "batch features: ROI %d has size[%d]=%d < 1", b, d, sizes[3 * b + d]);
     if (Na[b] < 0 || Na[(size_t)B + b] < 0) return fail(PRAD_E_ARG, "batch features: negative angle count of ROI %d", b);
   }
-  lay->in_domain = Ng <= PRAD_BF_MAX_NG;
+  lay->in_domain = !roi_levels_above(Ng, B, PRAD_BF_MAX_NG, lay->why, sizeof(lay->why));
   lay->offsets.assign((size_t)2 * BF_KINDS * (B + 1), 0);
   long long *el = lay->offsets.data(), *row = el + (size_t)BF_KINDS * (B + 1);
   long long e = 0, r = 0;
@@ -50,23 +52,30 @@ int features_layout(const int *sizes, int B, int Ng, int families, const int *Na
       if (f == BF_GLCM) lay->nglcm += n;
       const int *sz = sizes + 3 * b;
       const long long nj = f == BF_GLRLM ? std::max(sz[0], std::max(sz[1], sz[2])) : (f == BF_GLDM ? 4LL * Na[b] + 1 : (f == BF_GLSZM ? glszm_cols[b] : 0));
-      if (rec && (f == BF_GLRLM || f == BF_GLDM || f == BF_GLSZM)) lay->scratch += (long long)n * (Ng + nj);
+      if (rec && (f == BF_GLRLM || f == BF_GLDM || f == BF_GLSZM)) lay->scratch += (long long)n * (Ng[b] + nj);
     }
   }
   return PRAD_OK;
 }
 
+int features_plan(const int *sizes, int B, const RoiLevels &Ng, int families, const int *Na, const int *glszm_cols,
+                  long long *out_offsets, long long *nrec);
+int features_dev(const int *sizes, int B, const RoiLevels &Ng, int families, const int *Na, const int *glszm_cols, const double *glcm,
+                 const double *glrlm, const double *gldm, const double *ngtdm, const long long *offsets, const double *glszm,
+                 const long long *glszm_offsets, const int *glszm_sizes, const long long *glszm_sizes_offsets, int symmetric,
+                 int want_mcc, double *out, int *empty, void *stream);
+
 }  // namespace
 
 extern "C" int prad_batch_features_plan(const int *sizes, int B, int Ng, int families, const int *Na, const int *glszm_cols,
                                         long long *out_offsets, long long *nrec) {
-  if (!out_offsets || !nrec) return fail(PRAD_E_ARG, "batch features plan: NULL output");
-  FeatLayout lay;
-  PRAD_TRY(features_layout(sizes, B, Ng, families, Na, glszm_cols, &lay));
-  std::copy(lay.offsets.begin(), lay.offsets.end(), out_offsets);
-  nrec[0] = lay.nrec, nrec[1] = lay.nglcm, nrec[2] = lay.scratch;
-  if (!lay.in_domain) return fail(PRAD_E_UNSUPPORTED, "batch features: Ng=%d above %d (use the single calls per ROI)", Ng, PRAD_BF_MAX_NG);
-  return PRAD_OK;
+  return features_plan(sizes, B, RoiLevels{nullptr, Ng}, families, Na, glszm_cols, out_offsets, nrec);
+}
+
+extern "C" int prad_batch_features_plan_ng(const int *sizes, int B, const int *Ng, int families, const int *Na,
+                                           const int *glszm_cols, long long *out_offsets, long long *nrec) {
+  if (B > 0 && !Ng) return fail(PRAD_E_ARG, "batch features plan: Ng is NULL");
+  return features_plan(sizes, B, RoiLevels{Ng, 1}, families, Na, glszm_cols, out_offsets, nrec);
 }
 
 extern "C" int prad_batch_features_dev(const int *sizes, int B, int Ng, int families, const int *Na, const int *glszm_cols,
@@ -74,9 +83,41 @@ extern "C" int prad_batch_features_dev(const int *sizes, int B, int Ng, int fami
                                        const long long *offsets, const double *glszm, const long long *glszm_offsets,
                                        const int *glszm_sizes, const long long *glszm_sizes_offsets, int symmetric,
                                        int want_mcc, double *out, int *empty, void *stream) {
+  return features_dev(sizes, B, RoiLevels{nullptr, Ng}, families, Na, glszm_cols, glcm, glrlm, gldm, ngtdm, offsets, glszm,
+                      glszm_offsets, glszm_sizes, glszm_sizes_offsets, symmetric, want_mcc, out, empty, stream);
+}
+
+extern "C" int prad_batch_features_ng_dev(const int *sizes, int B, const int *Ng, int families, const int *Na,
+                                          const int *glszm_cols, const double *glcm, const double *glrlm, const double *gldm,
+                                          const double *ngtdm, const long long *offsets, const double *glszm,
+                                          const long long *glszm_offsets, const int *glszm_sizes,
+                                          const long long *glszm_sizes_offsets, int symmetric, int want_mcc, double *out,
+                                          int *empty, void *stream) {
+  if (B > 0 && !Ng) return fail(PRAD_E_ARG, "batch features: Ng is NULL");
+  return features_dev(sizes, B, RoiLevels{Ng, 1}, families, Na, glszm_cols, glcm, glrlm, gldm, ngtdm, offsets, glszm, glszm_offsets,
+                      glszm_sizes, glszm_sizes_offsets, symmetric, want_mcc, out, empty, stream);
+}
+
+namespace {
+
+int features_plan(const int *sizes, int B, const RoiLevels &Ng, int families, const int *Na, const int *glszm_cols,
+                  long long *out_offsets, long long *nrec) {
+  if (!out_offsets || !nrec) return fail(PRAD_E_ARG, "batch features plan: NULL output");
   FeatLayout lay;
   PRAD_TRY(features_layout(sizes, B, Ng, families, Na, glszm_cols, &lay));
-  if (!lay.in_domain) return fail(PRAD_E_UNSUPPORTED, "batch features: Ng=%d above %d (use the single calls per ROI)", Ng, PRAD_BF_MAX_NG);   // nothing launched
+  std::copy(lay.offsets.begin(), lay.offsets.end(), out_offsets);
+  nrec[0] = lay.nrec, nrec[1] = lay.nglcm, nrec[2] = lay.scratch;
+  if (!lay.in_domain) return fail(PRAD_E_UNSUPPORTED, "batch features: %s (use the single calls per ROI)", lay.why);
+  return PRAD_OK;
+}
+
+int features_dev(const int *sizes, int B, const RoiLevels &Ng, int families, const int *Na, const int *glszm_cols, const double *glcm,
+                 const double *glrlm, const double *gldm, const double *ngtdm, const long long *offsets, const double *glszm,
+                 const long long *glszm_offsets, const int *glszm_sizes, const long long *glszm_sizes_offsets, int symmetric,
+                 int want_mcc, double *out, int *empty, void *stream) {
+  FeatLayout lay;
+  PRAD_TRY(features_layout(sizes, B, Ng, families, Na, glszm_cols, &lay));
+  if (!lay.in_domain) return fail(PRAD_E_UNSUPPORTED, "batch features: %s (use the single calls per ROI)", lay.why);   // nothing launched
   if (B == 0 || lay.nrec == 0) return PRAD_OK;
   const double *mats[BF_KINDS] = {glcm, glrlm, gldm, ngtdm, glszm};
   if (!out || !empty) return fail(PRAD_E_ARG, "batch features: NULL output");
@@ -109,7 +150,8 @@ extern "C" int prad_batch_features_dev(const int *sizes, int B, int Ng, int fami
       const long long mat = f == BF_GLSZM ? glszm_offsets[b] : offsets[(size_t)f * (B + 1) + b];
       if (mat < 0) return fail(PRAD_E_ARG, "batch features: negative offset of ROI %d, family %d", b, f);
       const int *sz = sizes + 3 * b;
-      int Nj = Ng, NaM = 1;
+      const int ng = Ng[b];
+      int Nj = ng, NaM = 1;
       if (f == BF_GLCM) NaM = n;
       else if (f == BF_GLRLM) Nj = std::max(sz[0], std::max(sz[1], sz[2])), NaM = n;
       else if (f == BF_GLDM) Nj = 4 * Na[b] + 1;
@@ -120,12 +162,12 @@ extern "C" int prad_batch_features_dev(const int *sizes, int B, int Ng, int fami
         BatchFeatRec &r = recs[k++];
         r.mat = mat;
         r.scratch = zone ? scr : 0;
-        if (zone) scr += (long long)Ng + Nj;
+        if (zone) scr += (long long)ng + Nj;
         r.out = el[(size_t)f * (B + 1) + b] + (long long)a * kRow[f];
         r.sizes = (f == BF_GLSZM && glszm_sizes) ? glszm_sizes_offsets[b] : -1;
         r.empty = (int)(row[(size_t)f * (B + 1) + b] + a);
         r.kind = f, r.roi = b, r.a = a;
-        r.Ni = Ng, r.Nj = Nj, r.Na = NaM, r.pad = 0;
+        r.Ni = ng, r.Nj = Nj, r.Na = NaM, r.pad = 0;
       }
     }
   }
@@ -141,8 +183,9 @@ extern "C" int prad_batch_features_dev(const int *sizes, int B, int Ng, int fami
   A.empty = empty;
   A.symmetric = symmetric ? 1 : 0;
   A.mcc = mcc ? 1 : 0;
-  const size_t lds = sizeof(double) * batch_features_lds_doubles(Ng);
-  const size_t mcc_lds = ((mcc_scratch_bytes(Ng, Ng) + 15) & ~(size_t)15) + sizeof(double) * (size_t)Ng * Ng;   // staged
+  const int most = Ng.most(B);      // LDS by the largest count of the batch; a workgroup lays its own out by its record's Ni
+  const size_t lds = sizeof(double) * batch_features_lds_doubles(most);
+  const size_t mcc_lds = ((mcc_scratch_bytes(most, most) + 15) & ~(size_t)15) + sizeof(double) * (size_t)most * most;   // staged
 
   return batch_call(c, s, table, "batch-features", [&]() {
     if (mcc) {
@@ -157,3 +200,5 @@ extern "C" int prad_batch_features_dev(const int *sizes, int B, int Ng, int fami
     return check_launch("batch_mcc_kernel");
   });
 }
+
+}  // namespace

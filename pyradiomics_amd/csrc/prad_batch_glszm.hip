@@ -1,5 +1,6 @@
 // prad_batch_glszm.hip -- C ABI of the batched small-ROI GLSZM (include/pyradiomics_amd.h: prad_batch_glszm_max_vox,
-// prad_batch_glszm[_f2d]_dev, prad_batch_glszm_fill_dev); translation unit of libpyradiomics_amd.so.
+// prad_batch_glszm[_f2d | _ng]_dev, prad_batch_glszm_fill[_ng]_dev); translation unit of libpyradiomics_amd.so.  One implementation,
+// on a grey-level count per ROI (RoiLevels): the _ng entry points hand it their vector, the scalar ones one count for all.
 #include "kernels_batch_glszm.h"
 #include "prad_batch_common.h"
 
@@ -19,6 +20,11 @@ int launch_zones(Context &c, hipStream_t s, int B, size_t lds, const BatchZoneAr
   return check_launch("batch_glszm_kernel");
 }
 
+int batch_glszm(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B, const RoiLevels &Ng,
+                int force2Ddim, int *zones, int *summary, int *status, void *stream);
+int batch_glszm_fill(const int *zones, const int *summary_host, const long long *off, int B, const RoiLevels &Ng, int compact,
+                     double *out, const long long *out_offsets, int *sizes_out, const long long *sizes_offsets, void *stream);
+
 }  // namespace
 
 extern "C" int prad_batch_glszm_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B,
@@ -28,15 +34,43 @@ extern "C" int prad_batch_glszm_dev(const int32_t *levels, const uint8_t *mask, 
 
 extern "C" int prad_batch_glszm_f2d_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B,
                                         int Ng, int force2Ddim, int *zones, int *summary, int *status, void *stream) {
+  return batch_glszm(levels, mask, sizes, off, B, RoiLevels{nullptr, Ng}, force2Ddim, zones, summary, status, stream);
+}
+
+extern "C" int prad_batch_glszm_ng_dev(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B,
+                                       const int *Ng, int force2Ddim, int *zones, int *summary, int *status, void *stream) {
+  if (B > 0 && !Ng) return fail(PRAD_E_ARG, "batch GLSZM: Ng is NULL");
+  return batch_glszm(levels, mask, sizes, off, B, RoiLevels{Ng, 1}, force2Ddim, zones, summary, status, stream);
+}
+
+extern "C" int prad_batch_glszm_fill_dev(const int *zones, const int *summary_host, const long long *off, int B, int Ng,
+                                         int compact, double *out, const long long *out_offsets, int *sizes_out,
+                                         const long long *sizes_offsets, void *stream) {
+  return batch_glszm_fill(zones, summary_host, off, B, RoiLevels{nullptr, Ng}, compact, out, out_offsets, sizes_out, sizes_offsets,
+                          stream);
+}
+
+extern "C" int prad_batch_glszm_fill_ng_dev(const int *zones, const int *summary_host, const long long *off, int B, const int *Ng,
+                                            int compact, double *out, const long long *out_offsets, int *sizes_out,
+                                            const long long *sizes_offsets, void *stream) {
+  if (B > 0 && !Ng) return fail(PRAD_E_ARG, "batch GLSZM fill: Ng is NULL");
+  return batch_glszm_fill(zones, summary_host, off, B, RoiLevels{Ng, 1}, compact, out, out_offsets, sizes_out, sizes_offsets, stream);
+}
+
+namespace {
+
+int batch_glszm(const int32_t *levels, const uint8_t *mask, const int *sizes, const long long *off, int B, const RoiLevels &Ng,
+                int force2Ddim, int *zones, int *summary, int *status, void *stream) {
   PRAD_TRY(roi_count_check("batch GLSZM", sizes, B, 0));
-  if (Ng < 1) return fail(PRAD_E_ARG, "batch GLSZM: Ng=%d < 1", Ng);
+  PRAD_TRY(roi_levels_check("batch GLSZM", Ng, B));
   if (force2Ddim < -1 || force2Ddim > 2) return fail(PRAD_E_ARG, "batch GLSZM: forced dimension %d outside [-1, 2]", force2Ddim);
   long long max_vox = 1;
   PRAD_TRY(roi_sizes_check("batch GLSZM", sizes, B, &max_vox));
   if (B > 0 && (!levels || !mask || !off || !zones || !summary || !status)) return fail(PRAD_E_ARG, "batch GLSZM: NULL pointer");
   PRAD_TRY(roi_offsets_check("batch GLSZM", off, B));
   // valid arguments outside the domain: nothing is launched
-  if (Ng > PRAD_BZ_MAX_NG) return fail(PRAD_E_UNSUPPORTED, "batch GLSZM: Ng=%d above %d (use the single call per ROI)", Ng, PRAD_BZ_MAX_NG);
+  char why[96];
+  if (roi_levels_above(Ng, B, PRAD_BZ_MAX_NG, why, sizeof(why))) return fail(PRAD_E_UNSUPPORTED, "batch GLSZM: %s (use the single call per ROI)", why);
   for (int b = 0; b < B; b++)
     if (roi_nvox(sizes, b) > PRAD_BATCH_GLSZM_MAX_VOX)
       return fail(PRAD_E_UNSUPPORTED, "batch GLSZM: ROI %d holds %lld voxels, above %d (use the single call per ROI)", b,
@@ -52,13 +86,12 @@ extern "C" int prad_batch_glszm_f2d_dev(const int32_t *levels, const uint8_t *ma
   for (int b = 0; b < B; b++) {
     rois[b].off = off[b];
     rois[b].nz = sizes[3 * b], rois[b].ny = sizes[3 * b + 1], rois[b].nx = sizes[3 * b + 2];
-    rois[b].pad = 0;
+    rois[b].Ng = Ng[b];
   }
   BatchZoneArgs A;
   A.levels = levels;
   A.mask = mask;
   A.rois = table.dev;
-  A.Ng = Ng;
   A.vox_bytes = (int)((max_vox + 15) & ~15LL);
   A.zones = zones;
   A.summary = summary;
@@ -77,11 +110,10 @@ extern "C" int prad_batch_glszm_f2d_dev(const int32_t *levels, const uint8_t *ma
   });
 }
 
-extern "C" int prad_batch_glszm_fill_dev(const int *zones, const int *summary_host, const long long *off, int B, int Ng,
-                                         int compact, double *out, const long long *out_offsets, int *sizes_out,
-                                         const long long *sizes_offsets, void *stream) {
+int batch_glszm_fill(const int *zones, const int *summary_host, const long long *off, int B, const RoiLevels &Ng, int compact,
+                     double *out, const long long *out_offsets, int *sizes_out, const long long *sizes_offsets, void *stream) {
   if (B < 0) return fail(PRAD_E_ARG, "batch GLSZM fill: B=%d", B);
-  if (Ng < 1) return fail(PRAD_E_ARG, "batch GLSZM fill: Ng=%d < 1", Ng);
+  PRAD_TRY(roi_levels_check("batch GLSZM fill", Ng, B));
   if (B > 0 && (!zones || !summary_host || !off || !out || !out_offsets || (compact && (!sizes_out || !sizes_offsets))))
     return fail(PRAD_E_ARG, "batch GLSZM fill: NULL pointer");
   for (int b = 0; b < B; b++) {
@@ -91,7 +123,8 @@ extern "C" int prad_batch_glszm_fill_dev(const int *zones, const int *summary_ho
     if (sm[0] < 0 || sm[1] < 0 || sm[1] > PRAD_BATCH_GLSZM_MAX_VOX || sm[2] < 0 || sm[2] > sm[1] || sm[0] > PRAD_BATCH_GLSZM_MAX_VOX)
       return fail(PRAD_E_ARG, "batch GLSZM fill: summary of ROI %d is (%d, %d, %d)", b, sm[0], sm[1], sm[2]);
   }
-  if (Ng > PRAD_BZ_MAX_NG) return fail(PRAD_E_UNSUPPORTED, "batch GLSZM fill: Ng=%d above %d", Ng, PRAD_BZ_MAX_NG);
+  char why[96];
+  if (roi_levels_above(Ng, B, PRAD_BZ_MAX_NG, why, sizeof(why))) return fail(PRAD_E_UNSUPPORTED, "batch GLSZM fill: %s", why);
   if (B == 0) return PRAD_OK;
   Context &c = ctx();
   PRAD_TRY(c.ensure_device());
@@ -106,12 +139,14 @@ extern "C" int prad_batch_glszm_fill_dev(const int *zones, const int *summary_ho
     rois[b].nzones = summary_host[3 * b];
     rois[b].max_region = summary_host[3 * b + 1];
     rois[b].nsizes = summary_host[3 * b + 2];
-    rois[b].pad = 0;
+    rois[b].Ng = Ng[b];
   }
   return batch_call(c, s, table, "batch-glszm-lds", [&]() {
     Timed t(c, "batch_glszm", s);
-    hipLaunchKernelGGL(batch_glszm_fill_kernel, dim3((unsigned)B), dim3(PRAD_BZ_THREADS), 0, s, zones, table.dev, Ng,
-                       compact ? 1 : 0, out, sizes_out);
+    hipLaunchKernelGGL(batch_glszm_fill_kernel, dim3((unsigned)B), dim3(PRAD_BZ_THREADS), 0, s, zones, table.dev, compact ? 1 : 0,
+                       out, sizes_out);
     return check_launch("batch_glszm_fill_kernel");
   });
 }
+
+}  // namespace

@@ -1,5 +1,6 @@
 // prad_batch_merge.hip -- C ABI of the weighted angle merge of the batched small-ROI route (include/pyradiomics_amd.h:
-// prad_batch_merge_plan, prad_batch_merge_angles_dev); translation unit of libpyradiomics_amd.so.
+// prad_batch_merge_plan[_ng], prad_batch_merge_angles[_ng]_dev); translation unit of libpyradiomics_amd.so.  One implementation, on
+// a grey-level count per ROI (RoiLevels): the _ng entry points hand it their vector, the scalar ones one count for all.
 #include "kernels_batch_merge.h"
 #include "prad_batch_common.h"
 
@@ -19,10 +20,10 @@ inline long long cells_of(int f, const int *sz, int Ng) {
 }
 
 // Host only: no device is touched.
-int merge_layout(const int *sizes, int B, int Ng, int families, const int *Na, MergeLayout *lay) {
+int merge_layout(const int *sizes, int B, const RoiLevels &Ng, int families, const int *Na, MergeLayout *lay) {
   PRAD_TRY(roi_count_check("batch merge", sizes, B, 0));
   if (B > 0 && !Na) return fail(PRAD_E_ARG, "batch merge: Na is NULL");
-  if (Ng < 1) return fail(PRAD_E_ARG, "batch merge: Ng=%d < 1", Ng);
+  PRAD_TRY(roi_levels_check("batch merge", Ng, B));
   if (families < 1 || (families & ~(PRAD_BATCH_GLCM | PRAD_BATCH_GLRLM)))
     return fail(PRAD_E_ARG, "batch merge: families=%d is no subset of GLCM | GLRLM", families);
   PRAD_TRY(roi_sizes_check("batch merge", sizes, B, nullptr));
@@ -32,7 +33,7 @@ int merge_layout(const int *sizes, int B, int Ng, int families, const int *Na, M
     const int *sz = sizes + 3 * b;
     if (Na[b] < 0 || Na[(size_t)B + b] < 0) return fail(PRAD_E_ARG, "batch merge: negative angle count of ROI %d", b);
     for (int f = 0; f < 2; f++) {
-      const long long cells = (families >> f) & 1 ? cells_of(f, sz, Ng) : 0;
+      const long long cells = (families >> f) & 1 ? cells_of(f, sz, Ng[b]) : 0;
       if (cells > 0x7fffffffLL) return fail(PRAD_E_UNSUPPORTED, "batch merge: ROI %d has %lld cells", b, cells);
       o[(size_t)f * (B + 1) + b + 1] = o[(size_t)f * (B + 1) + b] + cells;
       lay->nrec += (cells + PRAD_BM_CELLS - 1) / PRAD_BM_CELLS;
@@ -42,9 +43,42 @@ int merge_layout(const int *sizes, int B, int Ng, int families, const int *Na, M
   return PRAD_OK;
 }
 
+int merge_plan(const int *sizes, int B, const RoiLevels &Ng, int families, const int *Na, long long *out_offsets);
+int merge_angles(const int *sizes, int B, const RoiLevels &Ng, int families, const int *Na, const double *glcm, const double *glrlm,
+                 const long long *offsets, const double *weights, const int *status, int symmetric, double *glcm_w,
+                 double *glrlm_w, void *stream);
+
 }  // namespace
 
 extern "C" int prad_batch_merge_plan(const int *sizes, int B, int Ng, int families, const int *Na, long long *out_offsets) {
+  return merge_plan(sizes, B, RoiLevels{nullptr, Ng}, families, Na, out_offsets);
+}
+
+extern "C" int prad_batch_merge_plan_ng(const int *sizes, int B, const int *Ng, int families, const int *Na,
+                                        long long *out_offsets) {
+  if (B > 0 && !Ng) return fail(PRAD_E_ARG, "batch merge plan: Ng is NULL");
+  return merge_plan(sizes, B, RoiLevels{Ng, 1}, families, Na, out_offsets);
+}
+
+extern "C" int prad_batch_merge_angles_dev(const int *sizes, int B, int Ng, int families, const int *Na, const double *glcm,
+                                           const double *glrlm, const long long *offsets, const double *weights,
+                                           const int *status, int symmetric, double *glcm_w, double *glrlm_w, void *stream) {
+  return merge_angles(sizes, B, RoiLevels{nullptr, Ng}, families, Na, glcm, glrlm, offsets, weights, status, symmetric, glcm_w,
+                      glrlm_w, stream);
+}
+
+extern "C" int prad_batch_merge_angles_ng_dev(const int *sizes, int B, const int *Ng, int families, const int *Na,
+                                              const double *glcm, const double *glrlm, const long long *offsets,
+                                              const double *weights, const int *status, int symmetric, double *glcm_w,
+                                              double *glrlm_w, void *stream) {
+  if (B > 0 && !Ng) return fail(PRAD_E_ARG, "batch merge: Ng is NULL");
+  return merge_angles(sizes, B, RoiLevels{Ng, 1}, families, Na, glcm, glrlm, offsets, weights, status, symmetric, glcm_w, glrlm_w,
+                      stream);
+}
+
+namespace {
+
+int merge_plan(const int *sizes, int B, const RoiLevels &Ng, int families, const int *Na, long long *out_offsets) {
   if (!out_offsets) return fail(PRAD_E_ARG, "batch merge plan: NULL output");
   MergeLayout lay;
   PRAD_TRY(merge_layout(sizes, B, Ng, families, Na, &lay));
@@ -52,9 +86,9 @@ extern "C" int prad_batch_merge_plan(const int *sizes, int B, int Ng, int famili
   return PRAD_OK;
 }
 
-extern "C" int prad_batch_merge_angles_dev(const int *sizes, int B, int Ng, int families, const int *Na, const double *glcm,
-                                           const double *glrlm, const long long *offsets, const double *weights,
-                                           const int *status, int symmetric, double *glcm_w, double *glrlm_w, void *stream) {
+int merge_angles(const int *sizes, int B, const RoiLevels &Ng, int families, const int *Na, const double *glcm, const double *glrlm,
+                 const long long *offsets, const double *weights, const int *status, int symmetric, double *glcm_w,
+                 double *glrlm_w, void *stream) {
   MergeLayout lay;
   PRAD_TRY(merge_layout(sizes, B, Ng, families, Na, &lay));
   if (B == 0 || lay.nrec == 0) return PRAD_OK;
@@ -86,7 +120,7 @@ extern "C" int prad_batch_merge_angles_dev(const int *sizes, int B, int Ng, int 
     const int *sz = sizes + 3 * b;
     for (int f = 0; f < 2; f++) {
       if (!((families >> f) & 1)) continue;
-      const long long cells = cells_of(f, sz, Ng);
+      const long long cells = cells_of(f, sz, Ng[b]);
       for (long long c0 = 0; c0 < cells; c0 += PRAD_BM_CELLS) {
         BatchMergeRec &r = recs[k++];
         r.in = offsets[(size_t)f * (B + 1) + b];
@@ -94,7 +128,7 @@ extern "C" int prad_batch_merge_angles_dev(const int *sizes, int B, int Ng, int 
         r.w = o[(size_t)2 * (B + 1) + b] + (f == BM_GLRLM ? Na[b] : 0);
         r.cell0 = (int)c0;
         r.ncell = (int)std::min<long long>(PRAD_BM_CELLS, cells - c0);
-        r.nj = (int)(cells / Ng);
+        r.nj = (int)(cells / Ng[b]);
         r.na = Na[(size_t)f * B + b];
         r.kind = f, r.roi = b;
       }
@@ -115,3 +149,5 @@ extern "C" int prad_batch_merge_angles_dev(const int *sizes, int B, int Ng, int 
     return check_launch("batch_merge_kernel");
   });
 }
+
+}  // namespace

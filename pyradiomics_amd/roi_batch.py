@@ -169,10 +169,10 @@ def _merge_flat(rois, Ng, families, dist, flat, status, plan, pl):
     moff = _cm.batch_merge_plan(rois.sizes, Ng, Na, fams)
     w = _cm.batch_weights(rois.sizes, Na, dist, pl.weightingNorm, pl.spacing, *pl.axes)
     out = {f: torch.empty(int(moff[_cm.MERGE_FAMILIES.index(f), rois.B]), dtype=torch.float64, device=rois.device) for f in fams}
-    rc = rois.lib.prad_batch_merge_angles_dev(_iptr(rois.sizes), rois.B, int(Ng), sum(1 << _cm.MERGE_FAMILIES.index(f) for f in fams),
-                                              _iptr(Na), _vp(flat.get("glcm")), _vp(flat.get("glrlm")), _lp(offsets),
-                                              w.ctypes.data_as(C.POINTER(C.c_double)), _vp(status), 1 if pl.symmetric else 0,
-                                              _vp(out.get("glcm")), _vp(out.get("glrlm")), _eng._stream_ptr())
+    merge, ng = _cm.batch_levels_call(rois.lib, "prad_batch_merge_angles_dev", Ng)
+    rc = merge(_iptr(rois.sizes), rois.B, ng, sum(1 << _cm.MERGE_FAMILIES.index(f) for f in fams), _iptr(Na),
+               _vp(flat.get("glcm")), _vp(flat.get("glrlm")), _lp(offsets), w.ctypes.data_as(C.POINTER(C.c_double)), _vp(status),
+               1 if pl.symmetric else 0, _vp(out.get("glcm")), _vp(out.get("glrlm")), _eng._stream_ptr())
     _lib.raise_for(rc, "batched angle merge")
     return {f + "_w": out[f] for f in fams}, moff
 
@@ -186,9 +186,10 @@ def _matrices_flat(rois, Ng, families, dist, gldm_a, plan=None, pl=Planar()):
     flat = {f: torch.empty(int(offsets[_cm.BATCH_FAMILIES.index(f), B]), dtype=torch.float64, device=rois.device) for f in families}
     status = torch.empty(B, dtype=torch.int32, device=rois.device)
     ptr = [_vp(flat.get(f)) for f in _cm.BATCH_FAMILIES]
-    rc = rois.lib.prad_calculate_batch_f2d_dev(_vp(rois.data), _vp(rois.mask), _iptr(rois.sizes), _lp(rois.off), B, int(Ng),
-                                               _cm.batch_family_bits(families), _iptr(dist), int(dist.shape[0]), int(gldm_a),
-                                               pl.f2d, ptr[0], ptr[1], ptr[2], ptr[3], _vp(status), _eng._stream_ptr())
+    calculate, ng = _cm.batch_levels_call(rois.lib, "prad_calculate_batch_f2d_dev", Ng)
+    rc = calculate(_vp(rois.data), _vp(rois.mask), _iptr(rois.sizes), _lp(rois.off), B, ng, _cm.batch_family_bits(families),
+                   _iptr(dist), int(dist.shape[0]), int(gldm_a), pl.f2d, ptr[0], ptr[1], ptr[2], ptr[3], _vp(status),
+                   _eng._stream_ptr())
     if rc == _lib.PRAD_E_UNSUPPORTED:
         return None
     _lib.raise_for(rc, "batched texture matrices")
@@ -202,37 +203,78 @@ def texture_matrices_batch_flat(levels, masks, sizes, Ng, families=_cm.BATCH_FAM
                                 force2Ddimension=0, weightingNorm=None, spacing=(1.0, 1.0, 1.0), symmetricalGLCM=True):
     """the native calls alone: -> ({family: flat float64 device buffer}, status list), or None when they decline the batch.
     force2D / force2Ddimension / weightingNorm / spacing / symmetricalGLCM as texture_matrices_batch: with weightingNorm the
-    dict also holds the flat merged buffers "glcm_w" / "glrlm_w" (cmatrices.batch_merge_plan lays them out)."""
-    return _matrices_flat(_roi_batch(levels, masks, sizes), Ng, tuple(families), list(distances), gldm_a,
+    dict also holds the flat merged buffers "glcm_w" / "glrlm_w" (cmatrices.batch_merge_plan lays them out).  Ng: an int, or an
+    int sequence [B] (cmatrices.batch_plan lays the buffers out with every ROI's own count); no partition happens here: one count
+    above 64 declines the batch."""
+    rois = _roi_batch(levels, masks, sizes)
+    return _matrices_flat(rois, _cm.batch_levels(Ng, rois.B), tuple(families), list(distances), gldm_a,
                           pl=_planar(force2D, force2Ddimension, weightingNorm, spacing, symmetricalGLCM))
+
+
+def _matrices_native(rois, Ng, families, dist, gldm_a, pl, merged):
+    """the native calls on the whole batch -> ({family: [B views into the flat buffers]}, status), or None when they decline"""
+    plan = _cm.batch_plan(rois.sizes, Ng, families, dist, *pl.axes)
+    res = _matrices_flat(rois, Ng, families, dist, gldm_a, plan, pl)
+    if res is None:
+        return None
+    shapes = _cm.batch_shapes(rois.sizes, Ng, plan[2])
+    flat, status = res
+    mats = {}
+    for f in families:
+        o = plan[1][_cm.BATCH_FAMILIES.index(f)]
+        mats[f] = [flat[f][int(o[b]):int(o[b + 1])].view(shapes[f][b]) for b in range(rois.B)]
+    if merged:
+        moff = _cm.batch_merge_plan(rois.sizes, Ng, plan[2], merged)
+        for f in merged:
+            o = moff[_cm.MERGE_FAMILIES.index(f)]
+            mats[f + "_w"] = [flat[f + "_w"][int(o[b]):int(o[b + 1])].view(shapes[f][b][:2] + (1,)) for b in range(rois.B)]
+    return mats, status
+
+
+def _matrices_looped(rois, Ng, families, dist, gldm_a, pl, merged):
+    """the single calls, ROI by ROI, on a batch of ONE count Ng"""
+    Na = _cm.batch_plan(rois.sizes, Ng, families, dist, *pl.axes)[2]
+    shapes = _cm.batch_shapes(rois.sizes, Ng, Na)
+    f2 = pl.axes
+    single = {"glcm": lambda i, m: _eng.glcm(i, m, Ng, dist, *f2)[0],
+              "glrlm": lambda i, m: _eng.glcm_glrlm(i, m, Ng, max(i.shape), *f2, want_glcm=False)[1],
+              "gldm": lambda i, m: _eng.gldm(i, m, Ng, int(gldm_a), dist, *f2),
+              "ngtdm": lambda i, m: _eng.ngtdm(i, m, Ng, dist, *f2)}
+    mats, status = _cm._looped_matrices(rois.boxes(range(rois.B)), Ng, families, shapes, single, rois.to_device)
+    if merged:
+        _cm.merge_looped(mats, rois.sizes, Na, dist, pl.weightingNorm, pl.spacing, *f2, pl.symmetric, rois.to_device)
+    return mats, status
 
 
 def _matrices(rois, Ng, families, distances, gldm_a, pl=Planar()):
     dist = [int(d) for d in distances]
-    plan = _cm.batch_plan(rois.sizes, Ng, families, dist, *pl.axes)
-    shapes = _cm.batch_shapes(rois.sizes, int(Ng), plan[2])
     merged = [f for f in _cm.MERGE_FAMILIES if f in families] if pl.weightingNorm is not None else []
-    res = _matrices_flat(rois, Ng, families, dist, gldm_a, plan, pl)
-    if res is not None:
-        flat, status = res
-        mats = {}
-        for f in families:
-            o = plan[1][_cm.BATCH_FAMILIES.index(f)]
-            mats[f] = [flat[f][int(o[b]):int(o[b + 1])].view(shapes[f][b]) for b in range(rois.B)]
-        if merged:
-            moff = _cm.batch_merge_plan(rois.sizes, Ng, plan[2], merged)
-            for f in merged:
-                o = moff[_cm.MERGE_FAMILIES.index(f)]
-                mats[f + "_w"] = [flat[f + "_w"][int(o[b]):int(o[b + 1])].view(shapes[f][b][:2] + (1,)) for b in range(rois.B)]
-        return mats, status
-    f2 = pl.axes
-    single = {"glcm": lambda i, m: _eng.glcm(i, m, int(Ng), dist, *f2)[0],
-              "glrlm": lambda i, m: _eng.glcm_glrlm(i, m, int(Ng), max(i.shape), *f2, want_glcm=False)[1],
-              "gldm": lambda i, m: _eng.gldm(i, m, int(Ng), int(gldm_a), dist, *f2),
-              "ngtdm": lambda i, m: _eng.ngtdm(i, m, int(Ng), dist, *f2)}
-    mats, status = _cm._looped_matrices(rois.boxes(range(rois.B)), int(Ng), families, shapes, single, rois.to_device)
-    if merged:
-        _cm.merge_looped(mats, rois.sizes, plan[2], dist, pl.weightingNorm, pl.spacing, *f2, pl.symmetric, rois.to_device)
+    B = rois.B
+    if not isinstance(Ng, np.ndarray):          # one count: the whole batch goes one way
+        return (_matrices_native(rois, Ng, families, dist, gldm_a, pl, merged)
+                or _matrices_looped(rois, Ng, families, dist, gldm_a, pl, merged))
+    # a count per ROI: the ROIs inside the native domain share ONE call, each of the others takes the single calls
+    Na = _cm.batch_plan(rois.sizes, Ng, families, dist, *pl.axes)[2]
+    inside = np.flatnonzero((Ng <= _cm.BATCH_MAX_NG) & (rois.nvox <= batch_max_vox()) & (Na[0] <= 127))
+    keys = list(families) + [f + "_w" for f in merged]
+    mats, status = {k: [None] * B for k in keys}, [_lib.PRAD_OK] * B
+    res = None
+    if len(inside):
+        res = _matrices_native(rois.subset(inside), np.ascontiguousarray(Ng[inside]), families, dist, gldm_a,
+                               pl.subset(inside, B), merged)
+    if res is None:
+        inside = inside[:0]
+    for k, b in enumerate(inside):
+        status[b] = res[1][k]
+        for key in keys:
+            mats[key][b] = res[0][key][k]
+    rest = np.setdiff1d(np.arange(B), inside)
+    for b in rest:
+        one, st = _matrices_looped(rois.subset(np.array([b])), int(Ng[b]), families, dist, gldm_a, pl.subset(np.array([b]), B), merged)
+        status[b] = st[0]
+        for key in keys:
+            mats[key][b] = one[key][0]
+    _cm._set_batch_route(_route(len(rest), B))
     return mats, status
 
 
@@ -252,8 +294,13 @@ def texture_matrices_batch(levels, masks, sizes, Ng, families=_cm.BATCH_FAMILIES
     entries "glcm_w" [Ng, Ng, 1] and "glrlm_w" [Ng, max(size), 1]: the per-angle matrices -- GLCM plus its transpose when
     symmetricalGLCM -- summed over the angles with the weights glcm._weights gives the feature classes for the ROI's angles and
     `spacing` ((z, y, x): one triple or float [B, 3]; used for nothing else).  The sum adds rounded products over the angles
-    ascending (csrc/kernels_batch_merge.h), on every route; a ROI without angles or with status 0 gets zeros."""
-    return _matrices(_roi_batch(levels, masks, sizes), Ng, tuple(families), distances, gldm_a,
+    ascending (csrc/kernels_batch_merge.h), on every route; a ROI without angles or with status 0 gets zeros.
+    Ng: an int as above, or an int sequence [B]: ROI b has Ng[b] levels -- its matrices have Ng[b] rows, its masked levels must
+    lie in [1, Ng[b]] -- as a fixed bin width gives a table of lesions.  The ROIs of at most 64 levels inside the box caps then
+    share ONE native call, each of the others takes the single calls with its own count, and last_batch_route() says "batch",
+    "mixed" or "looped"."""
+    rois = _roi_batch(levels, masks, sizes)
+    return _matrices(rois, _cm.batch_levels(Ng, rois.B), tuple(families), distances, gldm_a,
                      _planar(force2D, force2Ddimension, weightingNorm, spacing, symmetricalGLCM))
 
 
@@ -269,8 +316,9 @@ def _glszm_label(rois, sizes, off, Ng, f2d=-1):
     B = int(sizes.shape[0])
     zones = torch.empty(2 * rois.data.numel(), dtype=torch.int32, device=rois.device)
     meta = torch.empty(4 * B, dtype=torch.int32, device=rois.device)
-    rc = rois.lib.prad_batch_glszm_f2d_dev(_vp(rois.data), _vp(rois.mask), _iptr(sizes), _lp(off), B, int(Ng), int(f2d), _vp(zones),
-                                           _vp(meta), C.c_void_p(meta.data_ptr() + 12 * B), _eng._stream_ptr())
+    label, ng = _cm.batch_levels_call(rois.lib, "prad_batch_glszm_f2d_dev", Ng)
+    rc = label(_vp(rois.data), _vp(rois.mask), _iptr(sizes), _lp(off), B, ng, int(f2d), _vp(zones), _vp(meta),
+               C.c_void_p(meta.data_ptr() + 12 * B), _eng._stream_ptr())
     _lib.raise_for(rc, "batched GLSZM")
     host = meta.cpu().numpy()
     return zones, np.ascontiguousarray(host[:3 * B].reshape(B, 3)), host[3 * B:].copy()
@@ -295,40 +343,47 @@ def glszm_batch_zones(levels, masks, sizes, Ng, force2D=False, force2Ddimension=
     """the zone lists of B small ROIs from the labelling launch alone -> (list of B int32 device tensors [nzones, 2] of
     (level, size) in raster order of each zone's first voxel -- views into one buffer --, summary int32 numpy [B, 3]: zones,
     largest zone, distinct sizes; status int32 numpy [B]).  Raises NotImplementedError outside the native domain (Ng > 64, a box
-    above batch_glszm_max_vox() voxels).  force2D / force2Ddimension: as glszm_batch; weightingNorm / spacing are ignored."""
+    above batch_glszm_max_vox() voxels).  force2D / force2Ddimension: as glszm_batch; weightingNorm / spacing are ignored.  Ng: an
+    int, or an int sequence [B] (every ROI's levels are checked against its own count)."""
     rois = _roi_batch(levels, masks, sizes)
     pl = _planar(force2D, force2Ddimension, weightingNorm, spacing)
-    zones, summary, status = _glszm_label(rois, rois.sizes, rois.off, Ng, pl.f2d)
+    zones, summary, status = _glszm_label(rois, rois.sizes, rois.off, _cm.batch_levels(Ng, rois.B), pl.f2d)
     _cm._set_batch_route("batch")
     return [zones[2 * int(o):2 * int(o) + 2 * int(n)].view(-1, 2) for o, n in zip(rois.off, summary[:, 0])], summary, status
 
 
 def _glszm(rois, Ng, compact, pl=Planar()):
-    Ng, B, dev = int(Ng), rois.B, rois.device
-    covered = np.flatnonzero(rois.nvox <= batch_glszm_max_vox()) if Ng <= 64 else np.zeros(0, dtype=np.int64)
+    B, dev = rois.B, rois.device
+    ngv = _cm.batch_levels_vector(Ng, B)          # (the counts ROI by ROI, whichever form Ng has)
+    covered = np.flatnonzero((rois.nvox <= batch_glszm_max_vox()) & (ngv <= _cm.BATCH_MAX_NG))
     results, status = _GlszmBatch([None] * B), [_lib.PRAD_OK] * B
     if len(covered):
         coff = np.ascontiguousarray(rois.off[covered])
-        zones, summary, st = _glszm_label(rois, np.ascontiguousarray(rois.sizes[covered]), coff, Ng, pl.f2d)
+        cng = np.ascontiguousarray(ngv[covered]) if isinstance(Ng, np.ndarray) else Ng
+        zones, summary, st = _glszm_label(rois, np.ascontiguousarray(rois.sizes[covered]), coff, cng, pl.f2d)
         cols = np.maximum(summary[:, 2 if compact else 1], 1).astype(np.int64)
         k = summary[:, 2].astype(np.int64)
-        out_off, s_off = np.append(np.int64(0), np.cumsum(Ng * cols)), np.append(np.int64(0), np.cumsum(k))
+        out_off = np.append(np.int64(0), np.cumsum(ngv[covered].astype(np.int64) * cols))
+        s_off = np.append(np.int64(0), np.cumsum(k))
         flat = torch.empty(int(out_off[-1]), dtype=torch.float64, device=dev)
         sizes_dev = torch.empty(max(int(s_off[-1]), 1), dtype=torch.int32, device=dev)
-        rc = rois.lib.prad_batch_glszm_fill_dev(_vp(zones), _iptr(summary), _lp(coff), len(covered), Ng, 1 if compact else 0,
-                                                _vp(flat), _lp(out_off), _vp(sizes_dev), _lp(s_off), _eng._stream_ptr())
+        fill, ng = _cm.batch_levels_call(rois.lib, "prad_batch_glszm_fill_dev", cng)
+        rc = fill(_vp(zones), _iptr(summary), _lp(coff), len(covered), ng, 1 if compact else 0, _vp(flat), _lp(out_off),
+                  _vp(sizes_dev), _lp(s_off), _eng._stream_ptr())
         _lib.raise_for(rc, "batched GLSZM fill")
         sizes_host = sizes_dev.cpu().numpy() if compact else None
         for i, b in enumerate(covered):
-            P = flat[int(out_off[i]):int(out_off[i + 1])].view(Ng, int(cols[i]))
+            P = flat[int(out_off[i]):int(out_off[i + 1])].view(int(ngv[b]), int(cols[i]))
             results[b] = (P[:, :int(k[i])], sizes_host[s_off[i]:s_off[i + 1]].copy()) if compact else P
             status[b] = int(st[i])
         # (batch_features_per_angle evaluates the formulas on these buffers, in place)
         results.flat = GlszmFlat(flat, covered, out_off[:-1], cols, sizes_dev if compact else None, np.where(k > 0, s_off[:-1], -1))
     rest = sorted(set(range(B)) - set(int(b) for b in covered))
-    single = lambda i, m, Ns: _eng.glszm_compact(i, m, Ng, Ns, *pl.axes) if compact else _eng.glszm(i, m, Ng, Ns, *pl.axes)
-    for b, one, st in zip(rest, *_cm._looped_glszm(rois.boxes(rest), Ng, compact, single, rois.to_device, pl.f2d)):
-        results[b], status[b] = one, st
+    for b in rest:
+        ng = int(ngv[b])
+        single = lambda i, m, Ns: _eng.glszm_compact(i, m, ng, Ns, *pl.axes) if compact else _eng.glszm(i, m, ng, Ns, *pl.axes)
+        one, st = _cm._looped_glszm(rois.boxes([b]), ng, compact, single, rois.to_device, pl.f2d)
+        results[b], status[b] = one[0], st[0]
     _cm._set_batch_route("looped" if not len(covered) else _route(len(rest), B))
     return results, status
 
@@ -343,8 +398,11 @@ def glszm_batch(levels, masks, sizes, Ng, compact=True, force2D=False, force2Ddi
     mask).  compact=True: a result is (P float64 [Ng, k] device tensor, sizes int32 numpy [k] ascending) as glszm_compact
     returns; compact=False: the dense [Ng, max(maxRegion, 1)] tensor as glszm returns.  The results of the native route are
     views into one flat buffer.  ROIs above batch_glszm_max_vox() voxels, or every ROI when Ng > 64, go through glszm_compact /
-    glszm one by one (Ns = max(1, masked voxels)); last_batch_route() says "batch", "mixed" or "looped"."""
-    return _glszm(_roi_batch(levels, masks, sizes), Ng, compact, _planar(force2D, force2Ddimension, weightingNorm, spacing))
+    glszm one by one (Ns = max(1, masked voxels)); last_batch_route() says "batch", "mixed" or "looped".  Ng: an int, or an int
+    sequence [B]: ROI b has Ng[b] levels and a matrix of Ng[b] rows; the ROIs above 64 levels go one by one, the others share the
+    two launches."""
+    rois = _roi_batch(levels, masks, sizes)
+    return _glszm(rois, _cm.batch_levels(Ng, rois.B), compact, _planar(force2D, force2Ddimension, weightingNorm, spacing))
 
 
 # ---- feature formulas (prad_batch_features_dev, csrc/kernels_batch_features.h) -----------------------------------------------
@@ -388,18 +446,41 @@ def batch_features_per_angle(mats, Ng, glszm=None, symmetric=True, mcc=True):
     empty)]}, rows = angles for glcm (24 columns: the 23 of glcm_features, then glcm_mcc; NaN without `mcc`) and glrlm (16),
     one row for gldm (16), ngtdm (5; its flag says that no level occurs) and glszm (16): the arrays the single calls return,
     bit for bit.  Matrices that are views of the flat buffers of the batched calls are evaluated in two launches
-    (prad_batch_features_dev: Ng <= 64); anything else goes through the single calls, one by one."""
+    (prad_batch_features_dev: Ng <= 64); anything else goes through the single calls, one by one.  Ng: an int, or an int
+    sequence [B] -- the counts the matrices were built with; the ROIs of at most 64 levels then share the two launches and a ROI
+    above has no MCC (NaN), as glcm_mcc declines it."""
     lib = _lib.load()
-    Ng = int(Ng)
     fams = [f for f in FEATURE_FAMILIES[:4] if f in mats]
     B = len(mats[fams[0]]) if fams else len(glszm or [])
     if any(len(mats[f]) != B for f in fams) or (glszm is not None and len(glszm) != B):
         raise ValueError("the families differ in their number of ROIs")
+    Ng = _cm.batch_levels(Ng, B)
+    if isinstance(Ng, np.ndarray) and (Ng > _cm.BATCH_MAX_NG).any():
+        # the ROIs the launches take, as a batch of their own; each of the others through the single calls
+        out = {f: [None] * B for f in fams + (["glszm"] if glszm is not None else [])}
+        small = np.flatnonzero(Ng <= _cm.BATCH_MAX_NG)
+        if len(small):
+            zsub = None
+            if glszm is not None:
+                zsub = _GlszmBatch(glszm[b] for b in small)
+                zf = getattr(glszm, "flat", None)
+                if zf is not None:          # (its ROIs all have at most 64 levels: _glszm)
+                    zsub.flat = zf._replace(covered=np.searchsorted(small, zf.covered))
+            sub = batch_features_per_angle({f: [mats[f][b] for b in small] for f in fams}, np.ascontiguousarray(Ng[small]), zsub,
+                                           symmetric, mcc)
+            for f in out:
+                for k, b in enumerate(small):
+                    out[f][b] = sub[f][k]
+        for b in np.flatnonzero(Ng > _cm.BATCH_MAX_NG):
+            for f in out:
+                out[f][b] = _single_glszm_features(glszm[b], int(Ng[b])) if f == "glszm" else _single_features(f, mats[f][b], symmetric, False)
+        return out
     out = {f: [None] * B for f in fams}
     if glszm is not None:
         out["glszm"] = [None] * B
-    views = {f: _flat_offsets(list(mats[f])) for f in fams} if Ng <= 64 else {f: None for f in fams}
-    zflat = getattr(glszm, "flat", None) if (glszm is not None and Ng <= 64) else None
+    small = isinstance(Ng, np.ndarray) or Ng <= _cm.BATCH_MAX_NG
+    views = {f: _flat_offsets(list(mats[f])) for f in fams} if small else {f: None for f in fams}
+    zflat = getattr(glszm, "flat", None) if (glszm is not None and small) else None
     native = [f for f in fams if views[f] is not None]
     if (native or zflat is not None) and B:
         dev = (mats[native[0]][0] if native else zflat.P).device
@@ -433,15 +514,17 @@ def batch_features_per_angle(mats, Ng, glszm=None, symmetric=True, mcc=True):
                 soff[zflat.covered] = zflat.s_off
         lay = np.zeros((2, 5, B + 1), dtype=np.int64)
         nrec = np.zeros(3, dtype=np.int64)
-        rc = lib.prad_batch_features_plan(_iptr(sizes), B, Ng, bits, _iptr(Na), _iptr(cols), _lp(lay), _lp(nrec))
+        plan, ng = _cm.batch_levels_call(lib, "prad_batch_features_plan", Ng)
+        rc = plan(_iptr(sizes), B, ng, bits, _iptr(Na), _iptr(cols), _lp(lay), _lp(nrec))
         _lib.raise_for(rc, "batched features plan")
         nout, nrows = int(lay[0, 4, B]), int(lay[1, 4, B])
         # values and flags in one device block: one read-back
         block = torch.empty(nout + (nrows + 1) // 2 + 1, dtype=torch.float64, device=dev)
         flags = block[nout:].view(torch.int32)
-        rc = lib.prad_batch_features_dev(_iptr(sizes), B, Ng, bits, _iptr(Na), _iptr(cols), ptrs[0], ptrs[1], ptrs[2], ptrs[3],
-                                         _lp(offsets), zptr, _lp(zoff), sptr, _lp(soff), 1 if symmetric else 0, 1 if mcc else 0,
-                                         _vp(block), _vp(flags), _eng._stream_ptr())
+        features, ng = _cm.batch_levels_call(lib, "prad_batch_features_dev", Ng)
+        rc = features(_iptr(sizes), B, ng, bits, _iptr(Na), _iptr(cols), ptrs[0], ptrs[1], ptrs[2], ptrs[3], _lp(offsets), zptr,
+                      _lp(zoff), sptr, _lp(soff), 1 if symmetric else 0, 1 if mcc else 0, _vp(block), _vp(flags),
+                      _eng._stream_ptr())
         _lib.raise_for(rc, "batched features")
         host = block.cpu().numpy()
         vals, empty = host[:nout], host[nout:].view(np.int32)[:nrows] != 0
@@ -453,7 +536,8 @@ def batch_features_per_angle(mats, Ng, glszm=None, symmetric=True, mcc=True):
     for f in out:      # whatever the native call did not take
         for b in range(B):
             if out[f][b] is None:
-                out[f][b] = _single_glszm_features(glszm[b], Ng) if f == "glszm" else _single_features(f, mats[f][b], symmetric, mcc)
+                ng = int(Ng[b]) if isinstance(Ng, np.ndarray) else Ng
+                out[f][b] = _single_glszm_features(glszm[b], ng) if f == "glszm" else _single_features(f, mats[f][b], symmetric, mcc)
     return out
 
 
@@ -511,11 +595,14 @@ def texture_features_batch(levels, masks, sizes, Ng, classes=("glcm", "glrlm", "
     values; last_batch_route() says "batch", "mixed" or "looped".  mcc_angles=True adds the entry "glcm_mcc_angles": per ROI the
     MCC of every angle (float64 [Na], NaN for an empty angle; None with status 0) -- what the feature class averages as a flat
     vector (cmatrices._mcc_angle_mean), in another order of additions than the column mean of the table; with weightingNorm
-    it has length 1."""
+    it has length 1.
+    Ng: an int, or an int sequence [B] that gives ROI b its own count Ng[b] (the discretisation of a fixed bin width): the ROIs
+    of at most 64 levels inside the box caps go through the native calls together, whatever their counts; each of the others
+    takes the single calls, the route is then "mixed", and a ROI above 64 levels has no MCC (NaN)."""
     rois, classes = _roi_batch(levels, masks, sizes), tuple(classes)
     if not classes or any(c not in FEATURE_FAMILIES for c in classes):
         raise ValueError("classes must be a non-empty subset of %s" % (FEATURE_FAMILIES,))
-    return _texture_features(rois, Ng, classes, distances, gldm_a, symmetricalGLCM, mcc, mcc_angles,
+    return _texture_features(rois, _cm.batch_levels(Ng, rois.B), classes, distances, gldm_a, symmetricalGLCM, mcc, mcc_angles,
                              _planar(force2D, force2Ddimension, weightingNorm, spacing))
 
 
@@ -631,7 +718,7 @@ def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, b
                        force2Ddimension=0, weightingNorm=None, spacing=(1.0, 1.0, 1.0)):
     """The feature table of B small ROIs from their raw intensity boxes and masks (inputs as firstorder_batch): firstorder_batch
     and bin_batch -- two launches and two read-backs for the whole batch (binWidth, default 25, or binCount) -- then
-    texture_features_batch once per distinct Ng of the batch on the ROIs that share it.  -> ({class: float64 numpy [B, nfeat]},
+    texture_features_batch ONCE on the non-empty ROIs, every ROI with the Ng the discretisation gave it.  -> ({class: float64 numpy [B, nfeat]},
     status [B]): "firstorder" has the 19 columns of cmatrices.FIRSTORDER_FEATURES (firstorder.features_from_stats on the
     statistics, the level counts and voxelVolume, a number or [B]); the texture classes the columns of texture_features_batch.
     status 0: an empty ROI; its rows are NaN, the others are not affected.  last_batch_route() says "batch", "mixed" or
@@ -665,14 +752,17 @@ def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, b
     if texture:
         for c in texture:
             table[c] = np.full((B, _FEATURE_ROW[c]), np.nan)
-        for ng in sorted(set(int(g) for g in Ng[status == 1])):
-            idx = np.flatnonzero((Ng == ng) & (status == 1))
-            sub, st = _texture_features(binned.subset(idx), ng, texture, distances, gldm_a, symmetricalGLCM,
-                                        mcc and ng <= 64,       # (glcm_mcc declines more than 64 occurring levels)
-                                        extras and mcc and ng <= 64, pl.subset(idx, B))
+        idx = np.flatnonzero(status == 1)
+        if len(idx):
+            ngv = np.ascontiguousarray(Ng[idx].astype(np.intc))
+            same = bool((ngv == ngv[0]).all())          # (binCount: one count, the scalar calls)
+            few = ngv <= _cm.BATCH_MAX_NG               # (glcm_mcc declines more than 64 occurring levels)
+            sub, st = _texture_features(binned.subset(idx), int(ngv[0]) if same else ngv, texture, distances, gldm_a,
+                                        symmetricalGLCM, bool(mcc and few.any()), bool(extras and mcc and few.any()),
+                                        pl.subset(idx, B))
             routes.append(last_batch_route())
             for k, b in enumerate(idx):
-                if "glcm_mcc_angles" in sub:
+                if "glcm_mcc_angles" in sub and few[k]:
                     angles[b] = sub["glcm_mcc_angles"][k]
             for c in texture:
                 table[c][idx] = sub[c]
