@@ -820,6 +820,34 @@ int prad_batch_swt_plan(const int *sizes, int B, int flen, int *verdict, long lo
 int prad_batch_swt_dev(const void *in, int dtype, const int *sizes, const long long *off, int B, const double *dec_lo,
                        const double *dec_hi, int flen, double *out, long long band_stride, int *verdict, void *stream);
 
+/* ---- the Laplacian-of-Gaussian images of many small boxes (csrc/kernels_batch_log.h) -----------------------------------
+ * prad_batch_log_dev: ITK's LaplacianRecursiveGaussianImageFilter (NormalizeAcrossScale = normalize != 0) on each of B boxes
+ * ALONE, for S sigmas, one workgroup per (ROI, sigma) pair and the whole filter of a box inside one compute unit's LDS -- per
+ * ROI and sigma, bit for bit, what prad_log_multi_dev[_f64] gives for the box.  `in` (DEVICE) holds the boxes in the batch
+ * layout of prad_batch_firstorder_dev, in the image's own dtype (0 float32, 1 float64, 2 int32, 3 int16; the derivative pass
+ * of every term reads it widened to float64: exact); sizes ([B][3], z y x), off (element offsets, ascending, boxes not
+ * overlapping), spacing ([B][3], z y x, per ROI) and the S sigmas (1 <= S <= 8, in the units of spacing) are HOST arrays.
+ * out DEVICE [S][row_stride], float64 for dtype 1 and float32 otherwise, row_stride >= off[B - 1] + its voxels: the image of
+ * ROI b for sigmas[s] lies at out + s * row_stride + off[b] in the box's own shape -- every row is a batch-layout buffer.
+ * verdict HOST int [S][B]: 0 the pair was computed here; 8 the box is too large for the kernel -- an extent above 64, or
+ * 4 Nz Ny (Nx | 1) bytes (the float32 image with an odd row pitch) above the 160 KiB of a compute unit's LDS: 32^3 fits, 36^3
+ * does not -- and the single route (which asks the reference's question below itself) must serve the pair; 16 the reference
+ * yields NO IMAGE for the pair (imageoperations.py getLoGImage: an extent below 4, or below ceil(sigma / spacing) + 1).  The
+ * slice of `out` of a pair that is not 0 is never touched.
+ * The native ROIs are sorted into at most three classes by their LDS footprint (<= 16 KiB, <= 64 KiB, above); a class is one
+ * launch with the dynamic LDS of its largest ROI and 256, 512 or 768 lanes per workgroup.  One copy (the record, item and
+ * coefficient tables) and up to three launches on `stream`, which is then synchronised; no atomics, no memset; kernel family
+ * "batch_log" (prad_last_kernel_ms), prad_last_path "batch", prad_last_variant "batch-log".
+ * PRAD_E_ARG, before anything is launched: a NULL pointer, B < 1, S outside [1, 8], a size < 1, a sigma <= 0, a spacing <= 0,
+ * a negative offset, off[b] before the end of ROI b - 1, row_stride before the end of the last box, a dtype outside the list.
+ * prad_batch_log_plan (host only, pure, needs no device): the planner the call itself uses.  verdict as above; lds_class HOST
+ * int [B]: the class (0, 1, 2) of a ROI inside the kernel's domain, -1 for any other; *n_items = the workgroups of the call =
+ * the zeros of verdict.  Same argument errors as the call. */
+int prad_batch_log_plan(const int *sizes, int B, const double *spacing, const double *sigmas, int S, int *verdict,
+                        int *lds_class, long long *n_items);
+int prad_batch_log_dev(const void *in, int dtype, const int *sizes, const long long *off, int B, const double *spacing,
+                       const double *sigmas, int S, int normalize, void *out, long long row_stride, int *verdict, void *stream);
+
 /* ---- filter stack in front of the matrices (radiomics/imageoperations.py:756-970) ---------------------------
  * The arithmetic of both filters lives in third-party wheels (PyWavelets, SimpleITK/ITK) that are not part of
  * the reference tree; these entry points implement their published algorithms (see oracle/filters_oracle.py):

@@ -792,6 +792,22 @@ def calculate_wavelet_batch(images, wavelet="coif1", level=1, start_level=0, for
             for name, row in zip(names, names.rows)}, tuple(names)
 
 
+def calculate_log_batch(images, sigma, spacing=(1.0, 1.0, 1.0)):
+    """The LoG images of B small 3-D boxes (a list of host arrays: raw intensities) for the sigmas `sigma`: one upload,
+    engine.log_batch -- at most three launches for all boxes and sigmas inside its native domain -- and one download.  spacing:
+    (z, y, x), one triple or [B, 3].  -> ({image type name: [B numpy arrays in the boxes' shapes -- float64 for float64 boxes,
+    float32 otherwise --, None where the reference yields no image]}, names): the names getLoGImage yields, in its order.  Needs
+    a device (RuntimeError without one); last_batch_route() tells which route ran."""
+    ones = [np.ones(np.shape(i), dtype=bool) for i in images]
+    _, _, sizes, upload = _host_roi_batch(images, ones, "LoG images", raw=True)
+    logs, names, _, valid = _engine().log_batch(upload()[0], sizes, sigma, spacing)
+    host = logs.cpu().numpy()
+    nvox = sizes.astype(np.int64).prod(1)
+    off = np.concatenate([[0], np.cumsum(nvox)])
+    return {name: [host[s, off[b]:off[b + 1]].reshape(tuple(sizes[b])).copy() if valid[s, b] else None for b in range(len(nvox))]
+            for s, name in enumerate(names)}, tuple(names)
+
+
 # ---- fused voxel-based features of the other four texture classes (prad_voxel_texture_features_dev) ---------
 _ZONE_LIKE = {
     "glrlm": (3, ["ShortRunEmphasis", "LongRunEmphasis", "GrayLevelNonUniformity", "GrayLevelNonUniformityNormalized",

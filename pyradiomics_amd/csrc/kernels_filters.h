@@ -16,6 +16,7 @@
 #pragma once
 #include <type_traits>
 #include "prad_runtime.h"
+#include "prad_rgauss.h"      // RGaussCoef
 
 namespace prad {
 
@@ -180,10 +181,6 @@ __global__ void __launch_bounds__(256) swt3_fused_kernel(const TIN *__restrict__
     }
   }
 }
-
-struct RGaussCoef {
-  double N0, N1, N2, N3, D1, D2, D3, D4, M1, M2, M3, M4, BN1, BN2, BN3, BN4, BM1, BM2, BM3, BM4;
-};
 
 // Several sigmas per launch (blockIdx.y): a 256^3 volume has 65 536 lines = ONE wave per SIMD; the waves of the other sigmas
 // fill the machine (profiles/r03_probes.md section 11, profiles/r04_probes.md).

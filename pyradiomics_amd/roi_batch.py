@@ -918,6 +918,104 @@ def wavelet_batch(images, sizes=None, wavelet="coif1", level=1, start_level=0, f
     return bands, names, rois.sizes
 
 
+# ---- LoG images of the boxes (prad_batch_log_dev, csrc/kernels_batch_log.h) --------------------------------------------------
+LOG_NO_IMAGE = 16          # verdict of a (ROI, sigma) pair the reference yields no image for (PRAD_BLOG_NO_IMAGE)
+_LOG_MAX_SIGMAS = 8        # sigmas per call of prad_batch_log_dev
+
+
+def batch_log_plan(sizes, sigma, spacing=(1.0, 1.0, 1.0)):
+    """Host-side plan of the batched LoG launches (prad_batch_log_plan; pure, needs no device).  sizes: int [B, 3]; sigma: up to 8
+    values > 0; spacing: one (z, y, x) triple or [B, 3].  -> (verdict int [S, B]: 0 the kernel computes the pair, 8 the box is
+    too large for it (an extent above 64, or more than a compute unit's LDS) and the single route serves it, LOG_NO_IMAGE the
+    reference yields no image for the pair -- an extent below 4 or below ceil(sigma / spacing) + 1; lds_class int [B]: 0, 1, 2
+    by the LDS footprint of a box the kernel takes, -1 for any other).  ValueError for bad arguments."""
+    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
+    B = int(sizes.shape[0])
+    sig = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(-1))
+    sp = _cm.batch_spacing(spacing, B)
+    verdict = np.zeros((max(len(sig), 1), max(B, 1)), dtype=np.intc)
+    cls = np.zeros(max(B, 1), dtype=np.intc)
+    n = C.c_longlong(0)
+    rc = _lib.load().prad_batch_log_plan(_iptr(sizes), B, C.c_void_p(sp.ctypes.data), C.c_void_p(sig.ctypes.data), len(sig),
+                                         _iptr(verdict), _iptr(cls), C.byref(n))
+    _lib.raise_for(rc, "batch log plan")
+    return verdict[:len(sig), :B].copy(), cls[:B].copy()
+
+
+def _log_sigmas(sigma):
+    """the sigmas getLoGImage filters with, in its order and with its warning for the others; duplicates once -> (values, names)"""
+    from . import filters
+    good = []
+    for s in sigma:
+        if s > 0.0:
+            good.append(s)
+        else:
+            filters.logger.warning("applyLoG: sigma must be greater than 0.0: %s", s)
+    good = list(dict.fromkeys(good))
+    if not good:
+        raise ValueError("the batched LoG needs at least one sigma above 0")
+    return good, ["log-sigma-%s-mm-3D" % str(s).replace(".", "-") for s in good]
+
+
+def _log(rois, sigma, spacing, normalize, out):
+    sig, names = _log_sigmas(sigma)
+    B, S, W = rois.B, len(sig), rois.data.numel()
+    sp = _cm.batch_spacing(spacing, B)
+    dt = torch.float64 if rois.data.dtype == torch.float64 else torch.float32
+    if out is None:
+        out = torch.empty((S, W), dtype=dt, device=rois.device)
+    elif (out.dtype != dt or out.device != rois.device or out.dim() != 2 or tuple(out.shape) != (S, W)
+          or (W > 1 and out.stride(1) != 1) or (S > 1 and out.stride(0) < W)):
+        raise ValueError("out must be a %s [%d, %d] tensor on %s with contiguous rows" % (dt, S, W, rois.device))
+    stride = int(out.stride(0)) if S > 1 else W
+    values = np.ascontiguousarray(sig, dtype=np.float64)
+    verdict = np.zeros((S, B), dtype=np.intc)
+    for lo in range(0, S, _LOG_MAX_SIGMAS):
+        part = np.ascontiguousarray(values[lo:lo + _LOG_MAX_SIGMAS])
+        v = np.zeros((len(part), B), dtype=np.intc)
+        rc = rois.lib.prad_batch_log_dev(_vp(rois.data), _eng._DTYPE_CODES[rois.data.dtype], _iptr(rois.sizes), _lp(rois.off), B,
+                                         C.c_void_p(sp.ctypes.data), C.c_void_p(part.ctypes.data), len(part),
+                                         1 if normalize else 0, _vp(out[lo]), stride, _iptr(v), _eng._stream_ptr())
+        _lib.raise_for(rc, "batched LoG")
+        verdict[lo:lo + len(part)] = v
+    # the boxes the kernel does not take: the reference's own question (getLoGImage), then the single route box by box
+    valid = verdict == 0
+    looped = 0
+    for b in np.flatnonzero((verdict == 8).any(0)):
+        size = rois.sizes[b].astype(np.float64)
+        rows = [s for s in np.flatnonzero(verdict[:, b] == 8)
+                if size.min() >= 4 and np.all(size >= np.ceil(values[s] / sp[b]) + 1)]
+        if not rows:
+            continue
+        o, n = int(rois.off[b]), int(rois.nvox[b])
+        images = _eng.log_images(rois.view(rois.data, b), sp[b][::-1], [values[s] for s in rows], normalize)
+        for s, image in zip(rows, images):
+            out[s, o:o + n] = image.reshape(-1).to(dt)
+            valid[s, b] = True
+        looped += len(rows)
+    _cm._set_batch_route(_route(looped, int(valid.sum())))
+    return out, names, valid
+
+
+def log_batch(images, sizes=None, sigma=(1.0, 2.0, 3.0), spacing=(1.0, 1.0, 1.0), normalize=True, out=None):
+    """The LoG images of B small boxes for S sigmas in at most three launches: per box and sigma what getLoGImage computes on the
+    box alone -- ITK's LaplacianRecursiveGaussianImageFilter with NormalizeAcrossScale, engine.log_images(box, spacing, [sigma]) --
+    bit for bit.  images: as wavelet_batch takes them (a list of 3-D device tensors of one dtype -- float32, float64, int32,
+    int16; anything else is widened to float64 --, or a flat device tensor plus `sizes` int [B, 3]); spacing: (z, y, x), one triple
+    or [B, 3]; sigma: in the units of spacing, values <= 0 are dropped with the reference's warning, duplicates kept once.
+    -> (logs, names, sizes, valid): logs [S, W] on the device, W the voxels of the batch, float64 for float64 boxes and float32
+    otherwise -- every row is itself a flat batch tensor that roi_features_batch takes as `images`; names: the strings
+    getLoGImage yields ("log-sigma-1-0-mm-3D" ...), one per row; sizes int32 [B, 3]; valid bool [S, B]: False where the reference
+    yields no image (an extent below 4, or below ceil(sigma / spacing) + 1) -- that slice of `logs` is not written.  out: a
+    preallocated [S, W] tensor of that dtype (rows contiguous, row stride >= W) to fill instead.
+    Native: boxes whose extents all lie in 4 .. 64 and whose float32 copy, rows padded to an odd length, fits a compute unit's
+    LDS (32^3 does, 36^3 does not; batch_log_plan tells); the other boxes are filled from engine.log_images one by one.
+    last_batch_route() says "batch", "mixed" or "looped"."""
+    rois = _image_batch(images, sizes)
+    logs, names, valid = _log(rois, sigma, spacing, normalize, out)
+    return logs, names, rois.sizes, valid
+
+
 def _tight_boxes(rois):
     """The box the feature classes of the reference see -- computeFeatures crops every derived image to the ROI's bounding box
     (featureextractor.py:560-604), here cropToTumorMask(padDistance=0)'s box: the bounding box of the mask with its x extent
@@ -963,6 +1061,10 @@ def _tight_boxes(rois):
 _WAVELET_SETTINGS = ("wavelet", "level", "start_level")
 
 
+_IMAGE_TYPES = ("Original", "Wavelet")                 # what roi_features_batch_images takes
+_DERIVED_TYPES = ("Original", "Wavelet", "LoG")        # what roi_features_batch_derived takes
+
+
 def roi_features_batch_images(images, masks, sizes=None, imageTypes=None, classes=ROI_FEATURE_CLASSES, **settings):
     """roi_features_batch on the boxes themselves ("Original") and on their wavelet sub-bands ("Wavelet": wavelet_batch, one
     launch for all eight), each derived image binned on its own per ROI as the reference bins every derived image.  The
@@ -971,13 +1073,37 @@ def roi_features_batch_images(images, masks, sizes=None, imageTypes=None, classe
     reference's feature classes do, so a ROI's values do not depend on the margin it was handed over with.  imageTypes:
     {"Original": {}, "Wavelet": {}} by default; the dict of a type holds settings for that type alone (for "Wavelet" also
     wavelet / level / start_level), which override **settings -- the keyword arguments of roi_features_batch; force2D and
-    force2Ddimension also steer the transform, as in getWaveletImage.  Any other image type: NotImplementedError.
+    force2Ddimension also steer the transform, as in getWaveletImage.  Any other image type: NotImplementedError ("LoG" is
+    batched by roi_features_batch_derived, whose results for a box depend on the box it is handed, not on the ROI alone).
     -> ({image name: {class: float64 numpy [B, nfeat]}}, status [B]): image names "original" and those of wavelet_batch, in
     the reference's order; status[b] is the AND over the images.  last_batch_route() joins the routes of all calls."""
     imageTypes = {"Original": {}, "Wavelet": {}} if imageTypes is None else dict(imageTypes)
     for t in imageTypes:
-        if t not in ("Original", "Wavelet"):
-            raise NotImplementedError("roi_features_batch_images: image type %r (Original and Wavelet are batched)" % (t,))
+        if t not in _IMAGE_TYPES:
+            raise NotImplementedError("roi_features_batch_images: image type %r (Original and Wavelet are batched here%s)"
+                                      % (t, "; roi_features_batch_derived takes LoG" if t == "LoG" else ""))
+    return _roi_features_images(images, masks, sizes, imageTypes, classes, settings)
+
+
+def roi_features_batch_derived(images, masks, sizes=None, imageTypes=None, classes=ROI_FEATURE_CLASSES, **settings):
+    """roi_features_batch_images with the LoG images as a third image type: "LoG": {"sigma": [...]} makes one log_batch call for
+    all sigmas and one feature call per sigma; `spacing` (z, y, x; the argument the planar route reads) comes from the
+    settings.  The LoG is that of the box ALONE, the reference's with preCrop: a recursive filter has unbounded support, so --
+    unlike the wavelet sub-bands -- the LoG of a whole volume does not equal the LoG of a crop on the ROI's voxels, however wide
+    the margin, and the values of a ROI depend on the box it is handed over in.  The images go in the reference's order, that of
+    imageTypes ({"Original": {}, "Wavelet": {}, "LoG": ...} keys); image names are "original", those of wavelet_batch and those of
+    log_batch.  A ROI for which the reference yields no LoG image at some sigma (log_batch's `valid`) has NaN rows in that
+    image's tables, and its status is not lowered by them.  "LoG" with force2D and any image type but the three:
+    NotImplementedError.  -> as roi_features_batch_images."""
+    imageTypes = {"Original": {}, "Wavelet": {}} if imageTypes is None else dict(imageTypes)
+    for t in imageTypes:
+        if t not in _DERIVED_TYPES:
+            raise NotImplementedError("roi_features_batch_derived: image type %r (Original, Wavelet and LoG are batched)" % (t,))
+    return _roi_features_images(images, masks, sizes, imageTypes, classes, settings)
+
+
+def _roi_features_images(images, masks, sizes, imageTypes, classes, settings):
+    """the image types have been checked"""
     if not imageTypes:
         raise ValueError("roi_features_batch_images: no image type")
     rois = _roi_batch(images, masks, sizes, raw=True)
@@ -986,17 +1112,36 @@ def roi_features_batch_images(images, masks, sizes=None, imageTypes=None, classe
     pick, tight_sizes = _tight_boxes(rois)
     tight_mask = rois.mask[pick]
 
-    def features(name, data, kw):
+    def features(name, data, kw, no_image=None):
         table, st = roi_features_batch(data[pick], tight_mask, tight_sizes, classes, **kw)
         routes.append(last_batch_route())
+        st = np.asarray(st, dtype=np.int64)
+        if no_image is not None and no_image.any():
+            for v in table.values():
+                if isinstance(v, np.ndarray) and v.shape[:1] == (rois.B,):
+                    v[no_image] = np.nan if v.dtype.kind == "f" else 0
+            st = np.where(no_image, 1, st)
         tables[name] = table
-        status[:] &= np.asarray(st, dtype=np.int64)
+        status[:] &= st
 
     for t, custom in imageTypes.items():
         kw = dict(settings)
         kw.update(custom or {})
         if t == "Original":
             features("original", rois.data, kw)
+            continue
+        if t == "LoG":
+            sigma = kw.pop("sigma", [])
+            if kw.get("force2D", False):
+                raise NotImplementedError("roi_features_batch_derived: LoG with force2D is not batched")
+            logs, names, valid = _log(rois, sigma, kw.get("spacing", (1.0, 1.0, 1.0)), True, None)
+            routes.append(last_batch_route())
+            for s, name in enumerate(names):
+                image, bad = logs[s], ~valid[s]
+                for b in np.flatnonzero(bad):      # (a slice nothing wrote: the box itself stands in, its rows become NaN)
+                    o, n = int(rois.off[b]), int(rois.nvox[b])
+                    image[o:o + n] = rois.data[o:o + n].to(image.dtype)
+                features(name, image, kw, bad)
             continue
         wkw = {k: kw.pop(k) for k in _WAVELET_SETTINGS if k in kw}
         bands, names = _wavelet(rois, wkw.get("wavelet", "coif1"), wkw.get("level", 1), wkw.get("start_level", 0),
