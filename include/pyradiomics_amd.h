@@ -848,6 +848,33 @@ int prad_batch_log_plan(const int *sizes, int B, const double *spacing, const do
 int prad_batch_log_dev(const void *in, int dtype, const int *sizes, const long long *off, int B, const double *spacing,
                        const double *sigmas, int S, int normalize, void *out, long long row_stride, int *verdict, void *stream);
 
+/* ---- resampling many small boxes, each onto a grid of its own (csrc/kernels_batch_resample.h) ------------------------------
+ * prad_batch_mask_boxes_dev: mask (DEVICE, uint8, non-zero = ROI) holds B boxes in the batch layout; sizes ([B][3], z y x) and
+ * off (element offsets) are HOST arrays.  boxes HOST int [B][7]: lo z / y / x, hi z / y / x (inclusive) and the voxel count of
+ * every ROI; an empty mask gives count 0 (lo = the sizes, hi = -1).  One copy, ONE launch (a workgroup per ROI), one read-back
+ * of 28 B bytes on `stream`, which is synchronised; kernel family "batch_mask_boxes", prad_last_variant "batch-mask-boxes".
+ * prad_batch_resample_dev: prad_resample_dev on each of B boxes ALONE -- output voxel o of ROI b along axis d reads the box at
+ * the continuous index start[b][d] + o * step[b][d] (the product rounded before the sum); interp[b] 0 nearest, 1 linear,
+ * 3 cubic B-spline (the coefficients of the BOX, mirror boundaries at its faces) -- bit for bit what prad_resample_dev returns
+ * for the box.  `in` (DEVICE): the boxes in the batch layout in the image's dtype (0 float32, 1 float64, 2 int32, 3 int16);
+ * mask (DEVICE uint8, or NULL with out_mask NULL): the masks in the same layout, resampled nearest-neighbour on the same grid
+ * in the same launch.  sizes, off, start ([B][3]), step ([B][3]), newsize ([B][3]), interp ([B]), out_off ([B], ascending,
+ * outputs not overlapping) are HOST arrays in z y x order.  out (DEVICE, dtype of `in`; integer types are clamped to their
+ * range, then truncated) and out_mask receive ROI b at element out_off[b] in the shape newsize[b]; 0 outside the box.
+ * verdict HOST int [B]: 0 resampled here; 8 the box holds more than prad_batch_resample_max_vox() voxels (=
+ * prad_batch_max_vox()) and prad_resample_dev must serve it -- its output slice is not touched.  Output voxels are not capped.
+ * One copy and at most TWO launches whatever B is (the prefilter of the B-spline boxes, one workgroup per box, x then y then z
+ * pass; the evaluation, divided by output voxels) on `stream`, which is then synchronised; kernel family "batch_resample",
+ * prad_last_path "batch", prad_last_variant "batch-resample".  B = 0 is a valid call that launches nothing.
+ * PRAD_E_ARG, before anything is launched: a NULL pointer, B < 0, a size or newsize < 1, a start or step that is not finite,
+ * an interpolator outside {0, 1, 3}, a negative offset, out_off[b] before the end of ROI b - 1, a dtype outside the list, a mask
+ * without out_mask or the reverse. */
+int prad_batch_resample_max_vox(void);
+int prad_batch_mask_boxes_dev(const uint8_t *mask, const int *sizes, const long long *off, int B, int *boxes, void *stream);
+int prad_batch_resample_dev(const void *in, int dtype, const uint8_t *mask, const int *sizes, const long long *off, int B,
+                            const double *start, const double *step, const int *newsize, const int *interp,
+                            const long long *out_off, void *out, uint8_t *out_mask, int *verdict, void *stream);
+
 /* ---- filter stack in front of the matrices (radiomics/imageoperations.py:756-970) ---------------------------
  * The arithmetic of both filters lives in third-party wheels (PyWavelets, SimpleITK/ITK) that are not part of
  * the reference tree; these entry points implement their published algorithms (see oracle/filters_oracle.py):

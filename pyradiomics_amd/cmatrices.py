@@ -808,6 +808,31 @@ def calculate_log_batch(images, sigma, spacing=(1.0, 1.0, 1.0)):
             for s, name in enumerate(names)}, tuple(names)
 
 
+def calculate_mask_boxes_batch(masks):
+    """The bounding boxes of B 3-D masks (a list of host arrays, non-zero = ROI): one upload, engine.mask_boxes_batch -- one
+    launch -- and one read-back.  -> (lo int64 [B, 3], hi int64 [B, 3], count int64 [B]), inclusive (z, y, x) bounds; an empty
+    mask has count 0, lo = its shape and hi = -1.  Needs a device (RuntimeError without one)."""
+    _, _, sizes, upload = _host_roi_batch(masks, masks, "mask boxes", raw=True)
+    return _engine().mask_boxes_batch(upload()[1], sizes)
+
+
+def calculate_resample_batch(images, masks, spacing=(1.0, 1.0, 1.0), resampledPixelSpacing=None, interpolator="sitkBSpline",
+                             padDistance=5):
+    """resampleImage on each of B small 3-D boxes as if the box were the whole image (lists of host arrays: raw intensities and
+    masks, non-zero = ROI): one upload, engine.resample_batch -- three launches for all boxes inside its native domain -- and
+    one download.  spacing (z, y, x), one triple or [B, 3]; resampledPixelSpacing (x, y, z).  -> (images, masks: [B numpy arrays
+    on the new grids; uint8 masks], spacing float64 [B, 3] (z, y, x), origin_shift float64 [B, 3] (x, y, z), status int64 [B]:
+    1 for an empty mask, whose box is kept).  Needs a device (RuntimeError without one); last_batch_route() tells which route
+    ran."""
+    _, _, sizes, upload = _host_roi_batch(images, masks, "resampling", raw=True)
+    out, out_masks, newsize, new_spacing, shift, status = _engine().resample_batch(*upload(), sizes, spacing, resampledPixelSpacing,
+                                                                                   interpolator, padDistance)
+    host, host_m = out.cpu().numpy(), out_masks.cpu().numpy()
+    off = np.concatenate([[0], np.cumsum(newsize.astype(np.int64).prod(1))])
+    cut = lambda flat: [flat[off[b]:off[b + 1]].reshape(tuple(newsize[b])).copy() for b in range(len(newsize))]
+    return cut(host), cut(host_m), new_spacing, shift, status
+
+
 # ---- fused voxel-based features of the other four texture classes (prad_voxel_texture_features_dev) ---------
 _ZONE_LIKE = {
     "glrlm": (3, ["ShortRunEmphasis", "LongRunEmphasis", "GrayLevelNonUniformity", "GrayLevelNonUniformityNormalized",

@@ -5,7 +5,8 @@
 //   to_f64_kernel              image -> float64 coefficient volume
 //   bspline_prefilter_kernel   BSplineDecompositionImageFilter along one axis, in place, one lane per line: gain, causal
 //                              initialisation over the 1e-10 horizon (or the exact mirror sum for short lines), causal
-//                              and anti-causal recursion with the pole sqrt(3) - 2
+//                              and anti-causal recursion with the pole sqrt(3) - 2 (the line body is bspline_prefilter_line,
+//                              which kernels_batch_resample.h runs on the lines of many boxes in one launch)
 //   resample_kernel            one thread per output voxel: cubic B-spline weights on the mirrored 4^Nd support (or
 //                              linear / nearest), inside-buffer test, clamp + truncating cast to the pixel type
 // Multiplications and additions are kept unfused and in the order of pyradiomics_amd.imageoperations.resampleImage
@@ -21,15 +22,10 @@ __global__ void to_f64_kernel(const T *__restrict__ in, long long n, double *__r
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = (double)in[i];
 }
 
-// c viewed as [outer][N][inner]
-__global__ void __launch_bounds__(256) bspline_prefilter_kernel(double *__restrict__ c, long long outer, int N,
-                                                                long long inner, int horizon) {
+// one line of N samples, `st` doubles apart, filtered in place (N == 1 leaves it alone); shared with kernels_batch_resample.h
+__device__ __forceinline__ void bspline_prefilter_line(double *p, int N, long long st, int horizon) {
 #pragma clang fp contract(off)
-  const long long lines = outer * inner;
-  const long long line = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (line >= lines || N == 1) return;
-  double *p = c + (line / inner) * N * inner + (line % inner);
-  const long long st = inner;
+  if (N == 1) return;
   const double z = sqrt(3.0) - 2.0;
   const double gain = (1.0 - z) * (1.0 - 1.0 / z);
   for (int n = 0; n < N; n++) p[n * st] *= gain;
@@ -65,6 +61,15 @@ __global__ void __launch_bounds__(256) bspline_prefilter_kernel(double *__restri
     p[n * st] = v;
     last = v;
   }
+}
+
+// c viewed as [outer][N][inner]  (static: the header is included by two translation units)
+static __global__ void __launch_bounds__(256) bspline_prefilter_kernel(double *__restrict__ c, long long outer, int N,
+                                                                       long long inner, int horizon) {
+  const long long lines = outer * inner;
+  const long long line = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (line >= lines || N == 1) return;
+  bspline_prefilter_line(c + (line / inner) * N * inner + (line % inner), N, inner, horizon);
 }
 
 struct ResampleGeo {

@@ -1142,4 +1142,6 @@ from .roi_batch import (FEATURE_FAMILIES, ROI_FEATURE_CLASSES, batch_digitize_ma
                         gather_rois_batch, glszm_batch, glszm_batch_zones, last_batch_route, roi_features_batch,
                         texture_features_batch, texture_matrices_batch, texture_matrices_batch_flat,
                         BandNames, batch_swt_occupancy, batch_swt_plan, roi_features_batch_images, wavelet_band_names,
-                        wavelet_batch, batch_log_plan, log_batch, roi_features_batch_derived)
+                        wavelet_batch, batch_log_plan, log_batch, roi_features_batch_derived,
+                        RESAMPLE_EMPTY, ResamplePlan, batch_resample_max_vox, batch_resample_plan, mask_boxes_batch,
+                        resample_batch, resample_boxes_batch, roi_features_batch_resampled)

@@ -229,6 +229,8 @@ def cropToTumorMask(image, mask, label=1, padDistance=0, deviceResident=False, a
 # mask.  Restated here from the published algorithms and PINNED by the reference's `_resampling` golden vectors
 # (tests/golden/baseline_features.json: every feature of all six classes reproduces within 1e-12).
 _BSPLINE_POLE = np.sqrt(3.0) - 2.0
+# str(interpolator) of the settings -> the code of prad_resample_dev (SimpleITK's names, or its enum values 1, 2, 3)
+INTERPOLATOR_CODES = {"sitkNearestNeighbor": 0, "1": 0, "sitkLinear": 1, "2": 1, "sitkBSpline": 3, "3": 3}
 
 
 def _bspline_decompose_axis(c, axis, tol=1e-10):
@@ -328,7 +330,7 @@ def resampleImage(image, mask, **kwargs):
         inside = ok.reshape(shape) if inside is None else inside & ok.reshape(shape)
     dirm = np.array(msk.direction, dtype=float).reshape(nd, nd)
     origin = tuple(np.array(msk.origin) + dirm @ (old * start))
-    codes = {"sitkNearestNeighbor": 0, "1": 0, "sitkLinear": 1, "2": 1, "sitkBSpline": 3, "3": 3}
+    codes = INTERPOLATOR_CODES
     if str(interpolator) not in codes:
         raise NotImplementedError("interpolator %r" % (interpolator,))
     if (kwargs.get("deviceResident", False) or img.on_device) and nd <= 3:

@@ -1153,6 +1153,257 @@ def _roi_features_images(images, masks, sizes, imageTypes, classes, settings):
     return tables, status.tolist()
 
 
+# ---- resampling the boxes, each onto a grid of its own (prad_batch_resample_dev, csrc/kernels_batch_resample.h) ---------------
+RESAMPLE_EMPTY = 1         # status of a ROI with an empty mask: nothing to centre a grid on, the box is kept as it is
+
+
+class ResamplePlan(NamedTuple):
+    """what batch_resample_plan works out per ROI; every [B, 3] array is (z, y, x) but origin_shift"""
+    start: np.ndarray            # float64 [B, 3]: continuous input index of output voxel 0
+    step: np.ndarray             # float64 [B, 3]: input voxels per output voxel
+    newsize: np.ndarray          # intc [B, 3]
+    interpolator: np.ndarray     # intc [B]: 0 nearest (also: a plain crop), 1 linear, 3 cubic B-spline
+    spacing: np.ndarray          # float64 [B, 3]: the spacing of the new grid
+    origin_shift: np.ndarray     # float64 [B, 3], (x, y, z) as an Image's origin is: the new origin minus the box's, along its axes
+    status: np.ndarray           # int64 [B]: 0, or RESAMPLE_EMPTY
+
+
+def batch_resample_max_vox() -> int:
+    """voxels of the largest box prad_batch_resample_dev resamples itself (= batch_max_vox(); output voxels are not capped)"""
+    return int(_lib.load().prad_batch_resample_max_vox())
+
+
+def _interpolator_codes(interpolator, B):
+    """an interpolator name or code as resampleImage accepts it, or [B] of them -> intc [B]; NotImplementedError for any other"""
+    from .imageoperations import INTERPOLATOR_CODES
+    one = isinstance(interpolator, (str, int, np.integer))
+    items = [interpolator] * B if one else list(interpolator)
+    if len(items) != B:
+        raise ValueError("interpolator must be one name or code, or one per ROI (%d given for %d ROIs)" % (len(items), B))
+    for i in items:
+        if str(i) not in INTERPOLATOR_CODES:
+            raise NotImplementedError("interpolator %r" % (i,))
+    return np.array([INTERPOLATOR_CODES[str(i)] for i in items], dtype=np.intc).reshape(B)
+
+
+def batch_resample_plan(sizes, lo, hi, spacing, resampledPixelSpacing, padDistance=5, interpolator=3) -> ResamplePlan:
+    """The grid imageoperations.resampleImage would resample every box onto if the box were the whole image: its expressions in
+    float64, elementwise over [B, 3] (pure numpy, needs no device).  sizes int [B, 3]; lo / hi int [B, 3]: the inclusive
+    (z, y, x) bounds of the masks (mask_boxes_batch; hi < lo marks an empty mask); spacing (z, y, x), one triple or [B, 3];
+    resampledPixelSpacing (x, y, z) as in the parameter file it mirrors, a 0 keeps that axis' spacing, and so does an axis along
+    which the bounding box is one voxel thick; interpolator: a name or code resampleImage accepts, or [B] of them.
+    Where the spacing does not change (np.allclose, as in the reference) the ROI is a plain crop to cropToTumorMask's device
+    box -- the bounding box with its x extent grown to a multiple of four inside the box, imageoperations.alignedBox,
+    padDistance 0 -- expressed as nearest with step 1 and an integer start, so the kernel copies bits.  An empty mask keeps its
+    whole box the same way and gets status RESAMPLE_EMPTY.  -> ResamplePlan."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 3)
+    B = int(sizes.shape[0])
+    lo, hi = np.asarray(lo, dtype=np.int64).reshape(-1, 3), np.asarray(hi, dtype=np.int64).reshape(-1, 3)
+    if lo.shape[0] != B or hi.shape[0] != B:
+        raise ValueError("batch_resample_plan: %d sizes, %d lower bounds, %d upper bounds" % (B, lo.shape[0], hi.shape[0]))
+    if (sizes < 1).any():
+        raise ValueError("batch_resample_plan: a size below 1")
+    old = _cm.batch_spacing(spacing, B)[:, ::-1]                       # (x, y, z) from here on, like resampleImage
+    if not (old > 0).all():
+        raise ValueError("batch_resample_plan: spacing must be > 0")
+    new = np.asarray(resampledPixelSpacing, dtype=np.float64)
+    if new.shape != (3,):
+        raise AssertionError("Wrong dimensionality (%d-D) of resampledPixelSpacing!, 3-D required" % new.size)
+    if (new < 0).any() or not np.isfinite(new).all():
+        raise ValueError("batch_resample_plan: resampledPixelSpacing must be >= 0")
+    pad = padDistance
+    codes = _interpolator_codes(interpolator, B)
+    empty = (hi < lo).any(1)
+    if ((lo < 0) | (hi >= sizes))[~empty].any():
+        raise ValueError("batch_resample_plan: a bounding box leaves its box")
+    lo_z = np.where(empty[:, None], 0, lo)
+    hi_z = np.where(empty[:, None], sizes - 1, hi)
+    fullsize = sizes[:, ::-1]
+    lo_x, size = lo_z[:, ::-1], (hi_z - lo_z + 1)[:, ::-1]
+    new = np.where(new == 0, old, np.broadcast_to(new, (B, 3)))
+    new = np.where(size != 1, new, old)
+    crop = np.isclose(old, new).all(1) | empty                       # (np.allclose(old, new) per ROI)
+    new = np.where(crop[:, None], old, new)
+    ratio = old / new
+    L = np.floor((lo_x - 0.5) * ratio - pad)
+    U = np.ceil((lo_x + size - 0.5) * ratio + pad)
+    maxU = np.ceil(fullsize * ratio) - 1
+    L = np.where(L < 0, 0, L)
+    U = np.where(U > maxU, maxU, U)
+    newsize = np.array(U - L + 1, dtype=np.int64)
+    start = 0.5 * (new - old) / old + L / ratio
+    step = new / old
+    # the plain crops: alignedBox over the batch (every ROI with the x extent of its own box)
+    c_lo, c_hi = lo_z.copy(), hi_z.copy()
+    need = (-(c_hi[:, 2] - c_lo[:, 2] + 1)) % 4
+    grow = np.minimum(need, sizes[:, 2] - 1 - c_hi[:, 2])
+    c_hi[:, 2] += grow
+    c_lo[:, 2] -= np.minimum(need - grow, c_lo[:, 2])
+    c_lo, c_size = c_lo[:, ::-1], (c_hi - c_lo + 1)[:, ::-1]
+    start = np.where(crop[:, None], c_lo.astype(np.float64), start)
+    step = np.where(crop[:, None], 1.0, step)
+    newsize = np.where(crop[:, None], c_size, newsize)
+    zyx = lambda a, dt: np.ascontiguousarray(a[:, ::-1], dtype=dt)
+    return ResamplePlan(zyx(start, np.float64), zyx(step, np.float64), zyx(newsize, np.intc),
+                        np.where(crop, 0, codes).astype(np.intc), zyx(new, np.float64),
+                        np.ascontiguousarray(old * start), np.where(empty, RESAMPLE_EMPTY, 0).astype(np.int64))
+
+
+def _mask_boxes(rois):
+    boxes = np.zeros((max(rois.B, 1), 7), dtype=np.intc)
+    rc = rois.lib.prad_batch_mask_boxes_dev(_vp(rois.mask), _iptr(rois.sizes), _lp(rois.off), rois.B, _iptr(boxes),
+                                            _eng._stream_ptr())
+    _lib.raise_for(rc, "batched mask boxes")
+    boxes = boxes[:rois.B].astype(np.int64)
+    return boxes[:, 0:3].copy(), boxes[:, 3:6].copy(), boxes[:, 6].copy()
+
+
+def mask_boxes_batch(masks, sizes=None):
+    """The bounding boxes of B masks in ONE launch and one read-back of 28 B bytes.  masks: a list of 3-D device tensors, or a
+    flat device tensor holding the boxes back to back plus `sizes` (int [B, 3]); non-zero = ROI.  -> (lo int64 [B, 3], hi int64
+    [B, 3], count int64 [B]): inclusive (z, y, x) bounds and the voxels of every ROI, numpy arrays; an empty mask has count 0,
+    lo = its sizes and hi = -1 (what batch_resample_plan reads as empty)."""
+    if isinstance(masks, (list, tuple)):
+        if not len(masks):
+            raise ValueError("empty batch")
+        if any(m.dim() != 3 for m in masks):
+            raise ValueError("mask_boxes_batch takes 3-D boxes")
+        sizes = np.array([tuple(m.shape) for m in masks], dtype=np.intc).reshape(-1, 3)
+        masks = torch.cat([(m if m.dtype in (torch.bool, torch.uint8) else m != 0).reshape(-1).view(torch.uint8) for m in masks])
+    elif sizes is None:
+        raise ValueError("a flat mask tensor needs `sizes`")
+    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
+    masks = masks.reshape(-1)
+    if not masks.is_cuda:
+        raise ValueError("engine.* expects CUDA/HIP tensors; use pyradiomics_amd.cmatrices for numpy input")
+    masks = _eng._mask_u8(masks)
+    nvox = sizes.astype(np.int64).prod(1)
+    if not len(nvox) or int(nvox.sum()) != masks.numel():
+        raise ValueError("sizes describe %d voxels, the buffer holds %d" % (int(nvox.sum()), masks.numel()))
+    lib = _lib.load()
+    _set_device(lib, masks.device)
+    return _mask_boxes(RoiBatch(lib, None, masks, sizes, nvox, _offsets(nvox), masks.device))
+
+
+def _geometry(a, B, dtype, what):
+    a = np.ascontiguousarray(np.asarray(a, dtype=dtype))
+    if a.shape != (B, 3):
+        raise ValueError("%s must be an array [%d, 3]" % (what, B))
+    return a
+
+
+def _resample_boxes(rois, start, step, newsize, codes, out, out_masks):
+    """the geometry has been checked; rois.mask may be None -> (images, masks or None, verdict)"""
+    B = rois.B
+    nout = newsize.astype(np.int64).prod(1)
+    out_off, W = _offsets(nout), int(nout.sum())
+
+    def buffer(given, dtype, what):
+        if given is None:
+            return torch.empty(W, dtype=dtype, device=rois.device)
+        if given.dtype != dtype or given.device != rois.device or given.dim() != 1 or given.numel() < W or not given.is_contiguous():
+            raise ValueError("%s must be a contiguous flat %s tensor of at least %d elements on %s" % (what, dtype, W, rois.device))
+        return given
+    out = buffer(out, rois.data.dtype, "out")
+    if rois.mask is not None:
+        out_masks = buffer(out_masks, torch.uint8, "out_masks")
+    elif out_masks is not None:
+        raise ValueError("out_masks without masks")
+    verdict = np.zeros(max(B, 1), dtype=np.intc)
+    dp = lambda a: C.c_void_p(a.ctypes.data)
+    rc = rois.lib.prad_batch_resample_dev(_vp(rois.data), _eng._DTYPE_CODES[rois.data.dtype], _vp(rois.mask), _iptr(rois.sizes),
+                                          _lp(rois.off), B, dp(start), dp(step), _iptr(newsize), _iptr(codes), _lp(out_off),
+                                          _vp(out), _vp(out_masks), _iptr(verdict), _eng._stream_ptr())
+    _lib.raise_for(rc, "batched resampling")
+    verdict = verdict[:B]
+    rest = np.flatnonzero(verdict != 0)
+    for b in rest:                # boxes above batch_resample_max_vox(): the single route, into the same layout
+        o, n = int(out_off[b]), int(nout[b])
+        out[o:o + n] = _eng.resample(rois.view(rois.data, b), start[b], step[b], newsize[b], int(codes[b])).reshape(-1)
+        if rois.mask is not None:
+            m = _eng.resample(rois.view(rois.mask, b).to(torch.int16), start[b], step[b], newsize[b], 0)
+            out_masks[o:o + n] = m.reshape(-1).to(torch.uint8)
+    _cm._set_batch_route(_route(len(rest), B))
+    return out, out_masks, verdict
+
+
+def resample_boxes_batch(images, sizes, start, step, newsize, interpolator=3, masks=None, out=None, out_masks=None,
+                         return_verdict=False):
+    """A batch of engine.resample: box b of the batch is resampled ALONE -- output voxel o along axis d reads the box at the
+    continuous index start[b][d] + o * step[b][d] -- bit for bit what engine.resample(box, start[b], step[b], newsize[b],
+    interpolator[b]) returns, in at most TWO launches whatever B is (the B-spline prefilter of all boxes, one workgroup per box;
+    the evaluation, divided by output voxels).  images: a list of 3-D device tensors of one dtype (float32, float64, int32,
+    int16; anything else is widened to float64), or a flat device tensor plus `sizes` int [B, 3]; start / step float [B, 3],
+    newsize int [B, 3], all (z, y, x); interpolator: 0 nearest, 1 linear, 3 cubic B-spline, an int or [B]; masks (optional): the
+    uint8 masks in the same layout, resampled nearest-neighbour on the same grids in the same launch.  -> (images, masks or None):
+    flat device tensors in the batch layout of `newsize`, which every *_batch function takes as they are.  out / out_masks:
+    preallocated flat tensors (at least sum(prod(newsize)) elements) to fill instead; elements behind the last ROI are not
+    touched.  Native: boxes of at most batch_resample_max_vox() voxels, output voxels uncapped; the others are filled from
+    engine.resample one by one (return_verdict=True appends the verdicts, intc [B]: 0 native, 8 single route).
+    last_batch_route() says "batch", "mixed" or "looped".  The coefficients of the cubic B-spline
+    are those of the box: a recursive prefilter has unbounded support, so a box cut out of a larger scan does not resample to
+    the values of the resampled scan."""
+    rois = _image_batch(images, sizes) if masks is None else _roi_batch(images, masks, sizes, raw=True)
+    B = rois.B
+    codes = np.ascontiguousarray(np.broadcast_to(np.asarray(interpolator, dtype=np.intc), (B,)))
+    if not np.isin(codes, (0, 1, 3)).all():
+        raise NotImplementedError("resample_boxes_batch: interpolator codes are 0 nearest, 1 linear, 3 cubic B-spline")
+    start, step = _geometry(start, B, np.float64, "start"), _geometry(step, B, np.float64, "step")
+    newsize = _geometry(newsize, B, np.intc, "newsize")
+    if (newsize < 1).any():
+        raise ValueError("resample_boxes_batch: a newsize below 1")
+    res = _resample_boxes(rois, start, step, newsize, codes, out, out_masks)
+    return res if return_verdict else res[:2]
+
+
+def resample_batch(images, masks, sizes=None, spacing=(1.0, 1.0, 1.0), resampledPixelSpacing=None, interpolator="sitkBSpline",
+                   padDistance=5):
+    """imageoperations.resampleImage on each of B boxes as if the box were the whole image -- what
+    RadiomicsFeatureExtractor.execute does when it is handed the box as its image --, bit for bit, in THREE launches and one
+    read-back whatever B is: mask_boxes_batch (the bounding boxes, the only read-back), batch_resample_plan (host arithmetic),
+    resample_boxes_batch (prefilter, evaluation; image and mask together).  images / masks / sizes: as roi_features_batch takes
+    them; spacing (z, y, x), one triple or [B, 3]; resampledPixelSpacing (x, y, z) as in a parameter file, 0 keeps an axis;
+    interpolator: a name or code resampleImage accepts (NotImplementedError for any other), for the image -- the mask is always
+    nearest-neighbour; padDistance: voxels of the new grid kept around the bounding box.
+    -> (images, masks, sizes int32 [B, 3], spacing float64 [B, 3] (z, y, x), origin_shift float64 [B, 3] (x, y, z): what to add
+    to the box's origin along its axes, status int64 [B]): flat batch tensors on the new grids that every *_batch function
+    takes as they are.  A ROI whose spacing does not change is cropped (batch_resample_plan), one with an empty mask keeps its
+    box and has status RESAMPLE_EMPTY (resampleImage raises there); the others have status 0.
+    The resampled values are those of the box ALONE: the B-spline prefilter has unbounded support, so -- like the LoG of
+    roi_features_batch_derived -- they are not those of the resampled scan the box was cut from, however wide its margin.
+    Boxes above batch_resample_max_vox() voxels go through engine.resample; last_batch_route() says "batch", "mixed" or
+    "looped"."""
+    if resampledPixelSpacing is None:
+        raise ValueError("resample_batch needs resampledPixelSpacing")
+    rois = _roi_batch(images, masks, sizes, raw=True)
+    _interpolator_codes(interpolator, rois.B)                    # (raises before anything is launched)
+    lo, hi, _ = _mask_boxes(rois)
+    plan = batch_resample_plan(rois.sizes, lo, hi, spacing, resampledPixelSpacing, padDistance, interpolator)
+    out, out_masks, _ = _resample_boxes(rois, plan.start, plan.step, plan.newsize, plan.interpolator, None, None)
+    return out, out_masks, plan.newsize, plan.spacing, plan.origin_shift, plan.status
+
+
+def roi_features_batch_resampled(images, masks, sizes=None, spacing=(1.0, 1.0, 1.0), resampledPixelSpacing=None,
+                                 interpolator="sitkBSpline", padDistance=5, imageTypes=None, classes=ROI_FEATURE_CLASSES,
+                                 **settings):
+    """resample_batch, then roi_features_batch_derived on the resampled boxes: the feature table of B lesions handed over as raw
+    boxes with their own spacing under a parameter file that sets resampledPixelSpacing -- per ROI what
+    RadiomicsFeatureExtractor.execute(box, mask) computes with those settings and no preCrop.  The new spacing of every ROI goes
+    on as `spacing` (LoG, weightingNorm) and its product as voxelVolume.  As for the LoG, the values are those of the box ALONE
+    (resample_batch).  A ROI whose mask is empty -- before or after resampling -- has status 0 and NaN rows (the extractor raises
+    there).  imageTypes / classes / **settings / -> : as roi_features_batch_derived; last_batch_route() joins all calls."""
+    if "voxelVolume" in settings:
+        raise ValueError("roi_features_batch_resampled works out voxelVolume itself")
+    out, out_masks, newsize, new_spacing, _, _ = resample_batch(images, masks, sizes, spacing, resampledPixelSpacing, interpolator,
+                                                                padDistance)
+    route = last_batch_route()
+    tables, status = roi_features_batch_derived(out, out_masks, newsize, imageTypes, classes, spacing=new_spacing,
+                                                voxelVolume=new_spacing[:, 2] * new_spacing[:, 1] * new_spacing[:, 0],
+                                                **settings)          # ((x * y) * z, the order of the feature class)
+    _cm._set_batch_route(_joined_route([route, last_batch_route()]))
+    return tables, status
+
+
 # ---- the boxes of many labels of one label map in the batch layout (prad_batch_gather_dev, csrc/kernels_batch_gather.h) -------
 def gather_rois_batch(image, labelmap, labels, lo, hi, masks=True, images=True):
     """The boxes of B labels cut out of one 3-D volume in ONE launch, packed the way the *_batch functions take raw images.
