@@ -250,6 +250,20 @@ int prad_debug_sweep_plan(const int *size, int Nd, const int *angles, int Na, in
  * (word counts are narrowed to int.)  tests/test_pipe_plan.py checks these records against a model of the workspace. */
 int prad_debug_pipe_plan(const long long *events, int nevents, int *out, int cap);
 
+/* ---- debug: the route of a segment-mode GLSZM call (no device call, no launch) ------------------------------------------
+ * Plans for `size` ([Nd]), the HOST angle list `angles` ([Na][Nd]) and Ng levels as prad_calculate_glszm_dev does
+ * (csrc/prad_glszm_plan.h); irregular != 0: the route the call is rerun on when its byte pack finds a masked level outside
+ * [1, Ng].  Writes ints to out[0 .. cap), returns their number; -(the number needed) when cap is too small; 0 for arguments no
+ * call accepts.  The record:
+ *   route      0 dense 26, 1 dense 8, 2 / 3 / 4 int32 tiles with the full-26 / full-8 / offset-table border kernel, 5 label volume:
+ *              the prad_last_variant() names "dense26", "dense8", "tiles-full26", "tiles-full8", "tiles-offsets", "label-volume"
+ *   mode       1 the full 26-neighbourhood, 2 the full in-plane 8-neighbourhood, 0 neither
+ *   Nz Ny Nx   the 3-D-embedded extents (1 1 1 for the label volume of more than three dimensions)
+ *   tiles      workgroups of the tile kernel (0: label volume)
+ *   nback      backward offsets (0: label volume), then per offset: dz dy dx
+ * tests/test_glszm_route_plan.py checks these records against the rules. */
+int prad_debug_glszm_route(const int *size, int Nd, const int *angles, int Na, int Ng, int irregular, int *out, int cap);
+
 /* ---- GLCM: calculate_glcm (cmatrices.c:4-92) ---------------------------------------------------- */
 /* glcm: float64 [Nvox][Ng][Ng][Na] */
 int prad_calculate_glcm(const int32_t *image, const uint8_t *mask, const int *size, int Nd,

@@ -9,7 +9,7 @@ import subprocess
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libpyradiomics_amd.so")
-SOURCES = ["prad_api.hip", "prad_binning.hip", "prad_image.hip", "prad_firstorder.hip", "prad_features.hip", "prad_resample.hip", "prad_filters.hip",
+SOURCES = ["prad_api.hip", "prad_glszm.hip", "prad_binning.hip", "prad_image.hip", "prad_firstorder.hip", "prad_features.hip", "prad_resample.hip", "prad_filters.hip",
            "prad_labels.hip", "prad_batch.hip", "prad_batch_glszm.hip", "prad_batch_features.hip", "prad_batch_firstorder.hip",
            "prad_batch_gather.hip", "prad_batch_merge.hip", "prad_batch_swt.hip", "prad_batch_log.hip",
            "prad_batch_resample.hip"]

@@ -1,6 +1,6 @@
 // kernels_batch_glszm.h -- the GLSZM zone lists and matrices of MANY small ROIs, one launch each (gfx950).
 //
-// The single GLSZM call (kernels_glszm.h) labels 256^3 .. 512^3 volumes with a tiled two-level union-find: tile kernel,
+// The single GLSZM call (prad_glszm.hip) labels 256^3 .. 512^3 volumes with a tiled two-level union-find: tile kernel,
 // dense init, pairs, root sum, stats, a read-back, the fill.  A lesion box of 10^3 .. 37^3 voxels fits in LDS whole, so here
 // ONE workgroup of 256 threads labels a ROI completely on chip -- no tiles, no cross-tile pairs, no global forest.
 //
@@ -38,7 +38,7 @@
 //     sweep, at most the nz * ny voxels of one x-plane.  Forced z and forced y keep the reach along x and the slow path of
 //     the unforced kernel, confined to one plane.
 //   * LDS traffic.  Labels are read as ds_read_u16 and levels as ds_read_u8 through address_space(3) pointers (through a
-//     generic volatile pointer the compiler emits flat loads: kernels_glszm.h:175-177).  Banks are 4 bytes wide, 32 of them
+//     generic volatile pointer the compiler emits flat loads: kernels_glszm_labels.h, lds_find).  Banks are 4 bytes wide, 32 of them
 //     for these instructions: with a range of `chunk` voxels per thread, lane l reads label bytes 2 * chunk * l + const, so
 //     chunk = 2 (mod 4) -- an odd number of dwords -- puts the 32 lanes of a half wave on 32 different banks; the level bytes
 //     of two neighbouring lanes then share a bank at most two ways.  Ranges above 8 voxels are rounded up to such a length.

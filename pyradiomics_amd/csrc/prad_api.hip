@@ -15,7 +15,6 @@
 #include "kernels_sweepfw.h"
 #include "kernels_sweepfw2.h"
 #include "kernels_neigh.h"
-#include "kernels_glszm.h"
 #include "kernels_voxel.h"
 #include "kernels_voxslide.h"
 #include "kernels_mcc.h"
@@ -1149,6 +1148,11 @@ int image_shared_pack(Context &c, const int32_t *levels, const uint8_t *mask, lo
   return PRAD_OK;
 }
 void image_shared_pack_clear() { shared_pack() = SharedPack(); }
+
+int glszm_byte_pack(Context &c, hipStream_t s, const Geo &g, const int32_t *image, const uint8_t *mask, int Ng, int *flags_d,
+                    uint8_t **levels) {
+  return neigh_pack(&c, s, g, image, mask, Ng, flags_d, levels);
+}
 }  // namespace prad
 namespace {
 
@@ -1353,10 +1357,6 @@ int copy_back(Context &c, double *host, const double *dev, size_t count) {
 // =================================================================================================
 // extern "C"
 // =================================================================================================
-namespace prad {
-int zone_features_launch(Context &c, hipStream_t s, const double *P, int Ni, int Njcap, long long stride_i,
-                         const double *jvals_d, const int *nj_dev, double *out_d, int *empty_d);   // prad_features.hip
-}
 extern "C" {
 
 const char *prad_version(void) { return kVersion; }
@@ -1419,7 +1419,7 @@ int prad_release_workspace(void) {
     (void)pipelines_sync();
   }
   pipelines_forget(false);                // (what was known to be zero lived in the workspace)
-  glszm_state().valid = false;            // its zone list lives in the workspace
+  glszm_state_invalidate();               // its zone list lives in the workspace
   for (auto &kv : c.bufs) {
     if (kv.second.p) (void)hipFree(kv.second.p);
     kv.second.p = nullptr;
@@ -1799,89 +1799,7 @@ int prad_neigh_finalize_dev(int family, const long long *acc, int Ng, int Na, do
   return neigh_finalize_i64(family, acc, Ng, Na, out, (hipStream_t)stream);
 }
 
-// ---- GLSZM ----------------------------------------------------------------------------------
-int prad_calculate_glszm_dev(const int32_t *image, const uint8_t *mask, const int *size, int Nd, const int *angles,
-                             int Na, int Ng, int Ns, int Nvox, const int *voxels, int kernelRadius, int force2Ddim,
-                             long long *nzones, void *stream) {
-  Context &c = ctx();
-  PRAD_TRY(c.ensure_device());
-  Geo g;
-  PRAD_TRY(make_geo(size, Nd, &g));
-  if (!image || !mask || !angles || Na < 1 || Ng < 1 || Nvox < 1) return fail(PRAD_E_ARG, "bad GLSZM arguments");
-  hipStream_t s = (hipStream_t)stream;
-  PRAD_TRY(c.begin_call(s));
-  int rc = glszm_zones(c, s, g, image, mask, angles, Na, Ng, Ns, Nvox, voxels, kernelRadius, force2Ddim, nzones);
-  PRAD_TRY(c.end_call(s));
-  PRAD_HIP(hipStreamSynchronize(s));
-  return rc;
-}
-int prad_glszm_features_dev(const int32_t *image, const uint8_t *mask, const int *size, int Nd, const int *angles, int Na,
-                            int Ng, int Ns, double *out, int *empty, void *stream) {
-  Context &c = ctx();
-  PRAD_TRY(c.ensure_device());
-  Geo g;
-  PRAD_TRY(make_geo(size, Nd, &g));
-  if (!image || !mask || !angles || !out || !empty || Na < 1 || Ng < 1 || Ns < 1) return fail(PRAD_E_ARG, "bad GLSZM arguments");
-  hipStream_t s = (hipStream_t)stream;
-  PRAD_TRY(c.begin_call(s));
-  {   // (returns the largest zone, 0 here: nothing came back from the device; negative = error)
-    const int zrc = glszm_zones(c, s, g, image, mask, angles, Na, Ng, Ns, 1, nullptr, 0, -1, nullptr, true);
-    if (zrc < 0) return zrc;
-  }
-  GlszmState &st = glszm_state();
-  // distinct sizes sum to at most n voxels, so there are fewer than sqrt(2 n) + 1 of them
-  const int kcap = (int)std::min<long long>(g.n, (long long)std::sqrt(2.0 * (double)g.n) + 2);
-  int *stats = nullptr, *flags_d = nullptr, *large_sorted = nullptr, *meta = nullptr, *err = nullptr;
-  double *jv = nullptr, *P = nullptr, *d_out = nullptr;
-  PRAD_TRY(c.get<int>("glszm_stats", 8, &stats));
-  PRAD_TRY(c.get<int>("flags", 4, &flags_d));
-  PRAD_TRY(c.get<int>("glszm_small_rank", PRAD_SMALL_SIZES, &st.small_rank));
-  PRAD_TRY(c.get<int>("glszm_large_sorted", PRAD_RANK_LARGE + 1, &large_sorted));
-  PRAD_TRY(c.get<int>("glszm_meta", 8, &meta));
-  PRAD_TRY(c.get<int>("glszm_err", 4, &err));
-  PRAD_TRY(c.get<double>("glszm_jvals", (size_t)kcap, &jv));
-  PRAD_TRY(c.get<double>("glszm_compact", (size_t)Ng * kcap, &P));
-  PRAD_TRY(c.get<double>("glszm_feat_out", ZM_FEATURES + 4, &d_out));
-  int *d_empty = reinterpret_cast<int *>(d_out + ZM_FEATURES + 2);
-  PRAD_TRY(ZeroBatch().add(err, sizeof(int) * 4).add(P, sizeof(double) * (size_t)Ng * kcap).launch(s));
-  {
-    Timed t(c, "glszm", s);
-    hipLaunchKernelGGL(glszm_rank_kernel, dim3(1), dim3(1024), 0, s, (const unsigned *)st.small_bits, (const int *)st.large_list,
-                       (const int *)st.large_count, st.large_cap, (const int *)flags_d,
-                       (const unsigned long long *)(stats + 2), 2LL * Ns, kcap, st.small_rank, large_sorted, jv, meta);
-    PRAD_TRY(check_launch("glszm_rank_kernel"));
-    const int RL = Ng <= 8192 ? std::max(1, std::min(kcap, 8192 / Ng)) : 0;
-    hipLaunchKernelGGL(glszm_fill_compact_kernel, dim3(std::min(glszm_grid(g.n), st.parent ? glszm_fill_blocks() : 2048u)), dim3(256), sizeof(unsigned) * Ng * RL,
-                       s, g.n, st.labels, st.sizes, image, Ng, 0, RL, st.small_rank, 0, large_sorted, 0, P, err,
-                       (const int *)st.parent, (const int *)st.rootctl, (const int *)meta, kcap, (const unsigned *)st.tinfo);
-    PRAD_TRY(check_launch("glszm_fill_compact_kernel"));
-  }
-  const size_t nb = sizeof(double) * (ZM_FEATURES + 1);
-  const bool enq = c.deferred && c.in_arena(out, nb) && c.in_arena(empty, sizeof(int));
-  const bool direct = enq && Context::zero_copy();        // values, verdict and flag stored straight into the arena
-  PRAD_TRY(zone_features_launch(c, s, P, Ng, kcap, (long long)kcap, jv, meta + 2, direct ? out : d_out, direct ? empty : d_empty));
-  hipLaunchKernelGGL(glszm_verdict_kernel, dim3(1), dim3(1), 0, s, (const int *)meta, (const int *)err,
-                     (direct ? out : d_out) + ZM_FEATURES);
-  PRAD_TRY(check_launch("glszm_verdict_kernel"));
-  PRAD_TRY(c.end_call(s));
-  c.last_path = "glszm-unionfind";
-  if (direct) return PRAD_OK;
-  if (enq) {
-    PRAD_HIP(hipMemcpyAsync(out, d_out, nb, hipMemcpyDeviceToHost, s));
-    PRAD_HIP(hipMemcpyAsync(empty, d_empty, sizeof(int), hipMemcpyDeviceToHost, s));
-    return PRAD_OK;
-  }
-  void *pin = nullptr;
-  PRAD_TRY(c.get_pinned("glszm_feat_pin", sizeof(double) * (ZM_FEATURES + 4), &pin));
-  PRAD_HIP(hipMemcpyAsync(pin, d_out, sizeof(double) * (ZM_FEATURES + 3), hipMemcpyDeviceToHost, s));
-  PRAD_HIP(hipStreamSynchronize(s));
-  memcpy(out, pin, nb);
-  memcpy(empty, (const char *)pin + sizeof(double) * (ZM_FEATURES + 2), sizeof(int));
-  const int verdict = (int)out[ZM_FEATURES];
-  if (verdict & 2) return fail(PRAD_E_INDEX, "GLSZM: zone list would overflow the reference's Ns-sized scratch (Ns=%d)", Ns);
-  if (verdict) return fail(PRAD_E_UNSUPPORTED, "GLSZM features: the device-side ranking declined (verdict %d); use prad_calculate_glszm_dev", verdict);
-  return PRAD_OK;
-}
+// ---- GLSZM: the host-array wrappers (staging lives here; the entry points for device arrays: prad_glszm.hip) ----
 int prad_calculate_glszm(const int32_t *image, const uint8_t *mask, const int *size, int Nd, const int *angles,
                          int Na, int Ng, int Ns, int Nvox, const int *voxels, int kernelRadius, int force2Ddim,
                          long long *nzones) {
@@ -1891,12 +1809,6 @@ int prad_calculate_glszm(const int32_t *image, const uint8_t *mask, const int *s
   return prad_calculate_glszm_dev(st.image, st.mask, size, Nd, angles, Na, Ng, Ns, Nvox, st.voxels, kernelRadius,
                                   force2Ddim, nzones, c.own_stream);
 }
-int prad_fill_glszm_dev(double *glszm, int Nvox, int Ng, int maxRegion, void *stream) {
-  Context &c = ctx();
-  PRAD_TRY(c.ensure_device());
-  if (!glszm || Ng < 1 || maxRegion < 1) return fail(PRAD_E_ARG, "bad fill_glszm arguments");
-  return glszm_fill(c, (hipStream_t)stream, glszm, Nvox, Ng, maxRegion);
-}
 int prad_fill_glszm(double *glszm, int Nvox, int Ng, int maxRegion) {
   Context &c = ctx();
   PRAD_TRY(c.ensure_device());
@@ -1904,8 +1816,7 @@ int prad_fill_glszm(double *glszm, int Nvox, int Ng, int maxRegion) {
   const size_t n = (size_t)Nvox * Ng * maxRegion;
   double *d = nullptr;
   PRAD_TRY(c.get<double>("o_glszm", n, &d));
-  int rc = glszm_fill(c, c.own_stream, d, Nvox, Ng, maxRegion);
-  if (rc != PRAD_OK) return rc;
+  PRAD_TRY(prad_fill_glszm_dev(d, Nvox, Ng, maxRegion, c.own_stream));
   return copy_back(c, glszm, d, n);
 }
 // ---- fused voxel-based GLCM features -----------------------------------------------------------
@@ -2008,25 +1919,5 @@ int prad_voxel_texture_features_dev(int family, const int32_t *image, const uint
   return voxel_texture_features_dev(family, image, mask, size, Nd, angles, Na, Ng, alpha, Nvox, voxels, kernelRadius,
                                     force2Ddim, feature_ids, nfeat, out, (hipStream_t)stream);
 }
-
-int prad_glszm_sizes(int *sizes, int capacity) {
-  Context &c = ctx();
-  PRAD_TRY(c.ensure_device());
-  return glszm_distinct_sizes(c, sizes, capacity);
-}
-int prad_fill_glszm_compact_dev(double *glszm, int Ng, int nsizes, void *stream) {
-  Context &c = ctx();
-  PRAD_TRY(c.ensure_device());
-  if (!glszm || Ng < 1 || nsizes < 0) return fail(PRAD_E_ARG, "bad fill_glszm_compact arguments");
-  return glszm_fill_compact(c, (hipStream_t)stream, glszm, Ng, nsizes);
-}
-
-long long prad_glszm_zones(int v, int *tempData, long long capacity_pairs) {
-  Context &c = ctx();
-  int rc = c.ensure_device();
-  if (rc != PRAD_OK) return rc;
-  return glszm_copy_zones(c, v, tempData, capacity_pairs);
-}
-
 
 }  // extern "C"

@@ -1,6 +1,6 @@
-// prad_internal.h -- what the host units of the texture engine share: functions that prad_api.hip defines and prad_image.hip
-// (the case pipeline's queues and launcher, no kernel of its own) calls.  Nothing here is exported: the C ABI is
-// include/pyradiomics_amd.h.
+// prad_internal.h -- what the host units of the texture engine share: functions that one of prad_api.hip, prad_glszm.hip and
+// prad_features.hip defines and another of them, or prad_image.hip (the case pipeline's queues and launcher, no kernel of its
+// own), calls.  Nothing here belongs to the C ABI: that is include/pyradiomics_amd.h.
 #pragma once
 #include "prad_runtime.h"
 
@@ -28,7 +28,18 @@ int image_shared_pack(Context &c, const int32_t *levels, const uint8_t *mask, lo
                       hipStream_t s);
 void image_shared_pack_clear();
 
+// prad_glszm.hip's dense routes: the byte pack of a whole volume on s, bracketed as "pack", or the shared pack above when it is
+// this image's; flags_d[0] != 0: a masked level outside [1, Ng]
+int glszm_byte_pack(Context &c, hipStream_t s, const Geo &g, const int32_t *image, const uint8_t *mask, int Ng, int *flags_d,
+                    uint8_t **levels);
+// prad_glszm.hip: the zones of the last GLSZM call live in the workspace and go with it (prad_release_workspace)
+void glszm_state_invalidate();
+
 #pragma GCC visibility pop
+
+// prad_features.hip, for prad_glszm_features_dev: launch only, the columns were found on the device (default visibility, as defined)
+int zone_features_launch(Context &c, hipStream_t s, const double *P, int Ni, int Njcap, long long stride_i,
+                         const double *jvals_d, const int *nj_dev, double *out_d, int *empty_d);
 }  // namespace prad
 
 // prad_image.hip: the image queues' streams and events go with the workspace (prad_release_workspace).  C linkage and default

@@ -80,7 +80,7 @@ struct Context {
   hipEvent_t call_a = nullptr, call_b = nullptr;
   bool call_timed = false;
   const char *last_path = "none";
-  const char *last_variant = "none";   // which kernels served the last call: "fw", "fw2", "lines", "pairs" (GLCM / GLRLM), "neigh4-full26", "neigh4-rows", "neigh1", "pairs-lds64|lds32|global[+box32|+box64]" (GLDM / NGTDM); INTEGRATION.md
+  const char *last_variant = "none";   // which kernels served the last call: "fw", "fw2", "lines", "pairs" (GLCM / GLRLM), "neigh4-full26", "neigh4-rows", "neigh1", "pairs-lds64|lds32|global[+box32|+box64]" (GLDM / NGTDM), "dense26", "dense8", "tiles-full26", "tiles-full8", "tiles-offsets", "label-volume", "voxel-flood" (GLSZM: the route the HOST chose, prad_glszm_plan.h, after the retry of an irregular level; a work-list overflow is decided on the device and not reported); INTEGRATION.md
   // deferred mode (prad_set_deferred): GLCM/GLRLM device calls only enqueue work; the "levels outside [1, Ng]" flag of
   // every such call is latched into a sticky device word that prad_deferred_status() reads after synchronising
   bool deferred = false;
@@ -109,11 +109,6 @@ struct Context {
   unsigned long long lane_seq = 0;
   hipStream_t lane_stream[PRAD_MAX_LANES] = {};
   hipEvent_t lane_in[PRAD_MAX_LANES] = {};
-  // GLSZM phase-1 -> phase-2 state
-  long long glszm_nzones = 0;
-  int glszm_nvox = 0;
-  int glszm_max_region = 0;
-  std::vector<long long> glszm_zone_offsets;  // per kernel, into the device zone list (size nvox+1)
 
   int ensure_device() {
     if (!device_set) {

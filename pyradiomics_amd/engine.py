@@ -593,7 +593,9 @@ def last_path() -> str:
 
 def last_variant() -> str:
     """which kernels served the last call: "fw", "fw2", "lines" or "pairs" for GLCM / GLRLM; "neigh4-full26", "neigh4-rows",
-    "neigh1" or "pairs-lds64|lds32|global[+box32|+box64]" for GLDM / NGTDM (INTEGRATION.md)"""
+    "neigh1" or "pairs-lds64|lds32|global[+box32|+box64]" for GLDM / NGTDM; "dense26", "dense8", "tiles-full26", "tiles-full8",
+    "tiles-offsets", "label-volume" or "voxel-flood" for GLSZM -- the host's choice, after the retry of an irregular level; a
+    work-list overflow is decided on the device and not reported"""
     return _lib.last_variant()
 
 

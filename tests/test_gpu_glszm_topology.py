@@ -17,15 +17,18 @@ workspace gives the same bits; the dense matrix == reference == C checker where 
 dense call.  On a mismatch of the zone list the message names the first wrong zone, its first voxel, the nearest tile corner
 and prints the levels around it.
 
-Tile grid: 8 (z) x 8 (y) x 64 (x).  Routes and the cases that reach them are listed at each test.
+Tile grid: 8 (z) x 8 (y) x 64 (x).  Routes and the cases that reach them are listed at each test, and each test asserts the
+route its calls took: prad_last_variant() names the host's choice (csrc/prad_glszm_plan.h), after the retry of an irregular
+level; whether the work list overflowed is decided on the device and is not in the name.
 
 One kernel bug was found and fixed, in the ordered zone list only (matrices, zone counts and sizes were right throughout):
 glszm_zmin_kernel took parent[id] for the zone root, but glszm_rootsum_dense_kernel leaves parent[] only nearly flat -- see
 test_zone_order_when_the_parent_chains_are_not_flat.  On the kernels before the fix 9 of the 562 cases of this module failed,
 all on the order of two zones; with the fix all 563 pass (18 s on an MI355X).
 
-Sharpness.  One-line mutations of kernels_glszm.h in scratch builds (loaded through PRAD_LIB, never committed), each run once
-against this module on an MI355X, and the tests that failed (number of failing cases in brackets):
+Sharpness.  One-line mutations of the kernels (csrc/kernels_glszm_dense.h, kernels_glszm_labels.h) in scratch builds (loaded
+through PRAD_LIB, never committed), each run once against this module on an MI355X, and the tests that failed (number of
+failing cases in brackets):
     N2 grown without the `S2 &` restriction (pairs pruned through voxels of another level)                       [136]
         test_default_route (71), test_work_list_capacities, test_serpentine_and_combs_along_every_axis, test_random_blocks_on_seams,
         test_int32_route_by_irregular_level, test_level_shards, test_one_queue_features, test_pairs_kernel_grid,
@@ -514,8 +517,23 @@ def _explain(vol, z, got):
     return msg
 
 
-def _check(cm, checker, vol, force2D=False, f2d=0, Ng=None, dense=True):
-    """everything the module docstring lists, for one volume and one neighbourhood; -> number of GPU labellings made"""
+def _variant():
+    from pyradiomics_amd import _lib
+    return _lib.last_variant()
+
+
+def _dense(force2D):
+    """the name of the dense route (prad_last_variant): 26-neighbourhood, or the in-plane 8 of force2D along axis 0"""
+    return "dense8" if force2D else "dense26"
+
+
+def _int32(force2D):
+    return "tiles-full8" if force2D else "tiles-full26"
+
+
+def _check(cm, checker, vol, force2D=False, f2d=0, Ng=None, dense=True, route=None):
+    """everything the module docstring lists, for one volume and one neighbourhood; -> number of GPU labellings made.
+    route: the name prad_last_variant() must give after every labelling (the host's choice, after any retry)"""
     Ng = vol.Ng if Ng is None else Ng
     img, mask = vol.img, vol.mask
     Ns = int(mask.sum())
@@ -526,6 +544,7 @@ def _check(cm, checker, vol, force2D=False, f2d=0, Ng=None, dense=True):
     Pr, sr = gr.compact(z, Ng)
     want_list = gr.zone_list(z)
     P, s = cm.calculate_glszm_compact(img, mask, Ng, Ns, force2D, f2d)
+    assert route is None or _variant() == route, "%s: route %s, expected %s" % (vol.name, _variant(), route)
     nz, largest = int(P.sum()), (int(s[-1]) if len(s) else 0)
     assert nz == len(z) and largest == (int(z[:, 1].max()) if len(z) else 0), \
         "%s: %d zones, largest %d; reference %d, %d" % (vol.name, nz, largest, len(z), int(z[:, 1].max()) if len(z) else 0)
@@ -537,9 +556,11 @@ def _check(cm, checker, vol, force2D=False, f2d=0, Ng=None, dense=True):
         assert np.array_equal(got, want_list), "zone list (call %d) " % (again + 1) + _explain(vol, z, got)
     P2, s2 = cm.calculate_glszm_compact(img, mask, Ng, Ns, force2D, f2d)     # same workspace: stale rootctl, bitmaps, lists
     assert np.array_equal(s2, s) and np.array_equal(P2, P), "%s: second call on the same workspace" % vol.name
+    assert route is None or _variant() == route
     calls = 2
     if dense and Ng * max(largest, 1) <= DENSE_MAX:
         D = cm.calculate_glszm(img, mask, Ng, Ns, force2D, f2d)
+        assert route is None or _variant() == route
         want = gr.matrix(z, Ng)
         assert D.shape == want.shape and np.array_equal(D, want), "%s: dense matrix" % vol.name
         got = _gpu_zone_list(Ns)
@@ -555,7 +576,7 @@ def _check(cm, checker, vol, force2D=False, f2d=0, Ng=None, dense=True):
 @pytest.mark.parametrize("case", CATALOGUE_IDS)
 def test_default_route(cm, checker, case, force2D):
     from pyradiomics_amd import _lib
-    _check(cm, checker, BY_ID[case](), force2D, 0)
+    _check(cm, checker, BY_ID[case](), force2D, 0, route=_dense(force2D))
     assert _lib.last_path() == "glszm-unionfind"
 
 
@@ -609,14 +630,14 @@ def test_work_list_capacities(cm, checker, case, force2D, workcap, monkeypatch):
     their pairs before a later one finds the list full, at 1 none has; glszm_border8d_kernel must cope with both, and a list
     that never fills must give what the default capacity gives."""
     monkeypatch.setenv("PRAD_GLSZM_WORKCAP", str(workcap))
-    _check(cm, None, BY_ID[case](), force2D, 0)
+    _check(cm, None, BY_ID[case](), force2D, 0, route=_dense(force2D))     # (the overflow is the device's choice: not in the name)
 
 
 def test_work_list_capacities_on_random_blocks(cm, monkeypatch):
     for workcap in (1, 37, 1 << 24):
         monkeypatch.setenv("PRAD_GLSZM_WORKCAP", str(workcap))
         for force2D in (False, True):
-            _check(cm, None, random_blocks((72, 72, 264), (0, 0, 0), 271, 2), force2D, 0, dense=False)
+            _check(cm, None, random_blocks((72, 72, 264), (0, 0, 0), 271, 2), force2D, 0, dense=False, route=_dense(force2D))
 
 
 # ---- route 3: the int32 tile kernels ----------------------------------------------------------------------------------------------
@@ -625,7 +646,7 @@ def test_work_list_capacities_on_random_blocks(cm, monkeypatch):
 @pytest.mark.parametrize("case", MULTI_TILE)
 def test_int32_route_by_level_count(cm, checker, case, force2D, Ng):
     """Ng > 255 does not fit the packed bytes: glszm_tile_kernel + glszm_border_full_kernel<1|2> label the same volumes"""
-    _check(cm, checker if Ng == 256 else None, BY_ID[case](), force2D, 0, Ng=Ng)
+    _check(cm, checker if Ng == 256 else None, BY_ID[case](), force2D, 0, Ng=Ng, route=_int32(force2D))
 
 
 @pytest.mark.parametrize("Ng", [256, 300])
@@ -633,15 +654,15 @@ def test_int32_route_singles_at_the_level_count(cm, checker, Ng):
     """4096 zones in one tile and zones == voxels in many tiles, with levels up to Ng itself"""
     for vol in (singles((8, 8, 64), Ng), singles((17, 17, 130), Ng, 1)):
         assert vol.img.max() == Ng
-        _check(cm, checker, vol, False, 0)
-        _check(cm, checker, vol, True, 0)
+        _check(cm, checker, vol, False, 0, route=_int32(False))
+        _check(cm, checker, vol, True, 0, route=_int32(True))
 
 
 @pytest.mark.parametrize("f2d", [1, 2])
 @pytest.mark.parametrize("case", MULTI_TILE)
 def test_int32_route_by_force2d_dimension(cm, checker, case, f2d):
     """force2Ddimension 1 and 2: four in-plane offsets that are not the x-y ones (mode 0, glszm_border_kernel)"""
-    _check(cm, checker, BY_ID[case](), True, f2d)
+    _check(cm, checker, BY_ID[case](), True, f2d, route="tiles-offsets")
 
 
 @pytest.mark.parametrize("bad", [0, 9])
@@ -661,12 +682,13 @@ def test_int32_route_by_irregular_level(cm, checker, case, force2D, bad):
         checker.calculate_glszm(vol.img, vol.mask, vol.Ng, Ns, force2D, 0)
     with pytest.raises(IndexError):
         cm.calculate_glszm(vol.img, vol.mask, vol.Ng, Ns, force2D, 0)
+    assert _variant() == _int32(force2D), "the route after the retry"
     z = vol.zones(force2D, 0)
     assert ((z[:, 0] == bad) & (z[:, 1] == 1)).sum() == 1
     for again in range(2):
         got = _gpu_zone_list(Ns)
         assert np.array_equal(got, gr.zone_list(z)), "zone list (call %d) " % (again + 1) + _explain(vol, z, got)
-    _check(cm, checker, base, force2D, 0)
+    _check(cm, checker, base, force2D, 0, route=_dense(force2D))
 
 
 def test_empty_mask(cm, checker):
@@ -713,7 +735,7 @@ def test_label_volume_route_4d(cm, checker, shape):
     voxel a zone (16 colours by coordinate parity), one level, and a stack of serpentines whose path and walls each fuse
     across the fourth axis"""
     for m in (2, 3):
-        _check(cm, checker, checkerboard(shape, m))
+        _check(cm, checker, checkerboard(shape, m), route="label-volume")
     idx = np.indices(shape)
     colour = sum((idx[d] & 1) << d for d in range(4))
     rng = np.random.default_rng(4)
@@ -721,12 +743,12 @@ def test_label_volume_route_4d(cm, checker, shape):
     cen = {}
     for g, c in enumerate(np.bincount(lvl.ravel())):
         _add(cen, g, 1, int(c))
-    _check(cm, checker, Vol("singles4d%s" % (shape,), lvl, None, 240, cen))
-    _check(cm, checker, uniform(shape, 2, 2))
+    _check(cm, checker, Vol("singles4d%s" % (shape,), lvl, None, 240, cen), route="label-volume")
+    _check(cm, checker, uniform(shape, 2, 2), route="label-volume")
     s3 = serpentine(shape[1:])
     n1 = sum(sz * c for (g, sz), c in s3.cen.items() if g == 1)
     cen = _add(_add({}, 1, shape[0] * n1), 2, shape[0] * (s3.img.size - n1))
-    _check(cm, checker, Vol("serpentine4d%s" % (shape,), np.broadcast_to(s3.img, shape), None, 2, cen))
+    _check(cm, checker, Vol("serpentine4d%s" % (shape,), np.broadcast_to(s3.img, shape), None, 2, cen), route="label-volume")
 
 
 @pytest.mark.parametrize("shape", [(17, 130), (64, 64), (9, 255), (130, 17)])
@@ -735,14 +757,14 @@ def test_2d_input(cm, checker, shape):
     zone), combs, every pixel a zone"""
     Ny, Nx = shape
     plane, _, _, _, cen = serp_plane(Ny, Nx)
-    _check(cm, checker, Vol("serp2d%s" % (shape,), plane, None, 2, cen))
+    _check(cm, checker, Vol("serp2d%s" % (shape,), plane, None, 2, cen), route="dense8")
     for m in (2, 3):
         c3 = checkerboard((1, Ny, Nx), m)
-        _check(cm, checker, Vol("chk2d%s/%d" % (shape, m), c3.img[0], None, m, c3.cen2))
+        _check(cm, checker, Vol("chk2d%s/%d" % (shape, m), c3.img[0], None, m, c3.cen2), route="dense8")
     c3 = combs((1, Ny, Nx))
-    _check(cm, checker, Vol("combs2d%s" % (shape,), c3.img[0], None, 3, c3.cen))
+    _check(cm, checker, Vol("combs2d%s" % (shape,), c3.img[0], None, 3, c3.cen), route="dense8")
     s3 = singles((1, Ny, Nx), 255, 2)
-    _check(cm, checker, Vol("singles2d%s" % (shape,), s3.img[0], None, 255, s3.cen))
+    _check(cm, checker, Vol("singles2d%s" % (shape,), s3.img[0], None, 255, s3.cen), route="dense8")
 
 
 # ---- route 5: the lanes of glszm_pairs_kernel ------------------------------------------------------------------------------------
@@ -782,6 +804,7 @@ def test_large_volume_compact(cm, kind):
     vol = {"serpentine": serpentine, "checkerboard": checkerboard, "combs": combs}[kind].__wrapped__(shape)     # (not kept)
     Ns = vol.img.size
     P, s = cm.calculate_glszm_compact(vol.img, vol.mask, vol.Ng, Ns, False, 0)
+    assert _variant() == "dense26"
     Pc, sc = gr.census_matrix(vol.cen, vol.Ng)
     assert np.array_equal(s, sc) and np.array_equal(P[0], Pc), "closed form"
     z = vol.zones()
@@ -812,6 +835,7 @@ def test_one_queue_features(case, force2D):
     Ns = int(vol.mask.sum())
     got, flag = engine.glszm_features(L, M, vol.Ng, Ns, force2D, 0)
     assert got[16] == 0 and flag[0] == 0
+    assert _variant() == _dense(force2D)
     for k, n in enumerate(fr.ZONE_NAMES):
         want = float(ref["values"][n])
         print("%s %s err %.3g bound %.3g" % (vol.name, n, abs(got[k] - want), B[n]))
@@ -867,6 +891,7 @@ def test_voxel_mode_on_tile_corners(cm, checker, case, radius, force2D, masked):
     Ns = int(mask.sum())
     want = checker.calculate_glszm(vol.img, mask, vol.Ng, Ns, force2D, 0, kernelRadius=radius, voxels=vox)
     got = cm.calculate_glszm(vol.img, mask, vol.Ng, Ns, force2D, 0, kernelRadius=radius, voxels=vox)
+    assert _variant() == "voxel-flood"
     assert got.shape == want.shape and np.array_equal(got, want), (vol.name, radius, force2D, masked)
     # and the independent reference on the crop of every kernel
     for v, (z, y, x) in enumerate(centres):
