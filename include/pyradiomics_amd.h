@@ -862,6 +862,43 @@ int prad_batch_log_plan(const int *sizes, int B, const double *spacing, const do
 int prad_batch_log_dev(const void *in, int dtype, const int *sizes, const long long *off, int B, const double *spacing,
                        const double *sigmas, int S, int normalize, void *out, long long row_stride, int *verdict, void *stream);
 
+/* ---- the intensity transforms and the Gradient magnitude of many small boxes (csrc/kernels_batch_intensity.h) ---------------
+ * prad_batch_intensity_dev: the image types Square, SquareRoot, Logarithm, Exponential and Gradient of the reference
+ * (imageoperations.py:973-1091) on each of B boxes ALONE, in at most TWO launches for all boxes and all requested types.
+ * `in` (DEVICE) holds the boxes in the batch layout of prad_batch_firstorder_dev, in the image's own dtype (0 float32,
+ * 1 float64, 2 int32, 3 int16; widened to float64: exact); sizes ([B][3], z y x), off (element offsets, ascending, boxes not
+ * overlapping) and spacing ([B][3], z y x, per ROI; NULL = 1 everywhere; read for Gradient with gradientUseSpacing != 0 only)
+ * are HOST arrays.  types: bit 0 square, 1 squareroot, 2 logarithm, 3 exponential, 4 gradient.
+ * out64 DEVICE float64 [rows][row_stride], one row per requested pointwise type in the order of the bits, row_stride >=
+ * off[B - 1] + its voxels: the image of ROI b lies at out64 + row * row_stride + off[b] in the box's own shape -- every row is a
+ * batch-layout buffer.  With top = max |x| over the BOX: square (x / sqrt(top))^2 as (c x)(c x), c = 1 / sqrt(top); squareroot
+ * sign(x) sqrt(|x| top); logarithm (sign(x) log(|x| + 1)) (top / log(top + 1)); exponential exp((log(top) / top) x) -- float64,
+ * no contraction, the operations of the single route in their order.  out_grad DEVICE float32 [off[B - 1] + its voxels]: per
+ * axis z, y, x of extent > 1 the central difference 0.5 (x[i + 1] - x[i - 1]) with the neighbours clamped to the box (the box's
+ * own edge is replicated), times 1 / spacing[axis] rounded on the host (with gradientUseSpacing), squared and summed in that
+ * order in float64; the root rounded once to float32.  out64 / out_grad may be NULL when no bit asks for them.
+ * verdict HOST int [B]: 0 the ROI was computed here; 1 top == 0 (the reference's formulas divide by zero): no pointwise row of
+ * the ROI is written, its Gradient -- all zeros -- is; 2 a float box holds a NaN or an infinity: the caller fills every
+ * requested image of the ROI from the single route.  With a pointwise type a launch of one workgroup per ROI works out top,
+ * the constants and the verdicts, and the image launch writes nothing for a ROI of verdict 2; Gradient ALONE is ONE launch, which
+ * finds such a ROI itself -- its slice of out_grad is then written (NaN where the arithmetic gives NaN) and must be replaced.
+ * One copy (the record and item tables), the launches and one read-back (the verdicts) on `stream`, which is then synchronised;
+ * no atomics, no memset; kernel family "batch_intensity" (prad_last_kernel_ms), prad_last_path "batch", prad_last_variant
+ * "batch-intensity" ("batch-gradient" for Gradient alone).  B = 0 is a valid call that launches nothing.  Boxes are not capped.
+ * PRAD_E_ARG, before anything is launched: a NULL pointer, B < 0, types outside [1, 31], a size < 1, a spacing that is read and
+ * is not > 0 and finite, a negative offset, off[b] before the end of ROI b - 1, row_stride before the end of the last box, a dtype
+ * outside the list.  PRAD_E_UNSUPPORTED: more than 16 777 215 ROIs or workgroups (about 1.7e10 voxels) in one call.
+ * prad_batch_intensity_plan (host only, pure, needs no device): the planner the call itself uses.  *n_items = the workgroups
+ * of the image launch; items (may be NULL; int64 [*n_items][4], size it with a first call) = per workgroup the half-open range
+ * [w0, w1) of the batch's voxels in their packed order (voxel w of the batch is element w - sum of the voxels of the boxes before
+ * its own of that box) and the first and last ROI the range touches; a workgroup writes its voxels of every requested row.  The
+ * ranges tile [0, W) exactly once.  grid HOST int64 [2]: the workgroups of the two launches (grid[0] = 0 for Gradient alone).
+ * Same argument errors as the call. */
+int prad_batch_intensity_plan(const int *sizes, int B, int types, long long *n_items, long long *items, long long *grid);
+int prad_batch_intensity_dev(const void *in, int dtype, const int *sizes, const long long *off, int B, int types,
+                             const double *spacing, int gradientUseSpacing, double *out64, long long row_stride, float *out_grad,
+                             int *verdict, void *stream);
+
 /* ---- resampling many small boxes, each onto a grid of its own (csrc/kernels_batch_resample.h) ------------------------------
  * prad_batch_mask_boxes_dev: mask (DEVICE, uint8, non-zero = ROI) holds B boxes in the batch layout; sizes ([B][3], z y x) and
  * off (element offsets) are HOST arrays.  boxes HOST int [B][7]: lo z / y / x, hi z / y / x (inclusive) and the voxel count of

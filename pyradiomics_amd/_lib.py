@@ -159,6 +159,10 @@ SYMBOLS = {
     "prad_batch_log_plan": (C.c_int, [_ip, C.c_int, _vp, _vp, C.c_int, _ip, _ip, C.POINTER(C.c_longlong)]),
     "prad_batch_log_dev": (C.c_int, [_vp, C.c_int, _ip, C.POINTER(C.c_longlong), C.c_int, _vp, _vp, C.c_int, C.c_int, _vp,
                                      C.c_longlong, _ip, _vp]),
+    "prad_batch_intensity_plan": (C.c_int, [_ip, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                            C.POINTER(C.c_longlong)]),
+    "prad_batch_intensity_dev": (C.c_int, [_vp, C.c_int, _ip, C.POINTER(C.c_longlong), C.c_int, C.c_int, _vp, C.c_int, _vp,
+                                           C.c_longlong, _vp, _ip, _vp]),
     "prad_batch_resample_max_vox": (C.c_int, []),
     "prad_batch_mask_boxes_dev": (C.c_int, [_vp, _ip, C.POINTER(C.c_longlong), C.c_int, _ip, _vp]),
     "prad_batch_resample_dev": (C.c_int, [_vp, C.c_int, _vp, _ip, C.POINTER(C.c_longlong), C.c_int, _vp, _vp, _ip, _ip,

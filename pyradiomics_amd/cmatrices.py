@@ -808,6 +808,36 @@ def calculate_log_batch(images, sigma, spacing=(1.0, 1.0, 1.0)):
             for s, name in enumerate(names)}, tuple(names)
 
 
+def _host_boxes(flat, sizes):
+    """a flat host row in the batch layout -> [B numpy arrays in the boxes' shapes]"""
+    off = np.concatenate([[0], np.cumsum(sizes.astype(np.int64).prod(1))])
+    return [flat[off[b]:off[b + 1]].reshape(tuple(sizes[b])).copy() for b in range(len(sizes))]
+
+
+def calculate_intensity_batch(images, types=("Square", "SquareRoot", "Logarithm", "Exponential")):
+    """The Square, SquareRoot, Logarithm and Exponential images of B small 3-D boxes (a list of host arrays: raw intensities):
+    one upload, engine.intensity_batch -- two launches for all boxes and all types -- and one download.  -> ({image type name:
+    [B float64 numpy arrays in the boxes' shapes]}, names): the names the single functions yield ("square", "squareroot",
+    "logarithm", "exponential"), in the order of the rows.  Every image is that of the box ALONE (its own max |x|).  Needs a
+    device (RuntimeError without one); last_batch_route() tells which route ran."""
+    ones = [np.ones(np.shape(i), dtype=bool) for i in images]
+    _, _, sizes, upload = _host_roi_batch(images, ones, "intensity transforms", raw=True)
+    rows, names, _ = _engine().intensity_batch(upload()[0], sizes, types)
+    host = rows.cpu().numpy()
+    return {name: _host_boxes(host[r], sizes) for r, name in enumerate(names)}, tuple(names)
+
+
+def calculate_gradient_batch(images, spacing=(1.0, 1.0, 1.0), gradientUseSpacing=True):
+    """The Gradient magnitude images of B small 3-D boxes (a list of host arrays: raw intensities): one upload,
+    engine.gradient_batch -- one launch for all boxes -- and one download.  spacing: (z, y, x), one triple or [B, 3].  -> ([B
+    float32 numpy arrays in the boxes' shapes], "gradient"); the box's own edge is replicated.  Needs a device (RuntimeError
+    without one); last_batch_route() tells which route ran."""
+    ones = [np.ones(np.shape(i), dtype=bool) for i in images]
+    _, _, sizes, upload = _host_roi_batch(images, ones, "gradient images", raw=True)
+    image, name, _ = _engine().gradient_batch(upload()[0], sizes, spacing, gradientUseSpacing)
+    return _host_boxes(image.cpu().numpy(), sizes), name
+
+
 def calculate_mask_boxes_batch(masks):
     """The bounding boxes of B 3-D masks (a list of host arrays, non-zero = ROI): one upload, engine.mask_boxes_batch -- one
     launch -- and one read-back.  -> (lo int64 [B, 3], hi int64 [B, 3], count int64 [B]), inclusive (z, y, x) bounds; an empty

@@ -1146,4 +1146,6 @@ from .roi_batch import (FEATURE_FAMILIES, ROI_FEATURE_CLASSES, batch_digitize_ma
                         BandNames, batch_swt_occupancy, batch_swt_plan, roi_features_batch_images, wavelet_band_names,
                         wavelet_batch, batch_log_plan, log_batch, roi_features_batch_derived,
                         RESAMPLE_EMPTY, ResamplePlan, batch_resample_max_vox, batch_resample_plan, mask_boxes_batch,
-                        resample_batch, resample_boxes_batch, roi_features_batch_resampled)
+                        resample_batch, resample_boxes_batch, roi_features_batch_resampled,
+                        INTENSITY_NONFINITE, INTENSITY_TYPES, INTENSITY_ZERO, batch_intensity_plan, gradient_batch,
+                        intensity_batch, roi_features_batch_types)

@@ -1016,6 +1016,157 @@ def log_batch(images, sizes=None, sigma=(1.0, 2.0, 3.0), spacing=(1.0, 1.0, 1.0)
     return logs, names, rois.sizes, valid
 
 
+# ---- intensity transforms and Gradient of the boxes (prad_batch_intensity_dev, csrc/kernels_batch_intensity.h) ---------------
+INTENSITY_TYPES = ("Square", "SquareRoot", "Logarithm", "Exponential")      # bit k of the C `types`, in the order of the rows
+_GRADIENT_BIT = 1 << len(INTENSITY_TYPES)
+INTENSITY_ZERO = 1         # verdict of a ROI whose box is all zeros: the reference's formulas divide by zero (the single route)
+INTENSITY_NONFINITE = 2    # verdict of a float ROI that holds a NaN or an infinity (the single route, Gradient included)
+
+
+def _intensity_bits(types, what="intensity_batch"):
+    """the image type names `types` -> (the C bit mask, the names in the order of the rows); ValueError for any other name"""
+    types = (types,) if isinstance(types, str) else tuple(types)
+    unknown = [t for t in types if t not in INTENSITY_TYPES]
+    if unknown or not types:
+        raise ValueError("%s: types must be a non-empty subset of %s, got %r" % (what, INTENSITY_TYPES, types))
+    bits = sum(1 << INTENSITY_TYPES.index(t) for t in set(types))
+    return bits, tuple(t for t in INTENSITY_TYPES if t in types)
+
+
+def batch_intensity_plan(sizes, types=INTENSITY_TYPES + ("Gradient",)):
+    """Host-side plan of the batched intensity launches (prad_batch_intensity_plan; pure, needs no device).  sizes: int [B, 3] (B = 0
+    is a valid, empty plan); types: names out of "Square", "SquareRoot", "Logarithm", "Exponential", "Gradient".  -> (items int64
+    [n, 4]: per workgroup of the image launch the half-open range [w0, w1) of the batch's voxels in their packed order and the
+    first and last ROI the range touches -- a workgroup writes its voxels of every requested row; grid int64 [2]: the workgroups
+    of the constants launch -- one per ROI, 0 for Gradient alone -- and of the image launch).  ValueError for an unknown type
+    or a size below 1, NotImplementedError above the grid limit."""
+    types = (types,) if isinstance(types, str) else tuple(types)
+    bits = _GRADIENT_BIT if "Gradient" in types else 0
+    rest = tuple(t for t in types if t != "Gradient")
+    if rest or not bits:
+        bits |= _intensity_bits(rest, "batch_intensity_plan")[0]
+    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
+    B = int(sizes.shape[0])
+    lib = _lib.load()
+    n = C.c_longlong(0)
+    grid = np.zeros(2, dtype=np.int64)
+    _lib.raise_for(lib.prad_batch_intensity_plan(_iptr(sizes), B, bits, C.byref(n), None, _lp(grid)), "batch intensity plan")
+    items = np.zeros((max(int(n.value), 1), 4), dtype=np.int64)
+    _lib.raise_for(lib.prad_batch_intensity_plan(_iptr(sizes), B, bits, C.byref(n), _lp(items), _lp(grid)), "batch intensity plan")
+    return items[:int(n.value)], grid
+
+
+def _flat_voxels(images, sizes, what):
+    """the voxels of the batch, from the arguments alone (no device is asked): lists give their own shapes, a flat tensor must
+    hold what `sizes` describes"""
+    if isinstance(images, (list, tuple)):
+        if not len(images):
+            raise ValueError("empty batch")
+        return int(sum(int(i.numel()) for i in images))
+    if sizes is None:
+        raise ValueError("a flat image tensor needs `sizes`")
+    nvox = np.asarray(sizes, dtype=np.int64).reshape(-1, 3).prod(1)
+    if not len(nvox) or int(nvox.sum()) != images.numel():
+        raise ValueError("%s: sizes describe %d voxels, the buffer holds %d" % (what, int(nvox.sum()), images.numel()))
+    return int(nvox.sum())
+
+
+def _check_out(out, dtype, shape, what):
+    """`out` of the intensity calls: a tensor of `dtype` and `shape` with contiguous rows (row stride >= the row length)"""
+    if out is None:
+        return
+    W = shape[-1]
+    ok = (out.dtype == dtype and tuple(out.shape) == tuple(shape) and (W <= 1 or out.stride(-1) == 1)
+          and (len(shape) == 1 or shape[0] <= 1 or out.stride(0) >= W))
+    if not ok:
+        raise ValueError("%s: out must be a %s %s tensor with contiguous rows" % (what, dtype, list(shape)))
+
+
+def _intensity(rois, bits, spacing, use_spacing, out, out_grad):
+    """the C call and the fallback for any subset of the five types; out / out_grad have been checked but for their device.
+    -> (rows float64 [T, W] or None, gradient float32 [W] or None, verdict [B])"""
+    from . import filters
+    from .image import Image
+    B, W = rois.B, rois.data.numel()
+    names = [t for k, t in enumerate(INTENSITY_TYPES) if bits >> k & 1]
+    T, grad = len(names), bool(bits & _GRADIENT_BIT)
+    for o in (out, out_grad):
+        if o is not None and o.device != rois.device:
+            raise ValueError("out must live on %s" % (rois.device,))
+    if T and out is None:
+        out = torch.empty((T, W), dtype=torch.float64, device=rois.device)
+    if grad and out_grad is None:
+        out_grad = torch.empty(W, dtype=torch.float32, device=rois.device)
+    sp = _cm.batch_spacing(spacing, B)
+    if grad and use_spacing and not (np.isfinite(sp).all() and (sp > 0).all()):
+        raise ValueError("spacing must be positive and finite")
+    stride = int(out.stride(0)) if T > 1 else W
+    verdict = np.zeros(B, dtype=np.intc)
+    rc = rois.lib.prad_batch_intensity_dev(_vp(rois.data), _eng._DTYPE_CODES[rois.data.dtype], _iptr(rois.sizes), _lp(rois.off), B,
+                                           bits, C.c_void_p(sp.ctypes.data), 1 if use_spacing else 0, _vp(out if T else None),
+                                           stride, _vp(out_grad if grad else None), _iptr(verdict), _eng._stream_ptr())
+    _lib.raise_for(rc, "batched intensity transforms")
+    # the ROIs the kernels leave alone: the single route box by box, into the same layout (its NaN / inf are the single route's)
+    single = {"Square": filters.getSquareImage, "SquareRoot": filters.getSquareRootImage,
+              "Logarithm": filters.getLogarithmImage, "Exponential": filters.getExponentialImage}
+    looped = 0
+    for b in np.flatnonzero(verdict != 0):
+        o, n = int(rois.off[b]), int(rois.nvox[b])
+        box = Image(tensor=rois.view(rois.data, b), spacing=tuple(float(s) for s in sp[b][::-1]))
+        for row, t in enumerate(names):
+            image, _, _ = next(single[t](box, None, deviceResident=True))
+            out[row, o:o + n] = image.device_tensor().reshape(-1)
+        if grad and verdict[b] == INTENSITY_NONFINITE:
+            image, _, _ = next(filters.getGradientImage(box, None, deviceResident=True, gradientUseSpacing=bool(use_spacing)))
+            out_grad[o:o + n] = image.device_tensor().reshape(-1)
+        looped += 1 if (T or verdict[b] == INTENSITY_NONFINITE) else 0
+    _cm._set_batch_route(_route(looped, B))
+    return (out if T else None), (out_grad if grad else None), verdict
+
+
+def intensity_batch(images, sizes=None, types=INTENSITY_TYPES, out=None):
+    """The Square, SquareRoot, Logarithm and Exponential images of B small boxes in TWO launches whatever B and the number of types:
+    per box what filters.getSquareImage ... getExponentialImage compute on the box alone.  With top = max |x| of the BOX AS HANDED
+    OVER -- not of the scan it was cut from: the values are those of `execute` on the box, the reference's with preCrop --
+    square (c x)(c x), c = 1 / sqrt(top); squareroot sign(x) sqrt(|x| top); logarithm sign(x) log(|x| + 1) top / log(top + 1);
+    exponential exp(log(top) / top x), in float64 with the single route's operations in their order: square and squareroot equal
+    it bit for bit, logarithm and exponential to the accuracy of two implementations of log and exp.  images: as wavelet_batch
+    takes them (a list of 3-D device tensors of one dtype -- float32, float64, int32, int16; anything else is widened to float64 --,
+    or a flat device tensor plus `sizes` int [B, 3]); types: a subset of the four names.  -> (rows, names, sizes): rows float64
+    [T, W] on the device, W the voxels of the batch, one row per requested type in the order Square, SquareRoot, Logarithm,
+    Exponential -- every row is itself a flat batch tensor that roi_features_batch takes as `images`; names: the strings the
+    single functions yield ("square", "squareroot", "logarithm", "exponential"), one per row; sizes int32 [B, 3].  out: a
+    preallocated float64 [T, W] tensor (rows contiguous, row stride >= W) to fill instead.
+    Native: every box whatever its size.  A box that is all zeros (the formulas divide by zero) or, in a float batch, holds a NaN
+    or an infinity is filled from the single functions instead, so its NaN / inf are exactly theirs; last_batch_route() says
+    "batch", "mixed" or "looped".  Argument errors (an unknown type, sizes that do not describe the buffer, a bad `out`) are
+    raised before any device work."""
+    bits, kept = _intensity_bits(types)
+    W = _flat_voxels(images, sizes, "intensity_batch")
+    _check_out(out, torch.float64, (len(kept), W), "intensity_batch")
+    rois = _image_batch(images, sizes)
+    rows, _, _ = _intensity(rois, bits, (1.0, 1.0, 1.0), False, out, None)
+    return rows, tuple(t.lower() for t in kept), rois.sizes
+
+
+def gradient_batch(images, sizes=None, spacing=(1.0, 1.0, 1.0), gradientUseSpacing=True, out=None):
+    """The Gradient magnitude images of B small boxes in ONE launch: per box what filters.getGradientImage computes on the box
+    alone, bit for bit -- per axis z, y, x of extent above 1 the central difference 0.5 (x[i + 1] - x[i - 1]), divided by the
+    spacing unless gradientUseSpacing is false, squared and summed in float64, the root rounded once to float32.  The gradient
+    replicates the BOX's OWN edge (a voxel on a face of the box sees itself beyond it), not the scan the box was cut from: the
+    values are those of `execute` on the box, the reference's with preCrop.  images: as wavelet_batch takes them; spacing: (z, y,
+    x), one triple or [B, 3].  -> (image float32 [W] on the device -- a flat batch tensor that roi_features_batch takes as
+    `images` --, "gradient", sizes int32 [B, 3]).  out: a preallocated float32 [W] tensor to fill instead.
+    Native: every box whatever its size, an all-zero box included (its image is zeros).  A float box that holds a NaN or an
+    infinity is filled from the single function instead; last_batch_route() says "batch", "mixed" or "looped".  Argument errors
+    are raised before any device work."""
+    W = _flat_voxels(images, sizes, "gradient_batch")
+    _check_out(out, torch.float32, (W,), "gradient_batch")
+    rois = _image_batch(images, sizes)
+    _, image, _ = _intensity(rois, _GRADIENT_BIT, spacing, bool(gradientUseSpacing), None, out)
+    return image, "gradient", rois.sizes
+
+
 def _tight_boxes(rois):
     """The box the feature classes of the reference see -- computeFeatures crops every derived image to the ROI's bounding box
     (featureextractor.py:560-604), here cropToTumorMask(padDistance=0)'s box: the bounding box of the mask with its x extent
@@ -1102,12 +1253,53 @@ def roi_features_batch_derived(images, masks, sizes=None, imageTypes=None, class
     return _roi_features_images(images, masks, sizes, imageTypes, classes, settings)
 
 
-def _roi_features_images(images, masks, sizes, imageTypes, classes, settings):
-    """the image types have been checked"""
+_ALL_TYPES = _DERIVED_TYPES + INTENSITY_TYPES + ("Gradient",)       # what roi_features_batch_types takes: every image type
+
+
+def roi_features_batch_types(images, masks, sizes=None, imageTypes=None, classes=ROI_FEATURE_CLASSES, **settings):
+    """roi_features_batch_derived with the remaining five image types of the extractor: "Square", "SquareRoot", "Logarithm",
+    "Exponential" and "Gradient" -- ONE prad_batch_intensity_dev call (two launches) for all of them that are enabled, then one
+    feature call per image.  As with the LoG the images are those of the box ALONE, the reference's with preCrop: the
+    maximum |x| the four transforms scale with is that of the box as handed over, not of the scan it was cut from, and the
+    gradient replicates the box's own edge -- the values of a ROI depend on the box it is handed over in.  `spacing` (z, y, x;
+    one triple or [B, 3], the argument the planar route reads) and `gradientUseSpacing` (default True) come
+    from the settings; the latter is read here and handed to no feature call.  The images go in the reference's order, that
+    of imageTypes' keys, under the reference's image names ("square", "squareroot", "logarithm", "exponential", "gradient").  A ROI
+    whose box is all zeros or holds a value that is not finite gets the single route's images (intensity_batch).  Any name
+    that is no image type: NotImplementedError.  -> as roi_features_batch_images."""
+    imageTypes = {"Original": {}} if imageTypes is None else dict(imageTypes)
+    for t in imageTypes:
+        if t not in _ALL_TYPES:
+            raise NotImplementedError("roi_features_batch_types: %r is not an image type (%s)" % (t, ", ".join(_ALL_TYPES)))
+    return _roi_features_images(images, masks, sizes, imageTypes, classes, settings, own=("gradientUseSpacing",))
+
+
+def _roi_features_images(images, masks, sizes, imageTypes, classes, settings, own=()):
+    """the image types have been checked; own: settings the image types read that no feature call takes"""
     if not imageTypes:
         raise ValueError("roi_features_batch_images: no image type")
     rois = _roi_batch(images, masks, sizes, raw=True)
     tables, routes = {}, []
+    made = {}
+
+    def transformed():
+        """the images of every enabled type of the five, from one call"""
+        if not made:
+            bits, merged = 0, dict(settings)
+            for t, custom in imageTypes.items():
+                if t in INTENSITY_TYPES:
+                    bits |= 1 << INTENSITY_TYPES.index(t)
+                elif t == "Gradient":
+                    bits |= _GRADIENT_BIT
+                    merged.update(custom or {})
+            rows, grad, _ = _intensity(rois, bits, merged.get("spacing", (1.0, 1.0, 1.0)), merged.get("gradientUseSpacing", True),
+                                       None, None)
+            routes.append(last_batch_route())
+            kept = [t for k, t in enumerate(INTENSITY_TYPES) if bits >> k & 1]
+            made.update({t: rows[i] for i, t in enumerate(kept)})
+            made["Gradient"] = grad
+        return made
+
     status = np.ones(rois.B, dtype=np.int64)
     pick, tight_sizes = _tight_boxes(rois)
     tight_mask = rois.mask[pick]
@@ -1127,6 +1319,11 @@ def _roi_features_images(images, masks, sizes, imageTypes, classes, settings):
     for t, custom in imageTypes.items():
         kw = dict(settings)
         kw.update(custom or {})
+        for k in own:
+            kw.pop(k, None)
+        if t in INTENSITY_TYPES or t == "Gradient":
+            features(t.lower(), transformed()[t], kw)
+            continue
         if t == "Original":
             features("original", rois.data, kw)
             continue
