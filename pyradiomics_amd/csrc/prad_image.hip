@@ -130,6 +130,9 @@ int prad_image_enqueue_dev(const int32_t *levels, const uint8_t *mask, const voi
   void *blk = nullptr;
   PRAD_TRY(c.arena_alloc(sizeof(double) * std::max<size_t>(off, 8), &blk));
   double *res = (double *)blk;
+  // the arena is a ring: once it has wrapped, a block holds the values of an image long collected.  Parts that stay unwritten
+  // -- a class the device route declines below, the padding between parts -- read as zeros, as in a fresh arena
+  memset(blk, 0, sizeof(double) * std::max<size_t>(off, 8));
   *results = res;
   auto at = [&](int k) { return res + layout[k]; };
   // ONE byte-packed copy of the volume for the neighbourhood pass and the GLSZM (each of them packed for itself until round 6),

@@ -1383,7 +1383,8 @@ def _interpolator_codes(interpolator, B):
     return np.array([INTERPOLATOR_CODES[str(i)] for i in items], dtype=np.intc).reshape(B)
 
 
-def batch_resample_plan(sizes, lo, hi, spacing, resampledPixelSpacing, padDistance=5, interpolator=3) -> ResamplePlan:
+def batch_resample_plan(sizes, lo, hi, spacing, resampledPixelSpacing, padDistance=5, interpolator=3,
+                        alignCrop=True) -> ResamplePlan:
     """The grid imageoperations.resampleImage would resample every box onto if the box were the whole image: its expressions in
     float64, elementwise over [B, 3] (pure numpy, needs no device).  sizes int [B, 3]; lo / hi int [B, 3]: the inclusive
     (z, y, x) bounds of the masks (mask_boxes_batch; hi < lo marks an empty mask); spacing (z, y, x), one triple or [B, 3];
@@ -1391,8 +1392,10 @@ def batch_resample_plan(sizes, lo, hi, spacing, resampledPixelSpacing, padDistan
     which the bounding box is one voxel thick; interpolator: a name or code resampleImage accepts, or [B] of them.
     Where the spacing does not change (np.allclose, as in the reference) the ROI is a plain crop to cropToTumorMask's device
     box -- the bounding box with its x extent grown to a multiple of four inside the box, imageoperations.alignedBox,
-    padDistance 0 -- expressed as nearest with step 1 and an integer start, so the kernel copies bits.  An empty mask keeps its
-    whole box the same way and gets status RESAMPLE_EMPTY.  -> ResamplePlan."""
+    padDistance 0 -- expressed as nearest with step 1 and an integer start, so the kernel copies bits.  alignCrop=False cuts the
+    bounding box itself, the extent resampleImage's own crop has: what a filter applied to the crop must see
+    (roi_features_batch_resampled).  An empty mask keeps its whole box the same way and gets status RESAMPLE_EMPTY.
+    -> ResamplePlan."""
     sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 3)
     B = int(sizes.shape[0])
     lo, hi = np.asarray(lo, dtype=np.int64).reshape(-1, 3), np.asarray(hi, dtype=np.int64).reshape(-1, 3)
@@ -1432,7 +1435,7 @@ def batch_resample_plan(sizes, lo, hi, spacing, resampledPixelSpacing, padDistan
     step = new / old
     # the plain crops: alignedBox over the batch (every ROI with the x extent of its own box)
     c_lo, c_hi = lo_z.copy(), hi_z.copy()
-    need = (-(c_hi[:, 2] - c_lo[:, 2] + 1)) % 4
+    need = (-(c_hi[:, 2] - c_lo[:, 2] + 1)) % 4 if alignCrop else np.zeros(B, dtype=np.int64)
     grow = np.minimum(need, sizes[:, 2] - 1 - c_hi[:, 2])
     c_hi[:, 2] += grow
     c_lo[:, 2] -= np.minimum(need - grow, c_lo[:, 2])
@@ -1554,7 +1557,7 @@ def resample_boxes_batch(images, sizes, start, step, newsize, interpolator=3, ma
 
 
 def resample_batch(images, masks, sizes=None, spacing=(1.0, 1.0, 1.0), resampledPixelSpacing=None, interpolator="sitkBSpline",
-                   padDistance=5):
+                   padDistance=5, alignCrop=True):
     """imageoperations.resampleImage on each of B boxes as if the box were the whole image -- what
     RadiomicsFeatureExtractor.execute does when it is handed the box as its image --, bit for bit, in THREE launches and one
     read-back whatever B is: mask_boxes_batch (the bounding boxes, the only read-back), batch_resample_plan (host arithmetic),
@@ -1565,7 +1568,8 @@ def resample_batch(images, masks, sizes=None, spacing=(1.0, 1.0, 1.0), resampled
     -> (images, masks, sizes int32 [B, 3], spacing float64 [B, 3] (z, y, x), origin_shift float64 [B, 3] (x, y, z): what to add
     to the box's origin along its axes, status int64 [B]): flat batch tensors on the new grids that every *_batch function
     takes as they are.  A ROI whose spacing does not change is cropped (batch_resample_plan), one with an empty mask keeps its
-    box and has status RESAMPLE_EMPTY (resampleImage raises there); the others have status 0.
+    box and has status RESAMPLE_EMPTY (resampleImage raises there); the others have status 0.  alignCrop=False: a cropped ROI
+    keeps the bounding box's own x extent, as resampleImage's crop does, instead of one grown to a multiple of four.
     The resampled values are those of the box ALONE: the B-spline prefilter has unbounded support, so -- like the LoG of
     roi_features_batch_derived -- they are not those of the resampled scan the box was cut from, however wide its margin.
     Boxes above batch_resample_max_vox() voxels go through engine.resample; last_batch_route() says "batch", "mixed" or
@@ -1575,7 +1579,7 @@ def resample_batch(images, masks, sizes=None, spacing=(1.0, 1.0, 1.0), resampled
     rois = _roi_batch(images, masks, sizes, raw=True)
     _interpolator_codes(interpolator, rois.B)                    # (raises before anything is launched)
     lo, hi, _ = _mask_boxes(rois)
-    plan = batch_resample_plan(rois.sizes, lo, hi, spacing, resampledPixelSpacing, padDistance, interpolator)
+    plan = batch_resample_plan(rois.sizes, lo, hi, spacing, resampledPixelSpacing, padDistance, interpolator, alignCrop)
     out, out_masks, _ = _resample_boxes(rois, plan.start, plan.step, plan.newsize, plan.interpolator, None, None)
     return out, out_masks, plan.newsize, plan.spacing, plan.origin_shift, plan.status
 
@@ -1587,12 +1591,13 @@ def roi_features_batch_resampled(images, masks, sizes=None, spacing=(1.0, 1.0, 1
     boxes with their own spacing under a parameter file that sets resampledPixelSpacing -- per ROI what
     RadiomicsFeatureExtractor.execute(box, mask) computes with those settings and no preCrop.  The new spacing of every ROI goes
     on as `spacing` (LoG, weightingNorm) and its product as voxelVolume.  As for the LoG, the values are those of the box ALONE
-    (resample_batch).  A ROI whose mask is empty -- before or after resampling -- has status 0 and NaN rows (the extractor raises
-    there).  imageTypes / classes / **settings / -> : as roi_features_batch_derived; last_batch_route() joins all calls."""
+    (resample_batch).  A ROI whose spacing does not change is cut to its bounding box as resampleImage cuts it (alignCrop=False):
+    a filter sees the crop's own borders, and on a crop one to three columns wider the LoG of every ROI voxel differs.  A ROI
+    whose mask is empty -- before or after resampling -- has status 0 and NaN rows (the extractor raises there).  imageTypes / classes / **settings / -> : as roi_features_batch_derived; last_batch_route() joins all calls."""
     if "voxelVolume" in settings:
         raise ValueError("roi_features_batch_resampled works out voxelVolume itself")
     out, out_masks, newsize, new_spacing, _, _ = resample_batch(images, masks, sizes, spacing, resampledPixelSpacing, interpolator,
-                                                                padDistance)
+                                                                padDistance, alignCrop=False)
     route = last_batch_route()
     tables, status = roi_features_batch_derived(out, out_masks, newsize, imageTypes, classes, spacing=new_spacing,
                                                 voxelVolume=new_spacing[:, 2] * new_spacing[:, 1] * new_spacing[:, 0],
