@@ -926,6 +926,46 @@ int prad_batch_resample_dev(const void *in, int dtype, const uint8_t *mask, cons
                             const double *start, const double *step, const int *newsize, const int *interp,
                             const long long *out_off, void *out, uint8_t *out_mask, int *verdict, void *stream);
 
+/* ---- resegmentation on the device (radiomics/imageoperations.py:533-640 resegmentMask; csrc/kernels_resegment.h) ------------
+ * The ROI is restricted to the voxels x with t0' <= x (one threshold) or t0' <= x <= t1' (two), [t0, t1] = sorted(range):
+ * mode 0 absolute t' = t; 1 relative t' = top * t, top = the ROI's maximum; 2 sigma t' = mu + sd * t, mu the ROI's mean and sd
+ * its population standard deviation.  The products are NOT sorted again: a negative maximum gives a descending pair, which keeps
+ * nothing.  The arithmetic is numpy's on the host arrays for thresholds given as Python numbers: int16 / int32 / float64 images
+ * are compared in float64; float32 images in float32 -- the bound is rounded to float32 first, and a relative bound is ONE
+ * float32 product of the maximum and the rounded number.  The sum of an integer image is an exact 64-bit integer and its mean
+ * one float64 division; every floating-point sum has one fixed order (no floating-point atomics; counts and boxes use integer
+ * atomics), so the thresholds depend on the data alone and two calls give the same bits.
+ * prad_resegment_dev: image (DEVICE; dtype 0 float32, 1 float64, 2 int32, 3 int16) and labelmap (DEVICE; label_dtype 2 int32,
+ *   3 int16, 4 uint8, the codes of prad_label_census_dev) are C-contiguous arrays [size[0]]..[size[Nd-1]], Nd = 1..3; size and
+ *   the nrange (1 or 2) values of range are HOST arrays.  out_mask (DEVICE, the label map's dtype and shape): `label` in the kept
+ *   ROI, 0 everywhere else -- voxels of other labels included; every element is written.  HOST outputs: counts int64 [2] = ROI
+ *   voxels on entry and kept; box int [6] = lo z / y / x, hi z / y / x of the kept ROI, inclusive (leading axes of an array with
+ *   Nd < 3 have extent 1; nothing kept: lo = the sizes, hi = -1); thr float64 [2] = the thresholds (thr[1] = +inf with one).
+ *   At most THREE launches -- absolute: initialisation and mask; relative: maximum and mask; sigma: count and sum, squared
+ *   deviations about the mean (as np.std is defined), mask -- and ONE read-back of 64 bytes on `stream`, which is synchronised.
+ *   Work is divided by voxels over a grid that follows from the voxel count alone; 64-bit indices.  Kernel family "resegment"
+ *   (prad_last_kernel_ms), prad_last_path "resegment", prad_last_variant "resegment-absolute" / "-relative" / "-sigma".
+ *   PRAD_E_UNSUPPORTED: sigma mode on a float32 image (numpy accumulates its mean in float32; nothing is launched); a NaN or an
+ *   infinity inside the ROI (found by the launches: out_mask is then not valid) -- the host code serves both.  PRAD_E_ARG, before
+ *   anything is launched: a NULL pointer, a dtype or mode outside the lists, nrange outside [1, 2], a NaN in range, Nd outside
+ *   [1, 3], a size < 1.
+ * prad_batch_resegment_dev: the same for B boxes in the batch layout of prad_batch_firstorder_dev (image in its own dtype, uint8
+ *   mask, non-zero = ROI; HOST sizes [B][3] / off), one mode and range for all of them, in ONE launch -- a workgroup per ROI walks
+ *   its box once per pass -- and one read-back.  out_mask DEVICE uint8, the batch layout: 1 in the kept ROI, 0 elsewhere.  HOST
+ *   outputs: boxes int [B][7] in the layout of prad_batch_mask_boxes_dev (box and count of the KEPT ROI), thr float64 [B][2],
+ *   verdict int [B]: 0 fine; 1 the ROI is empty on entry; 2 a non-finite value inside the ROI; 3 at most one voxel kept (boxes
+ *   still holds the count); 8 not served here -- a box above prad_batch_max_vox() voxels (the cap only keeps one workgroup's walk
+ *   short: the kernel keeps no copy of the box) or sigma mode on float32 -- the slice of out_mask is not touched.  Verdicts 1 and 2
+ *   write an all-zero mask.  A ROI's row depends on its values alone, not on its place in the batch or on the other ROIs.  Kernel
+ *   family "batch_resegment", prad_last_path "batch", prad_last_variant "batch-resegment".  B = 0 is a valid call that launches
+ *   nothing.  PRAD_E_ARG as above, and for B < 0, a negative offset. */
+int prad_resegment_dev(const void *image, int dtype, const void *labelmap, int label_dtype, const int *size, int Nd, int label,
+                       int mode, const double *range, int nrange, void *out_mask, long long *counts, int *box, double *thr,
+                       void *stream);
+int prad_batch_resegment_dev(const void *image, int dtype, const uint8_t *mask, const int *sizes, const long long *off, int B,
+                             int mode, const double *range, int nrange, uint8_t *out_mask, int *boxes, double *thr, int *verdict,
+                             void *stream);
+
 /* ---- filter stack in front of the matrices (radiomics/imageoperations.py:756-970) ---------------------------
  * The arithmetic of both filters lives in third-party wheels (PyWavelets, SimpleITK/ITK) that are not part of
  * the reference tree; these entry points implement their published algorithms (see oracle/filters_oracle.py):

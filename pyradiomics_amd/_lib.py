@@ -167,6 +167,10 @@ SYMBOLS = {
     "prad_batch_mask_boxes_dev": (C.c_int, [_vp, _ip, C.POINTER(C.c_longlong), C.c_int, _ip, _vp]),
     "prad_batch_resample_dev": (C.c_int, [_vp, C.c_int, _vp, _ip, C.POINTER(C.c_longlong), C.c_int, _vp, _vp, _ip, _ip,
                                           C.POINTER(C.c_longlong), _vp, _vp, _ip, _vp]),
+    "prad_resegment_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int,
+                                     _vp, C.POINTER(C.c_longlong), _ip, C.POINTER(C.c_double), _vp]),
+    "prad_batch_resegment_dev": (C.c_int, [_vp, C.c_int, _vp, _ip, C.POINTER(C.c_longlong), C.c_int, C.c_int,
+                                           C.POINTER(C.c_double), C.c_int, _vp, _ip, C.POINTER(C.c_double), _ip, _vp]),
     "prad_swt_level1":(C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp]),
     "prad_swt_level1_dev": (C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp, _vp]),
     "prad_swt_level1_any_dev": (C.c_int, [_vp, C.c_int, _ip, C.c_int, _vp, _vp, C.c_int, _ip, C.c_int, _vp, _vp]),

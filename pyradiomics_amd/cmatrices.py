@@ -846,6 +846,18 @@ def calculate_mask_boxes_batch(masks):
     return _engine().mask_boxes_batch(upload()[1], sizes)
 
 
+def calculate_resegment_batch(images, masks, resegmentRange=None, resegmentMode="absolute"):
+    """resegmentMask on each of B small 3-D boxes (lists of host arrays: raw intensities and masks, non-zero = ROI): one upload,
+    engine.resegment_batch -- one launch for all boxes inside its native domain -- and one download.  -> (masks: [B uint8 numpy
+    arrays in the boxes' shapes, 1 in the kept ROI], boxes int64 [B, 7]: lo z / y / x, hi z / y / x and count of the kept ROI,
+    thresholds float64 [B, 2], status int64 [B]: 0 fine, 1 empty on entry, 3 at most one voxel kept).  Needs a device
+    (RuntimeError without one); last_batch_route() tells which route ran."""
+    _engine()._resegment_args(resegmentRange, resegmentMode)      # (resegmentMask's ValueErrors, before a device is asked)
+    _, _, sizes, upload = _host_roi_batch(images, masks, "resegmentation", raw=True)
+    out, boxes, thr, status = _engine().resegment_batch(*upload(), sizes, resegmentRange, resegmentMode)
+    return _host_boxes(out.cpu().numpy(), sizes), boxes, thr, status
+
+
 def calculate_resample_batch(images, masks, spacing=(1.0, 1.0, 1.0), resampledPixelSpacing=None, interpolator="sitkBSpline",
                              padDistance=5):
     """resampleImage on each of B small 3-D boxes as if the box were the whole image (lists of host arrays: raw intensities and

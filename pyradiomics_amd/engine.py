@@ -558,6 +558,89 @@ def label_census(mask: torch.Tensor, max_label=None):
     return labels, t[labels, 0].copy(), t[labels, 1:1 + nd].copy(), t[labels, 1 + nd:].copy()
 
 
+RESEGMENT_MODES = {"absolute": 0, "relative": 1, "sigma": 2}
+
+
+def _resegment_args(resegmentRange, resegmentMode):
+    """the argument checks of imageoperations.resegmentMask, with its texts: -> (mode code, sorted range); no device is asked"""
+    if resegmentRange is None:
+        raise ValueError("resegmentRange is None.")
+    if len(resegmentRange) == 0 or len(resegmentRange) > 2:
+        raise ValueError("Length %d is not allowed for resegmentRange" % len(resegmentRange))
+    if resegmentMode not in RESEGMENT_MODES:
+        raise ValueError("Resegment mode %s not recognized." % resegmentMode)
+    return RESEGMENT_MODES[resegmentMode], sorted(resegmentRange)
+
+
+def _resegment_numbers(rng, mode: int, integer_image: bool) -> np.ndarray:
+    """the thresholds as float64 where the kernels' arithmetic is numpy's for them -- Python numbers (a parameter file's) and
+    float64 scalars -- else NotImplementedError: the caller takes the host code.  A Python integer beyond +-1 times an integer
+    image's maximum is a product in the IMAGE's type on the host (it may wrap): not reproduced here."""
+    for t in rng:
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, float, np.integer, np.float64)):
+            raise NotImplementedError("resegment: a threshold of type %s" % type(t).__name__)
+        if isinstance(t, (int, np.integer)):
+            if abs(int(t)) > 2 ** 53 or (mode == 1 and integer_image and abs(int(t)) > 1) or \
+                    (isinstance(t, np.integer) and mode != 0):
+                raise NotImplementedError("resegment: integer threshold %r" % (t,))
+        elif t != t:
+            raise NotImplementedError("resegment: a NaN threshold")
+    return np.array([float(t) for t in rng], dtype=np.float64)
+
+
+def resegment(image: torch.Tensor, labelmap: torch.Tensor, label, resegmentRange, resegmentMode: str = "absolute"):
+    """imageoperations.resegmentMask on the device (prad_resegment_dev; at most three launches, one read-back of 64 bytes):
+    -> (mask tensor in the label map's element type holding `label` in the kept ROI and 0 elsewhere, kept voxel count, lo, hi
+    -- int64 [Nd], the inclusive box of the kept ROI in array order -- and the thresholds, float64 [2], [1] = inf for one bound).
+    The mask equals the host function's voxel for voxel.  Raises that function's ValueErrors with its texts: a range of None, of
+    length 0 or above 2, an unknown mode, "Resegmentation excluded too many voxels ..." when at most one voxel is kept.
+    NotImplementedError where the device does not reproduce numpy (the caller then uses the host code): sigma mode on a
+    float32 image, a non-finite value inside the ROI, element types the kernels do not read, thresholds that are not plain
+    numbers."""
+    mode, rng = _resegment_args(resegmentRange, resegmentMode)
+    if not (hasattr(image, "is_cuda") and image.is_cuda and labelmap.is_cuda):
+        raise ValueError("engine.resegment expects CUDA/HIP tensors")
+    if image.dtype not in _DTYPE_CODES:
+        raise NotImplementedError("resegment: image element type %s" % image.dtype)
+    if tuple(image.shape) != tuple(labelmap.shape) or not 1 <= image.dim() <= 3:
+        raise NotImplementedError("resegment: image %s, label map %s" % (tuple(image.shape), tuple(labelmap.shape)))
+    try:
+        if label != int(label) or abs(int(label)) > 2 ** 31 - 1:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise NotImplementedError("resegment: label %r" % (label,))
+    try:
+        lab = _label_tensor(labelmap, "resegment")
+    except ValueError as e:
+        raise NotImplementedError(str(e))
+    t = _resegment_numbers(rng, mode, not image.dtype.is_floating_point)
+    lib = _lib.load()
+    image = image.contiguous()
+    dev = image.device.index if image.device.index is not None else torch.cuda.current_device()
+    _lib.raise_for(lib.prad_set_device(dev), "set_device")
+    nd = image.dim()
+    size = np.array(image.shape, dtype=np.intc)
+    out = torch.empty_like(lab)
+    counts = np.zeros(2, dtype=np.int64)
+    box = np.zeros(6, dtype=np.intc)
+    thr = np.zeros(2, dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    rc = lib.prad_resegment_dev(C.c_void_p(image.data_ptr()), _DTYPE_CODES[image.dtype], C.c_void_p(lab.data_ptr()),
+                                _LABEL_CODES[lab.dtype], _iptr(size), nd, int(label), mode, t.ctypes.data_as(dp), len(t),
+                                C.c_void_p(out.data_ptr()), counts.ctypes.data_as(C.POINTER(C.c_longlong)), _iptr(box),
+                                thr.ctypes.data_as(dp), _stream_ptr())
+    _lib.raise_for(rc, "resegment")
+    before, kept = int(counts[0]), int(counts[1])
+    if before == 0 and mode == 1:      # (np.max of the empty ROI)
+        raise ValueError("zero-size array to reduction operation maximum which has no identity")
+    if kept <= 1:
+        raise ValueError("Resegmentation excluded too many voxels with label %s (retained %d voxel(s))! "
+                         "Cannot extract features" % (label, kept))
+    if labelmap.dtype == torch.bool:
+        out = out.view(torch.bool)
+    return out, kept, box[3 - nd:3].astype(np.int64), box[6 - nd:6].astype(np.int64), thr
+
+
 def workspace_bytes() -> int:
     """device bytes of scratch the library currently holds for this thread"""
     return int(_lib.load().prad_workspace_bytes())
@@ -1148,4 +1231,4 @@ from .roi_batch import (FEATURE_FAMILIES, ROI_FEATURE_CLASSES, batch_digitize_ma
                         RESAMPLE_EMPTY, ResamplePlan, batch_resample_max_vox, batch_resample_plan, mask_boxes_batch,
                         resample_batch, resample_boxes_batch, roi_features_batch_resampled,
                         INTENSITY_NONFINITE, INTENSITY_TYPES, INTENSITY_ZERO, batch_intensity_plan, gradient_batch,
-                        intensity_batch, roi_features_batch_types)
+                        intensity_batch, roi_features_batch_types, RESEGMENT_EMPTY, RESEGMENT_TOO_FEW, resegment_batch)

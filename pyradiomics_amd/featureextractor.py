@@ -248,9 +248,10 @@ class RadiomicsFeatureExtractor:
           - the derived images of the enabled image types (the wavelet's sub-bands, the LoG's sigmas ...) are produced once;
           - each label's crops go through the per-image pipeline of execute() with its one-image look-ahead, and label i + 1's
             first crop is queued before label i's last image is collected (as executeMany overlaps cases).
-        When a setting makes the IMAGE depend on the label -- `resampledPixelSpacing` with an interpolator, `preCrop`,
-        `resegmentRange` -- the derived images cannot be shared: the call still loads and counts once and then runs execute()'s
-        steps label by label (the same results; the filter stack is repeated per label).
+        When a setting makes the IMAGE depend on the label -- `resampledPixelSpacing` with an interpolator, `preCrop` -- the
+        derived images cannot be shared: the call still loads and counts once and then runs execute()'s steps label by label
+        (the same results; the filter stack is repeated per label).  `resegmentRange` changes the MASK alone: the derived images
+        stay shared and every label is resegmented on the device (imageoperations.resegmentMask) in its own steps.
         Peak memory: the shared path keeps every derived image of the call alive until the last label is done (Wavelet: 8
         full-size float64 sub-bands, LoG: one image per sigma -- 1.2 GB for a 256^3 case with Wavelet and one sigma), where
         execute() holds the ones in flight.
@@ -262,6 +263,8 @@ class RadiomicsFeatureExtractor:
         costs one engine.roi_features_batch for all of them.  Results, order, failures and warnings are those of the default
         mode -- texture features, order statistics and counts bit for bit; the summed first-order features come from the
         batched kernel's own summation order -- and every other label takes the per-label steps unchanged.
+        With `resegmentRange` batched=True is not wired to engine.resegment_batch: every label keeps taking the per-label steps
+        (lastLabelsRoute() lists them as "single"), with the shared filter stack and the device resegmentation.
         lastLabelsRoute() tells which label went which way."""
         s = self.settings.copy()
         if labels is not None:
@@ -282,7 +285,7 @@ class RadiomicsFeatureExtractor:
             if not labels:
                 raise ValueError("No labels found in this mask (i.e. nothing is segmented)!")
         per_label_image = ((s.get("resampledPixelSpacing") is not None and s.get("interpolator") is not None)
-                           or s.get("preCrop", False) or s.get("resegmentRange") is not None)
+                           or s.get("preCrop", False))
         shared = None
         if not per_label_image:
             s["label"] = self.settings.get("label", 1)
@@ -290,7 +293,7 @@ class RadiomicsFeatureExtractor:
             shared = (base, list(self._derivedImages(base, mask, s)))
         route = {"batched": [], "single": [], "mixed": []}
         ready, mixed = {}, {}
-        if batched and shared is not None and on_dev:
+        if batched and shared is not None and on_dev and s.get("resegmentRange") is None:
             ready, mixed = self._batchedLabels(image, mask, labels, shared, s)
         prev, cur = None, None
         try:
@@ -540,7 +543,8 @@ class RadiomicsFeatureExtractor:
             image, mask = imageoperations.cropToTumorMask(image, mask, label, padDistance=s.get("padDistance", 5),
                                                           deviceResident=on_dev, alignRows=False)
         if s.get("resegmentRange") is not None:
-            if not np.any(mask.array == label):
+            known = imageoperations.censusLookup(mask, label)      # (a census of this mask answers without a scan)
+            if (known[0] == 0) if known is not None else not np.any(mask.array == label):
                 raise ValueError("Label (%g) not present in mask" % label)
             mask = imageoperations.resegmentMask(image, mask, **s)
             if s.get("additionalInfo", True):

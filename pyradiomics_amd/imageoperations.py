@@ -405,10 +405,44 @@ def normalizeImage(image, **kwargs):
     return img.like(out * float(scale))
 
 
+def _resegmentOnDevice(image, mask, kwargs):
+    """both Images are in HBM already, or the caller works device-resident and the backend has device tensors"""
+    if image.on_device and mask.on_device:
+        return True
+    if not kwargs.get("deviceResident", False):
+        return False
+    from . import backend
+    return bool(getattr(backend.get(), "DEVICE_TENSORS", False))
+
+
+def _resegmentDevice(image, mask, label, rng, mode):
+    """resegmentMask through engine.resegment: the new mask as a device-resident Image whose census (one label: the kept count
+    and box) and ("bbox", label) are filled in, or None where the device declines and the host code must run"""
+    engine = _engine()
+    try:
+        out, kept, lo, hi, _thr = engine.resegment(image.device_tensor(), mask.device_tensor(), label, rng, mode)
+    except NotImplementedError as e:
+        logger.debug("resegmentMask on the host: %s", e)
+        return None
+    new = mask.like(tensor=out)
+    new._derived[("bbox", label)] = (lo.astype(int), hi.astype(int))
+    if int(label) >= 1:
+        new._derived["census"] = {"labels": np.array([int(label)], dtype=np.int64), "counts": np.array([kept], dtype=np.int64),
+                                  "lo": lo[None, :].astype(np.int64), "hi": hi[None, :].astype(np.int64),
+                                  "index": {int(label): 0}}
+        new._derived[("bbox", int(label))] = (lo.astype(int), hi.astype(int))
+    return new
+
+
 def resegmentMask(image, mask, **kwargs):
     """Restricts the ROI to voxels whose intensity lies in `resegmentRange` (1 threshold: >= T; 2: closed range),
     with the thresholds absolute, relative to the ROI maximum, or in standard deviations around the ROI mean
-    (imageoperations.py:533-640).  Returns a new mask Image holding `label` inside the kept ROI."""
+    (imageoperations.py:533-640).  Returns a new mask Image holding `label` inside the kept ROI.
+    When image and mask live on the device (or `deviceResident` is set and the backend works on device tensors) the step runs
+    there (engine.resegment: at most three launches, 64 bytes read back) and the mask Image returned is device-resident, with the
+    kept count and box recorded as a census of its one label, so the next step does not scan it.  The host code below is the
+    oracle: the device mask equals it voxel for voxel.  It also serves what the device does not reproduce: sigma mode on a
+    float32 image (numpy's float32 mean), a NaN or an infinity inside the ROI, element types the kernels do not read."""
     rng = kwargs["resegmentRange"]
     mode = kwargs.get("resegmentMode", "absolute")
     label = kwargs.get("label", 1)
@@ -416,6 +450,10 @@ def resegmentMask(image, mask, **kwargs):
         raise ValueError("resegmentRange is None.")
     if len(rng) == 0 or len(rng) > 2:
         raise ValueError("Length %d is not allowed for resegmentRange" % len(rng))
+    if isinstance(image, Image) and isinstance(mask, Image) and _resegmentOnDevice(image, mask, kwargs):
+        done = _resegmentDevice(image, mask, label, rng, mode)
+        if done is not None:
+            return done
     im = as_array(image)
     roi = as_array(mask) == label
     if mode == "absolute":
@@ -437,6 +475,25 @@ def resegmentMask(image, mask, **kwargs):
     out = np.zeros(roi.shape, dtype="int")
     out[roi] = label
     return mask.like(out) if isinstance(mask, Image) else Image(out)
+
+
+def resegmentArrays(im, roi, rng, mode="absolute"):
+    """resegmentMask's arithmetic on host arrays without its exceptions, for the ROIs engine.resegment_batch hands to the host:
+    im numpy array, roi boolean array of a NON-EMPTY ROI, rng / mode checked by the caller.  -> (kept ROI, boolean; thresholds
+    [t0] or [t0, t1], the scalars numpy compares with)"""
+    roi = np.array(roi, dtype=bool)
+    if mode == "absolute":
+        thr = sorted(rng)
+    elif mode == "relative":
+        top = np.max(im[roi])
+        thr = [top * t for t in sorted(rng)]
+    else:
+        mu, sd = np.mean(im[roi]), np.std(im[roi])
+        thr = [mu + sd * t for t in sorted(rng)]
+    roi[roi] = im[roi] >= thr[0]
+    if len(thr) == 2:
+        roi[roi] = im[roi] <= thr[1]
+    return roi, thr
 
 
 # ---- image / mask geometry (imageoperations.py:177-402: checkMask step 1, _correctMask, _checkROI) -----------------

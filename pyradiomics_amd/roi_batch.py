@@ -715,7 +715,8 @@ def bin_batch(images, masks, sizes=None, stats=None, **binning):
 
 def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, binWidth=None, binCount=None, voxelArrayShift=0,
                        voxelVolume=1.0, distances=(1,), gldm_a=0, symmetricalGLCM=True, mcc=True, extras=False, force2D=False,
-                       force2Ddimension=0, weightingNorm=None, spacing=(1.0, 1.0, 1.0)):
+                       force2Ddimension=0, weightingNorm=None, spacing=(1.0, 1.0, 1.0), resegmentRange=None,
+                       resegmentMode="absolute"):
     """The feature table of B small ROIs from their raw intensity boxes and masks (inputs as firstorder_batch): firstorder_batch
     and bin_batch -- two launches and two read-backs for the whole batch (binWidth, default 25, or binCount) -- then
     texture_features_batch ONCE on the non-empty ROIs, every ROI with the Ng the discretisation gave it.  -> ({class: float64 numpy [B, nfeat]},
@@ -726,16 +727,19 @@ def roi_features_batch(images, masks, sizes=None, classes=ROI_FEATURE_CLASSES, b
     for a ROI with more than 64 levels, as without `mcc`).  extras=True adds two entries the label route of the feature extractor
     needs to report what the feature classes report: "gray_levels" int64 [B], the number of grey levels that occur in the ROI, and
     (with glcm) "glcm_mcc_angles", see texture_features_batch.  force2D / force2Ddimension / weightingNorm / spacing: passed
-    to texture_features_batch; the first-order columns do not depend on them."""
+    to texture_features_batch; the first-order columns do not depend on them.  resegmentRange / resegmentMode: the masks are
+    resegmented first (resegment_batch: one more launch and read-back), per ROI what execute() does with these settings; a ROI
+    that is empty afterwards, or keeps a single voxel, is reported as an empty ROI is."""
     from . import firstorder as _fo
-    rois = _roi_batch(images, masks, sizes, raw=True)
+    spec = _resegment_settings({"resegmentRange": resegmentRange, "resegmentMode": resegmentMode})
+    rois, reseg_route = _resegmented(_roi_batch(images, masks, sizes, raw=True), spec)
     pl = _planar(force2D, force2Ddimension, weightingNorm, spacing)
     classes = tuple(classes)
     if not classes or any(c not in ROI_FEATURE_CLASSES for c in classes):
         raise ValueError("classes must be a non-empty subset of %s" % (ROI_FEATURE_CLASSES,))
     binning = {"binCount": binCount} if binCount is not None else {"binWidth": 25 if binWidth is None else binWidth}
     B = rois.B
-    routes = []
+    routes = [] if reseg_route is None else [reseg_route]
     rows, verdict = _firstorder(rois, voxelArrayShift)
     routes.append(last_batch_route())
     levels, Ng, _, counts = _bin(rois, (rows, verdict), binning)
@@ -1227,7 +1231,10 @@ def roi_features_batch_images(images, masks, sizes=None, imageTypes=None, classe
     force2Ddimension also steer the transform, as in getWaveletImage.  Any other image type: NotImplementedError ("LoG" is
     batched by roi_features_batch_derived, whose results for a box depend on the box it is handed, not on the ROI alone).
     -> ({image name: {class: float64 numpy [B, nfeat]}}, status [B]): image names "original" and those of wavelet_batch, in
-    the reference's order; status[b] is the AND over the images.  last_batch_route() joins the routes of all calls."""
+    the reference's order; status[b] is the AND over the images.  last_batch_route() joins the routes of all calls.
+    resegmentRange / resegmentMode (settings of the call, not of an image type; also taken by roi_features_batch_derived,
+    _types and _resampled -- there after resampling): the masks are resegmented once on the boxes as given (resegment_batch),
+    every image type then uses the new masks; a ROI that fails resegmentation has status 0 and NaN rows."""
     imageTypes = {"Original": {}, "Wavelet": {}} if imageTypes is None else dict(imageTypes)
     for t in imageTypes:
         if t not in _IMAGE_TYPES:
@@ -1278,8 +1285,12 @@ def _roi_features_images(images, masks, sizes, imageTypes, classes, settings, ow
     """the image types have been checked; own: settings the image types read that no feature call takes"""
     if not imageTypes:
         raise ValueError("roi_features_batch_images: no image type")
-    rois = _roi_batch(images, masks, sizes, raw=True)
-    tables, routes = {}, []
+    settings = dict(settings)
+    # resegmentRange / resegmentMode: the masks are resegmented ONCE, on the boxes as given (the Original image, as execute()
+    # orders the steps); every image type then works with the new masks
+    spec = _resegment_settings(settings)
+    rois, reseg_route = _resegmented(_roi_batch(images, masks, sizes, raw=True), spec)
+    tables, routes = {}, ([] if reseg_route is None else [reseg_route])
     made = {}
 
     def transformed():
@@ -1319,7 +1330,7 @@ def _roi_features_images(images, masks, sizes, imageTypes, classes, settings, ow
     for t, custom in imageTypes.items():
         kw = dict(settings)
         kw.update(custom or {})
-        for k in own:
+        for k in tuple(own) + ("resegmentRange", "resegmentMode"):      # (per call, not per image type: done above)
             kw.pop(k, None)
         if t in INTENSITY_TYPES or t == "Gradient":
             features(t.lower(), transformed()[t], kw)
@@ -1604,6 +1615,98 @@ def roi_features_batch_resampled(images, masks, sizes=None, spacing=(1.0, 1.0, 1
                                                 **settings)          # ((x * y) * z, the order of the feature class)
     _cm._set_batch_route(_joined_route([route, last_batch_route()]))
     return tables, status
+
+
+# ---- resegmentation of the boxes, each by its own thresholds (prad_batch_resegment_dev, csrc/kernels_batch_resegment.h) -------
+RESEGMENT_EMPTY = 1        # status of a ROI that is empty on entry
+RESEGMENT_TOO_FEW = 3      # status of a ROI of which at most one voxel is kept (resegmentMask raises there); boxes holds the count
+
+
+def _resegment_host(rois, b, rng, modename, out, boxes, thr):
+    """ROI b through the host arithmetic (imageoperations.resegmentArrays), into the same layout -> its status"""
+    from . import imageoperations
+    im = rois.view(rois.data, b).cpu().numpy()
+    roi = rois.view(rois.mask, b).cpu().numpy() != 0
+    shape = np.array(roi.shape, dtype=np.int64)
+    boxes[b] = np.concatenate([shape, [-1, -1, -1, 0]])
+    thr[b] = 0.0
+    if not roi.any():
+        rois.view(out, b).zero_()
+        return RESEGMENT_EMPTY
+    with np.errstate(all="ignore"):
+        kept, t = imageoperations.resegmentArrays(im, roi, rng, modename)
+    rois.view(out, b).copy_(torch.from_numpy(kept.astype(np.uint8)).to(rois.device))
+    compare = np.float32 if im.dtype == np.float32 else np.float64
+    with np.errstate(all="ignore"):
+        thr[b] = [float(compare(t[0])), float(compare(t[1])) if len(t) == 2 else np.inf]
+    n = int(kept.sum())
+    if n:
+        idx = np.nonzero(kept)
+        boxes[b] = [i.min() for i in idx] + [i.max() for i in idx] + [n]
+    return 0 if n > 1 else RESEGMENT_TOO_FEW
+
+
+def _resegment(rois, resegmentRange, resegmentMode):
+    """-> (flat uint8 masks, boxes int64 [B, 7], thresholds float64 [B, 2], status int64 [B])"""
+    mode, rng = _eng._resegment_args(resegmentRange, resegmentMode)
+    B = rois.B
+    out = torch.empty_like(rois.mask)
+    boxes = np.zeros((max(B, 1), 7), dtype=np.intc)
+    thr = np.zeros((max(B, 1), 2), dtype=np.float64)
+    verdict = np.zeros(max(B, 1), dtype=np.intc)
+    try:
+        t = _eng._resegment_numbers(rng, mode, not rois.data.dtype.is_floating_point)
+    except NotImplementedError:      # thresholds whose host arithmetic the kernel does not reproduce: every ROI on the host
+        verdict[:] = 8
+    else:
+        dp = C.POINTER(C.c_double)
+        rc = rois.lib.prad_batch_resegment_dev(_vp(rois.data), _eng._DTYPE_CODES[rois.data.dtype], _vp(rois.mask), _iptr(rois.sizes),
+                                               _lp(rois.off), B, mode, t.ctypes.data_as(dp), len(t), _vp(out), _iptr(boxes),
+                                               thr.ctypes.data_as(dp), _iptr(verdict), _eng._stream_ptr())
+        _lib.raise_for(rc, "batched resegmentation")
+    boxes, thr, status = boxes[:B].astype(np.int64), thr[:B], verdict[:B].astype(np.int64)
+    rest = np.flatnonzero((status == 2) | (status == 8))
+    for b in rest:
+        status[b] = _resegment_host(rois, b, rng, resegmentMode, out, boxes, thr)
+    _cm._set_batch_route(_route(len(rest), B))
+    return out, boxes, thr, status
+
+
+def resegment_batch(images, masks, sizes=None, resegmentRange=None, resegmentMode="absolute"):
+    """imageoperations.resegmentMask on each of B boxes in ONE launch and one read-back: every ROI is restricted to its voxels
+    inside `resegmentRange` (one threshold: >= t; two: the closed range), taken absolutely, relative to the ROI's own maximum
+    or in standard deviations about the ROI's own mean ("absolute", "relative", "sigma").  images / masks / sizes: as
+    firstorder_batch takes them.  -> (masks: flat uint8 device tensor in the batch layout, 1 in the kept ROI; boxes int64 [B, 7]:
+    lo z / y / x, hi z / y / x and the voxel count of the KEPT ROI, mask_boxes_batch's layout; thresholds float64 [B, 2], [1] =
+    inf with one bound; status int64 [B]: 0 fine, RESEGMENT_EMPTY (1) the ROI was empty on entry, RESEGMENT_TOO_FEW (3) at most
+    one voxel is kept -- a status where resegmentMask raises, not an exception).  Every mask equals the host function's voxel
+    for voxel.  ROIs the launch does not serve -- a non-finite value inside the ROI, a box above batch_max_vox() voxels, sigma
+    mode on float32 boxes (numpy's float32 mean) -- go through the host arithmetic one by one, into the same layout;
+    last_batch_route() says "batch", "mixed" or "looped".  Raises resegmentMask's ValueErrors for a range of None, of length 0 or
+    above 2, and an unknown mode, before any device is asked."""
+    _eng._resegment_args(resegmentRange, resegmentMode)
+    return _resegment(_roi_batch(images, masks, sizes, raw=True), resegmentRange, resegmentMode)
+
+
+def _resegment_settings(settings):
+    """pops resegmentRange / resegmentMode off `settings` and checks them (resegmentMask's ValueErrors, before any device is
+    asked) -> (range, mode), or None without a range"""
+    rng, mode = settings.pop("resegmentRange", None), settings.pop("resegmentMode", "absolute")
+    if rng is None:
+        return None
+    _eng._resegment_args(rng, mode)
+    return rng, mode
+
+
+def _resegmented(rois, spec):
+    """the composite calls' resegmentation step -> (rois with the new masks -- all zeros for a ROI that fails, which the feature
+    calls then report as they report an empty ROI --, the step's route or None)"""
+    if spec is None:
+        return rois, None
+    out, _boxes, _thr, status = _resegment(rois, *spec)
+    for b in np.flatnonzero(status == RESEGMENT_TOO_FEW):
+        rois.view(out, b).zero_()
+    return rois._replace(mask=out), last_batch_route()
 
 
 # ---- the boxes of many labels of one label map in the batch layout (prad_batch_gather_dev, csrc/kernels_batch_gather.h) -------
