@@ -264,6 +264,19 @@ int prad_debug_pipe_plan(const long long *events, int nevents, int *out, int cap
  * tests/test_glszm_route_plan.py checks these records against the rules. */
 int prad_debug_glszm_route(const int *size, int Nd, const int *angles, int Na, int Ng, int irregular, int *out, int cap);
 
+/* ---- debug: the pairs tier of a segment-mode GLDM / NGTDM call (no device call, no launch) -----------------------------
+ * Plans as pairs_neigh does (csrc/prad_neigh_plan.h) for `size` ([Nd]), the HOST angle list `angles` ([Na][Nd]) and Ng levels;
+ * ngtdm: 0 GLDM, 1 NGTDM; knobs: bit 0 PRAD_NO_PAIRS, bit 1 PRAD_NGTDM_NO_BOX (the environment is NOT read); cus <= 0: the
+ * device's count, 256 without a device.  Writes 15 ints to out[0 .. cap), returns their number; -(the number needed) when cap is
+ * too small; 0 for arguments no call accepts.  The record:
+ *   applies  variant      the tier takes the call; index into the prad_last_variant() names "none", then "pairs-global",
+ *                         "pairs-lds64", "pairs-lds32" each plain, "+box32" and "+box64" (1 + 3 * placement + word)
+ *   box narrow  mode      box sums, in 32-bit words; bins 0 global, 1 LDS, 2 LDS as u32 under the grid's voxel cap
+ *   lds threads grid  box_grid     LDS bytes, workgroup size and grid of the bin kernel; grid of the box-axis kernels
+ *   Nz Ny Nx  rz ry rx    the 3-D-embedded extents; the largest |offset| per axis
+ * tests/test_neigh_route_plan.py checks these records against tests/neigh_reference.expected_route and the overflow rule. */
+int prad_debug_neigh_plan(const int *size, int Nd, const int *angles, int Na, int Ng, int ngtdm, int knobs, int cus, int *out, int cap);
+
 /* ---- GLCM: calculate_glcm (cmatrices.c:4-92) ---------------------------------------------------- */
 /* glcm: float64 [Nvox][Ng][Ng][Na] */
 int prad_calculate_glcm(const int32_t *image, const uint8_t *mask, const int *size, int Nd,

@@ -58,6 +58,7 @@ SYMBOLS = {
     "prad_debug_sweep_plan": (C.c_int, [_ip, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_int]),
     "prad_debug_pipe_plan": (C.c_int, [C.POINTER(C.c_longlong), C.c_int, _ip, C.c_int]),
     "prad_debug_glszm_route": (C.c_int, [_ip, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _ip, C.c_int]),
+    "prad_debug_neigh_plan": (C.c_int, [_ip, C.c_int, _ip] + [C.c_int] * 5 + [_ip, C.c_int]),
     "prad_calculate_glcm": (C.c_int, _COMMON + [C.c_int] + _VOX + [_vp]),
     "prad_calculate_glcm_dev": (C.c_int, _COMMON + [C.c_int] + _VOX + [_vp, _vp]),
     "prad_calculate_glrlm": (C.c_int, _COMMON + [C.c_int, C.c_int] + _VOX + [_vp]),

@@ -7,6 +7,8 @@
 //   anything else (voxel mode, Nd > 3, |offset| > 1, large Ng), or a volume whose masked levels fall outside
 //   [1, Ng] (detected on the device by pack_levels)
 //       -> exact generic kernels (kernels_generic.h)                 path "generic"
+// GLDM / NGTDM: byte kernels (kernels_neigh.h, path "neigh"), then the 16-bit tier (kernels_pairs.h, path "pairs": planned by
+// prad_neigh_plan.h, executed by pairs_neigh below), then the exact kernels.
 // There is no host-side compute path: without a HIP device every calculate_* call fails with PRAD_E_HIP.
 #include "prad_runtime.h"
 #include "kernels_generic.h"
@@ -21,6 +23,7 @@
 #include "kernels_voxtex.h"
 #include "prad_sweep_plan.h"
 #include "prad_pipe_plan.h"
+#include "prad_neigh_plan.h"
 #include "prad_internal.h"
 
 #include <algorithm>
@@ -103,6 +106,8 @@ int angle_build(const int *size, const int *distances, int Nd, int Ndist, int f2
   return got == Na ? 0 : 1;
 }
 static_assert(kMaxSweepAngles == PRAD_MAX_SWEEP, "prad_internal.h: kMaxSweepAngles");
+static_assert(kPairMaxAngles == PRAD_PAIR_MAXA && sizeof(PairsNeighPlan().o) == sizeof(PairAngles().o) && kPairLdsBytes == PRAD_PAIR_LDS_WORDS * 4,
+              "prad_neigh_plan.h: the kernels' table sizes");
 }  // namespace prad
 
 namespace {
@@ -665,6 +670,14 @@ int sweep_glcm_glrlm(Call &k, const SweepKnobs &kn, const SweepPlan &p, int Ng, 
   return PRAD_OK;
 }
 
+// the 16-bit level volume of the pairs tier (GLCM / GLRLM below, GLDM / NGTDM in pairs_neigh); flags_d[0]: a level outside 1..Ng
+int pairs_pack(Call &k, int Ng, lev16 *L) {
+  Timed t(*k.c, "pack", k.s);
+  const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((k.g.n + 255) / 256, (long long)cu_count() * 16));
+  hipLaunchKernelGGL(pairs_pack_kernel, dim3(gx), dim3(256), 0, k.s, k.image, k.mask, k.g.n, Ng, L, k.flags_d);
+  return check_launch("pairs_pack_kernel");
+}
+
 // GLCM and/or GLRLM, device pointers
 // The tier between the sweeps and the exact kernels (kernels_pairs.h): segment mode, Nd <= 3, any offset list of up to 128
 // angles, up to 38 400 grey levels.  *used = false when the call is not for it or the pack found a level outside 1..Ng
@@ -702,12 +715,7 @@ int pairs_glcm_glrlm(Call &k, const SweepKnobs &kn, int Ng, int Nr, double *glcm
   }
   PRAD_HIP(hipMemsetAsync(k.flags_d, 0, sizeof(int) * 4, s));
   const int cus = cu_count();
-  {
-    Timed t(c, "pack", s);
-    const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((k.g.n + 255) / 256, (long long)cus * 16));
-    hipLaunchKernelGGL(pairs_pack_kernel, dim3(gx), dim3(256), 0, s, k.image, k.mask, k.g.n, Ng, L, k.flags_d);
-    PRAD_TRY(check_launch("pairs_pack_kernel"));
-  }
+  PRAD_TRY(pairs_pack(k, Ng, L));
   if (glcm) {
     Timed t(c, "pairs", s);
     PRAD_HIP(hipMemsetAsync(gacc, 0, sizeof(u32) * gwords, s));
@@ -852,145 +860,65 @@ int texture_pairs_runs(const int32_t *image, const uint8_t *mask, const int *siz
 }  // namespace prad
 namespace {
 
+// the switches of the GLDM / NGTDM pairs tier, read once per call (DESIGN.md lists them)
+NeighKnobs neigh_knobs_from_env() { return {getenv("PRAD_NO_PAIRS") != nullptr, getenv("PRAD_NGTDM_NO_BOX") != nullptr}; }
+
+template <typename WT, int SH>   // the box sums' word: (u32, 24) narrow, (u64, 40)
+int launch_pairs_box(Call &k, const PairsNeighPlan &p, const lev16 *L, void *b1, void *b2, int Ng, u64 *acc64) {
+  const int *D = p.dims, *flags = k.flags_d;
+  hipLaunchKernelGGL((pairs_box_axis_kernel<WT, SH>), dim3(p.box_grid), dim3(256), 0, k.s, L, (const WT *)nullptr, (WT *)b1, D[0],
+                     D[1], D[2], 2, p.rad[2], flags);
+  hipLaunchKernelGGL((pairs_box_axis_kernel<WT, SH>), dim3(p.box_grid), dim3(256), 0, k.s, (const lev16 *)nullptr, (const WT *)b1,
+                     (WT *)b2, D[0], D[1], D[2], 1, p.rad[1], flags);
+  auto *kern = p.mode == 2 ? &pairs_ngtdm_box_kernel<2, WT, SH>
+             : p.mode == 1 ? &pairs_ngtdm_box_kernel<1, WT, SH> : &pairs_ngtdm_box_kernel<0, WT, SH>;
+  if (p.mode) PRAD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.threads), p.lds, k.s, L, (const WT *)b2, D[0], D[1], D[2], p.rad[0], Ng, k.Na + 1,
+                     acc64, flags);
+  return check_launch("pairs_ngtdm_box_kernel");
+}
+
 // GLDM / NGTDM on the 16-bit level volume (kernels_pairs.h): what kernels_neigh.h does not take -- more than 255 levels, bin
-// tables beyond its LDS budget.  Synchronous calls only; *used = false: not for this tier, or a level outside 1..Ng.
+// tables beyond its LDS budget.  Whether the tier applies, where the bins live and every launch size: plan_pairs_neigh
+// (prad_neigh_plan.h).  Synchronous calls only; *used = false: not for this tier, or a level outside 1..Ng.
 int pairs_neigh(Call &k, bool ngtdm, int Ng, int alpha, double *out, bool *used, bool box_only = false) {
   *used = false;
   Context &c = *k.c;
-  if (k.vm.voxels || k.g.nd > 3 || Ng < 1 || Ng > 65535 || k.g.n >= 0x7fffffffLL || getenv("PRAD_NO_PAIRS")) return PRAD_OK;
-  int dims[3] = {1, 1, 1};
-  for (int d = 0; d < k.g.nd; d++) dims[3 - k.g.nd + d] = k.g.size[d];
-  // NGTDM over a FULL box of neighbours (distances [1], [1, 2], [1, 2, 3] ...; in-plane boxes under force2D): separable box sums
-  // (kernels_pairs.h); decided on the host's angle list -- the path needs the radii only, not the tier's 128-entry angle table
-  int rad[3] = {0, 0, 0};
-  bool box = ngtdm && !getenv("PRAD_NGTDM_NO_BOX");
-  long long cube = 1;
-  if (box) {
-    for (int a = 0; a < k.Na; a++)
-      for (int d = 0; d < k.g.nd; d++) rad[3 - k.g.nd + d] = std::max(rad[3 - k.g.nd + d], std::abs(k.angles_h[a * k.g.nd + d]));
-    cube = (long long)(2 * rad[0] + 1) * (2 * rad[1] + 1) * (2 * rad[2] + 1);
-    box = cube - 1 == k.Na && cube <= 4096 && cube * Ng < (1LL << 40);
-    if (box) {        // cube - 1 distinct non-zero offsets inside the cube are the whole cube
-      std::vector<char> seen((size_t)cube, 0);
-      for (int a = 0; box && a < k.Na; a++) {
-        long long idx = 0;
-        bool zero = true;
-        for (int d = 0; d < 3; d++) {
-          const int o = d < 3 - k.g.nd ? 0 : k.angles_h[a * k.g.nd + (d - (3 - k.g.nd))];
-          zero = zero && o == 0;
-          idx = idx * (2 * rad[d] + 1) + (o + rad[d]);
-        }
-        if (zero || seen[(size_t)idx]) box = false;
-        else seen[(size_t)idx] = 1;
-      }
-    }
-  }
-  if (box_only && !box) return PRAD_OK;
-  if (!box && k.Na > PRAD_PAIR_MAXA) return PRAD_OK;
-  PairAngles A;
-  memset(&A, 0, sizeof(A));
-  A.n = std::min(k.Na, PRAD_PAIR_MAXA);
-  for (int a = 0; a < A.n; a++)
-    for (int d = 0; d < k.g.nd; d++) {
-      const int o = k.angles_h[a * k.g.nd + d];
-      if (o < -127 || o > 127) return PRAD_OK;
-      A.o[a][3 - k.g.nd + d] = (signed char)o;
-    }
-  const size_t nacc = (size_t)Ng * (k.Na + 1);
-  if (nacc * sizeof(u64) > ((size_t)1 << 30)) return PRAD_OK;
+  const PairsNeighInput in = {k.g.nd, k.g.size, k.angles_h, k.Na, Ng, ngtdm, k.vm.voxels != nullptr};
+  const PairsNeighPlan p = plan_pairs_neigh(in, neigh_knobs_from_env(), cu_count());
+  if (!p.applies || (box_only && !p.box)) return PRAD_OK;
+  const size_t bytes = (size_t)Ng * (k.Na + 1) * (ngtdm ? sizeof(u64) : sizeof(u32));
   hipStream_t s = k.s;
   lev16 *L = nullptr;
-  u32 *acc32 = nullptr;
-  u64 *acc64 = nullptr;
+  void *acc = nullptr;
   PRAD_TRY(c.get<lev16>("pairs_levels", (size_t)k.g.n + 8, &L));
-  if (ngtdm) PRAD_TRY(c.get<u64>("pairs_ngtdm_acc", nacc, &acc64));
-  else PRAD_TRY(c.get<u32>("pairs_gldm_acc", nacc, &acc32));
+  PRAD_TRY(c.get(ngtdm ? "pairs_ngtdm_acc" : "pairs_gldm_acc", bytes, &acc));
   PRAD_HIP(hipMemsetAsync(k.flags_d, 0, sizeof(int) * 4, s));
-  const int cus = cu_count();
-  {
-    Timed t(c, "pack", s);
-    const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((k.g.n + 255) / 256, (long long)cus * 16));
-    hipLaunchKernelGGL(pairs_pack_kernel, dim3(gx), dim3(256), 0, s, k.image, k.mask, k.g.n, Ng, L, k.flags_d);
-    PRAD_TRY(check_launch("pairs_pack_kernel"));
-  }
+  PRAD_TRY(pairs_pack(k, Ng, L));
   {
     Timed t(c, "pairs", s);
-    if (ngtdm) PRAD_HIP(hipMemsetAsync(acc64, 0, sizeof(u64) * nacc, s));
-    else PRAD_HIP(hipMemsetAsync(acc32, 0, sizeof(u32) * nacc, s));
-    // bins in LDS when they fit 150 KB: GLDM u32; NGTDM u64, or u32 with a grid fine enough that a workgroup's sums
-    // (voxels x angles x Ng at most) stay below 2^32
-    const size_t budget = (size_t)PRAD_PAIR_LDS_WORDS * 4;
-    int mode = 0;
-    size_t lds = 0;
-    if (!ngtdm) {
-      if (nacc * sizeof(u32) <= budget) { mode = 1; lds = nacc * sizeof(u32); }
-    } else if (nacc * sizeof(u64) <= budget) {
-      mode = 1; lds = nacc * sizeof(u64);
-    } else if (nacc * sizeof(u32) <= budget) {
-      mode = 2; lds = nacc * sizeof(u32);
-    }
-    // bins beyond 40 KB: one workgroup per CU, so make it a 16-wave one (4 waves per CU left the neighbour gathers
-    // latency-bound: GLDM at 300 levels x 124 angles took 7.8 ms)
-    const unsigned bt = (mode && lds > 40 * 1024) ? 1024u : 256u;
-    long long want = (long long)cus * (bt == 1024 ? 1 : 16);
-    if (mode == 2) {      // voxels per workgroup <= 2^32 / (Na * Ng) / 2
-      const long long cap = std::max<long long>(1, (1LL << 31) / ((long long)k.Na * Ng));
-      want = std::max(want, (k.g.n + cap - 1) / cap);
-    }
-    const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((k.g.n + bt - 1) / bt, want));
-    // which bin placement (and which box-sum word) serves the call: prad_last_variant()
-    static const char *const kVariant[3][3] = {{"pairs-global", "pairs-global+box32", "pairs-global+box64"},
-                                               {"pairs-lds64", "pairs-lds64+box32", "pairs-lds64+box64"},
-                                               {"pairs-lds32", "pairs-lds32+box32", "pairs-lds32+box64"}};
-    const bool narrow = box && cube <= 127 && cube * Ng < (1LL << 24);      // (ROI voxels << 24 | level sum) fits 32 bits
-    c.last_variant = kVariant[!ngtdm && mode ? 2 : mode][box ? (narrow ? 1 : 2) : 0];   // (the label names the LDS bin width: GLDM's are u32)
-    if (box) {
+    PRAD_HIP(hipMemsetAsync(acc, 0, bytes, s));
+    c.last_variant = pairs_variant_name(p.variant);   // which bin placement (and which box-sum word) serves the call
+    if (p.box) {
       void *b1 = nullptr, *b2 = nullptr;
-      PRAD_TRY(c.get("pairs_box1", (size_t)k.g.n * (narrow ? 4 : 8), &b1));
-      PRAD_TRY(c.get("pairs_box2", (size_t)k.g.n * (narrow ? 4 : 8), &b2));
-      const unsigned ga = (unsigned)std::max<long long>(1, std::min<long long>((k.g.n + 255) / 256, (long long)cus * 32));
-      const int W = k.Na + 1;
-#define PRAD_PB(MODE_, WT_, SH_)                                                                                                \
-  do {                                                                                                                          \
-    hipLaunchKernelGGL((pairs_box_axis_kernel<WT_, SH_>), dim3(ga), dim3(256), 0, s, (const lev16 *)L, (const WT_ *)nullptr,    \
-                       (WT_ *)b1, dims[0], dims[1], dims[2], 2, rad[2], (const int *)k.flags_d);                                \
-    hipLaunchKernelGGL((pairs_box_axis_kernel<WT_, SH_>), dim3(ga), dim3(256), 0, s, (const lev16 *)nullptr, (const WT_ *)b1,   \
-                       (WT_ *)b2, dims[0], dims[1], dims[2], 1, rad[1], (const int *)k.flags_d);                                \
-    if (MODE_) PRAD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pairs_ngtdm_box_kernel<MODE_, WT_, SH_>),           \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                             \
-    hipLaunchKernelGGL((pairs_ngtdm_box_kernel<MODE_, WT_, SH_>), dim3(gx), dim3(bt), lds, s, (const lev16 *)L,                 \
-                       (const WT_ *)b2, dims[0], dims[1], dims[2], rad[0], Ng, W, acc64, (const int *)k.flags_d);               \
-  } while (0)
-      if (narrow) {
-        if (mode == 2) PRAD_PB(2, u32, 24);
-        else if (mode == 1) PRAD_PB(1, u32, 24);
-        else PRAD_PB(0, u32, 24);
-      } else {
-        if (mode == 2) PRAD_PB(2, u64, 40);
-        else if (mode == 1) PRAD_PB(1, u64, 40);
-        else PRAD_PB(0, u64, 40);
-      }
-#undef PRAD_PB
-      PRAD_TRY(check_launch("pairs_ngtdm_box_kernel"));
+      PRAD_TRY(c.get("pairs_box1", (size_t)k.g.n * (p.narrow ? 4 : 8), &b1));
+      PRAD_TRY(c.get("pairs_box2", (size_t)k.g.n * (p.narrow ? 4 : 8), &b2));
+      if (p.narrow) PRAD_TRY((launch_pairs_box<u32, 24>(k, p, L, b1, b2, Ng, (u64 *)acc)));
+      else PRAD_TRY((launch_pairs_box<u64, 40>(k, p, L, b1, b2, Ng, (u64 *)acc)));
     } else {
-#define PRAD_PN(NG_, MODE_)                                                                                                     \
-  do {                                                                                                                          \
-    if (MODE_) PRAD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pairs_neigh_kernel<NG_, MODE_>),                    \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                             \
-    hipLaunchKernelGGL((pairs_neigh_kernel<NG_, MODE_>), dim3(gx), dim3(bt), lds, s, A, L, dims[0], dims[1], dims[2], Ng,       \
-                       alpha, acc32, acc64, k.flags_d);                                                                         \
-  } while (0)
-    if (ngtdm && mode == 2) PRAD_PN(true, 2);
-    else if (ngtdm && mode == 1) PRAD_PN(true, 1);
-    else if (ngtdm) PRAD_PN(true, 0);
-    else if (mode == 1) PRAD_PN(false, 1);
-    else PRAD_PN(false, 0);
-#undef PRAD_PN
-    PRAD_TRY(check_launch("pairs_neigh_kernel"));
+      PairAngles A;
+      A.n = p.na;
+      memcpy(A.o, p.o, sizeof(A.o));
+      auto *kern = ngtdm ? (p.mode == 2 ? &pairs_neigh_kernel<true, 2> : p.mode == 1 ? &pairs_neigh_kernel<true, 1> : &pairs_neigh_kernel<true, 0>)
+                         : (p.mode == 1 ? &pairs_neigh_kernel<false, 1> : &pairs_neigh_kernel<false, 0>);
+      if (p.mode) PRAD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+      hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.threads), p.lds, s, A, (const lev16 *)L, p.dims[0], p.dims[1], p.dims[2], Ng, alpha,
+                         ngtdm ? nullptr : (u32 *)acc, ngtdm ? (u64 *)acc : nullptr, (const int *)k.flags_d);
+      PRAD_TRY(check_launch("pairs_neigh_kernel"));
     }
   }
-  if (ngtdm) PRAD_TRY(neigh_finalize_ngtdm(&c, s, acc64, Ng, k.Na, out));
-  else PRAD_TRY(neigh_finalize_gldm(&c, s, acc32, Ng, k.Na, out));
+  if (ngtdm) PRAD_TRY(neigh_finalize_ngtdm(&c, s, (const u64 *)acc, Ng, k.Na, out));
+  else PRAD_TRY(neigh_finalize_gldm(&c, s, (const u32 *)acc, Ng, k.Na, out));
   PRAD_TRY(read_flags(k));
   *used = k.flags_h[0] == 0;
   if (!*used) {      // irregular level: the exact kernels redo the call on a zeroed output (the finalize kernels wrote zeros and,
@@ -1678,6 +1606,22 @@ int prad_debug_pipe_plan(const long long *events, int nevents, int *out, int cap
   if ((int)r.size() > cap) return -(int)r.size();
   std::copy(r.begin(), r.end(), out);
   return (int)r.size();
+}
+
+// The pairs tier of a segment-mode GLDM / NGTDM call as ints (the record's order: include/pyradiomics_amd.h).  Host only.
+int prad_debug_neigh_plan(const int *size, int Nd, const int *angles, int Na, int Ng, int ngtdm, int knobs, int cus, int *out, int cap) {
+  if (!size || !angles || !out || Nd < 1 || Nd > PRAD_MAX_ND || Na < 1 || Ng < 1 || cap < 1) return 0;
+  for (int d = 0; d < Nd; d++)
+    if (size[d] < 1) return 0;
+  const PairsNeighInput in = {Nd, size, angles, Na, Ng, ngtdm != 0, false};
+  const NeighKnobs kn = {(knobs & 1) != 0, (knobs & 2) != 0};
+  const PairsNeighPlan p = plan_pairs_neigh(in, kn, cus > 0 ? cus : cu_count());
+  const int r[] = {(int)p.applies, p.variant, (int)p.box, (int)p.narrow, p.mode, (int)p.lds, (int)p.threads, (int)p.grid,
+                   (int)p.box_grid, p.dims[0], p.dims[1], p.dims[2], p.rad[0], p.rad[1], p.rad[2]};
+  const int n = (int)(sizeof(r) / sizeof(r[0]));
+  if (n > cap) return -n;
+  std::copy(r, r + n, out);
+  return n;
 }
 
 // ---- GLCM / GLRLM ---------------------------------------------------------------------------

@@ -8,6 +8,12 @@ For every kernel whose mangled name holds one of the fragments: VGPRs, SGPRs, sp
 the flat operations (all / inside a loop = between a label and a later branch back to it), and for every GROUP LOOP
 (an innermost loop with at least 48 ds_add_u32: the plain groups of the walks) its waits: lgkmcnt(0) waits, and the
 vmcnt waits in program order.
+
+    python scripts/asm_counts.py --compare parent.s new.s
+
+Are the kernels of two builds the same instruction text?  Per kernel the body between its entry label and .Lfunc_end, comments
+stripped and the local labels (.LBB<n>_<m>, .Ltmp<n>, .Lfunc_end<n>) renumbered in order of appearance; prints one row per
+kernel name of either side (lines of assembly, verdict) and exits 1 unless both sides hold the same names with identical bodies.
 """
 import re
 import sys
@@ -95,7 +101,33 @@ def report(name, k):
             sum(bool(re.match(r"^\s+s_load_", l)) for l in seg), lg0, sum("v_readlane" in l for l in seg), " ".join(vm)))
 
 
+def canonical(body):
+    names, out = {}, []
+    for l in body:
+        l = l.split(";")[0].rstrip()
+        if l:
+            out.append(re.sub(r"\.L(?:BB\d+_\d+|tmp\d+|func_end\d+)", lambda m: names.setdefault(m.group(0), ".L%d" % len(names)), l))
+    return out
+
+
+def compare(path_a, path_b):
+    a, b = kernels(path_a), kernels(path_b)
+    bad = 0
+    print("| kernel | lines | verdict |\n|---|---|---|")
+    for name in sorted(set(a) | set(b)):
+        if name not in a or name not in b:
+            verdict = "MISSING in the %s build" % ("first" if name not in a else "second")
+        else:
+            verdict = "identical" if canonical(a[name]["body"]) == canonical(b[name]["body"]) else "DIFFERENT"
+        bad += verdict != "identical"
+        print("| `%s` | %d | %s |" % (name, len(canonical((a.get(name) or b[name])["body"])), verdict))
+    print("\n%d kernels in the first build, %d in the second, %d not identical" % (len(a), len(b), bad))
+    return 1 if bad else 0
+
+
 def main():
+    if sys.argv[1] == "--compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
     ks = kernels(sys.argv[1])
     for name in sorted(ks):
         if any(f in name for f in sys.argv[2:]):
