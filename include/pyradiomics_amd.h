@@ -1029,6 +1029,34 @@ int prad_log_dev_f64(const double *in, const int *size, int Nd, const double *sp
 int prad_log_multi_dev_f64(const double *in, const int *size, int Nd, const double *spacing, const double *sigmas,
                            int nsig, int normalize, double *const *outs, void *stream);
 
+/* ---- LBP2D: local binary patterns by plane (csrc/kernels_lbp2d.h, csrc/kernels_batch_lbp2d.h) ----------------------------------
+ * The image type LBP2D of the reference (imageoperations.py:1094-1166 on scikit-image's local_binary_pattern, whose arithmetic
+ * is restated in csrc/kernels_lbp2d.h and DESIGN.md "LBP2D": float64, every product and sum rounded, nothing fused).
+ * prad_lbp2d_dev: ONE launch for the volume `in` (DEVICE, dtype code 0 float32, 1 float64, 2 int32, 3 int16) of extents
+ * size[3] = (nz, ny, nx) -- a 2-D image is (1, ny, nx) with axis 0 --, planes stacked along `axis` (force2Ddimension: 0 rows y
+ * cols x, 1 rows z cols x, 2 rows y cols z).  rp, cp HOST float64 [P]: the row and column offset of every sample, computed by
+ * the caller (round(-R sin(2 pi i / P), 5), round(R cos(2 pi i / P), 5)); halo = ceil(R), and every |rp|, |cp| <= halo.
+ * method: 0 uniform, 1 default, 2 ror.  out (DEVICE, not `in`): the codes in the image's own dtype.  The call only enqueues on
+ * `stream`.  PRAD_E_UNSUPPORTED (nothing launched; the caller takes its host route) for P > 24, halo > 8 or more than 2^31 - 1
+ * tiles; PRAD_E_ARG for an extent below 1, an axis outside 0 .. 2, P < 1, a sample beyond the halo, an unknown method or
+ * dtype, in == out, and default / ror codes of more than 15 samples into an int16 image.
+ * prad_lbp2d_plan (host only, pure, needs no device): the plan the call executes.  tile int [3]: the output voxels (tz, ty, tx)
+ * of a workgroup; grid int64 [4]: the tiles along z, y, x and their product, the workgroups of the launch; *lds_bytes: the
+ * dynamic LDS of a workgroup (at most 40 KiB); *verdict: 0 native, 1 halo outside [0, 8], 2 too many workgroups.
+ * prad_batch_lbp2d_dev: the same images for B boxes ALONE (cells beyond a box's edge read 0.0) in ONE launch, boxes of any size,
+ * in the batch layout of prad_batch_firstorder_dev (sizes HOST int [B][3], off HOST int64 [B], boxes following one another);
+ * out DEVICE float64, box b at out + off[b]: bit for bit what prad_lbp2d_dev writes for the box, widened.  Same statuses.
+ * prad_batch_lbp2d_plan: one tile shape per launch, that of the largest extent per axis; *n_items workgroups; items (may be
+ * NULL; int [*n_items][4], size it with a first call) = per workgroup the ROI and the first output voxel (z0, y0, x0) of its
+ * tile inside the box. */
+int prad_lbp2d_plan(const int *size, int axis, int halo, int *tile, long long *grid, long long *lds_bytes, int *verdict);
+int prad_lbp2d_dev(const void *in, int dtype, const int *size, int axis, const double *rp, const double *cp, int P, int halo,
+                   int method, void *out, void *stream);
+int prad_batch_lbp2d_plan(const int *sizes, int B, int axis, int halo, int *tile, long long *n_items, int *items,
+                          long long *lds_bytes, int *verdict);
+int prad_batch_lbp2d_dev(const void *in, int dtype, const int *sizes, const long long *off, int B, int axis, const double *rp,
+                         const double *cp, int P, int halo, int method, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@ LIB = os.path.join(CSRC, "libpyradiomics_amd.so")
 SOURCES = ["prad_api.hip", "prad_glszm.hip", "prad_binning.hip", "prad_image.hip", "prad_firstorder.hip", "prad_features.hip", "prad_resample.hip", "prad_filters.hip",
            "prad_labels.hip", "prad_batch.hip", "prad_batch_glszm.hip", "prad_batch_features.hip", "prad_batch_firstorder.hip",
            "prad_batch_gather.hip", "prad_batch_merge.hip", "prad_batch_swt.hip", "prad_batch_log.hip",
-           "prad_batch_resample.hip", "prad_batch_intensity.hip", "prad_resegment.hip", "prad_batch_resegment.hip"]
+           "prad_batch_resample.hip", "prad_batch_intensity.hip", "prad_resegment.hip", "prad_batch_resegment.hip",
+           "prad_lbp2d.hip", "prad_batch_lbp2d.hip"]
 
 
 def _headers() -> list:

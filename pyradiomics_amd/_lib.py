@@ -181,6 +181,12 @@ SYMBOLS = {
     "prad_log_f64": (C.c_int, [_vp, _ip, C.c_int, _vp, C.c_double, C.c_int, _vp]),
     "prad_log_dev_f64": (C.c_int, [_vp, _ip, C.c_int, _vp, C.c_double, C.c_int, _vp, _vp]),
     "prad_log_multi_dev_f64": (C.c_int, [_vp, _ip, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "prad_lbp2d_plan": (C.c_int, [_ip, C.c_int, C.c_int, _ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _ip]),
+    "prad_lbp2d_dev": (C.c_int, [_vp, C.c_int, _ip, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "prad_batch_lbp2d_plan": (C.c_int, [_ip, C.c_int, C.c_int, C.c_int, _ip, C.POINTER(C.c_longlong), _ip,
+                                        C.POINTER(C.c_longlong), _ip]),
+    "prad_batch_lbp2d_dev": (C.c_int, [_vp, C.c_int, _ip, C.POINTER(C.c_longlong), C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int,
+                                       C.c_int, _vp, _vp]),
 }
 
 _lib = None

@@ -838,6 +838,35 @@ def calculate_gradient_batch(images, spacing=(1.0, 1.0, 1.0), gradientUseSpacing
     return _host_boxes(image.cpu().numpy(), sizes), name
 
 
+def calculate_lbp2d(array, radius=1, samples=8, method="uniform", force2Ddimension=0):
+    """The LBP2D image of a host array (2-D, or 3-D with the planes stacked along force2Ddimension): one upload, engine.lbp2d --
+    one launch -- and one download.  -> numpy array of the input's shape: 3-D in the dtype the device holds it in (float32,
+    float64, int32, int16; anything else is widened to float64), 2-D as float64.  Needs a device (RuntimeError without one);
+    NotImplementedError beyond the kernel's domain (ceil(radius) <= 8): filters.lbp2d_host computes those."""
+    from . import filters
+    a = np.asarray(array)
+    if a.ndim not in (2, 3):
+        raise ValueError("LBP2D takes 2-D and 3-D images")
+    if a.dtype not in (np.float32, np.float64, np.int32, np.int16):
+        a = a.astype(np.float64)
+    filters.lbp2d_settings(radius, samples, method, a.dtype if a.ndim == 3 else None)      # (before any device work)
+    eng = _engine()
+    return eng.lbp2d(_to_device(a), radius, samples, method, force2Ddimension).cpu().numpy()
+
+
+def calculate_lbp2d_batch(images, lbp2DRadius=1, lbp2DSamples=8, lbp2DMethod="uniform", force2Ddimension=0):
+    """The LBP2D images of B 3-D boxes (a list of host arrays: raw intensities): one upload, engine.lbp2d_batch -- one launch for
+    all boxes -- and one download.  -> ([B float64 numpy arrays in the boxes' shapes], "lbp-2D"); every image is that of the box
+    ALONE (a sample beyond its edge reads 0).  Needs a device (RuntimeError without one); last_batch_route() tells which route
+    ran."""
+    from . import filters
+    filters.lbp2d_settings(lbp2DRadius, lbp2DSamples, lbp2DMethod)
+    ones = [np.ones(np.shape(i), dtype=bool) for i in images]
+    _, _, sizes, upload = _host_roi_batch(images, ones, "LBP2D images", raw=True)
+    image, name, _ = _engine().lbp2d_batch(upload()[0], sizes, lbp2DRadius, lbp2DSamples, lbp2DMethod, force2Ddimension)
+    return _host_boxes(image.cpu().numpy(), sizes), name
+
+
 def calculate_mask_boxes_batch(masks):
     """The bounding boxes of B 3-D masks (a list of host arrays, non-zero = ROI): one upload, engine.mask_boxes_batch -- one
     launch -- and one read-back.  -> (lo int64 [B, 3], hi int64 [B, 3], count int64 [B]), inclusive (z, y, x) bounds; an empty

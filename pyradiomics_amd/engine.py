@@ -1221,6 +1221,73 @@ def log_image(image: torch.Tensor, spacing_xyz, sigma: float, normalize: bool = 
     return out.to(out_type)
 
 
+def lbp2d_native(dtype, radius=1, samples=8) -> bool:
+    """whether the LBP2D kernels take a tensor of `dtype` with these settings (csrc/prad_lbp2d_plan.h): float32, float64, int32
+    or int16, ceil(R) <= 8, P <= 24.  Everything else is filters.lbp2d_host's."""
+    from .filters import LBP2D_MAX_SAMPLES, LBP2D_NATIVE_HALO
+    return dtype in _DTYPE_CODES and 0 < float(radius) <= LBP2D_NATIVE_HALO and 1 <= int(samples) <= LBP2D_MAX_SAMPLES
+
+
+def _lbp2d_table(radius, samples, method, dtype):
+    """the checked settings as the C arguments: (rp, cp, P, halo, method code)"""
+    from . import filters
+    R, P, method = filters.lbp2d_settings(radius, samples, method, dtype)
+    rp, cp = filters.lbp2d_offsets(R, P)
+    return np.ascontiguousarray(rp), np.ascontiguousarray(cp), P, int(np.ceil(R)), filters.LBP2D_METHODS.index(method)
+
+
+def lbp2d_plan(shape, force2Ddimension=0, halo=1):
+    """Host-side plan of the LBP2D launch (prad_lbp2d_plan; pure, needs no device).  shape: (nz, ny, nx) or (ny, nx); halo =
+    ceil(lbp2DRadius).  -> dict: tile (tz, ty, tx) the output voxels of a workgroup, grid (tiles along z, y, x), groups their
+    product, lds the bytes of dynamic LDS, verdict 0 native / 1 halo beyond the domain / 2 too many workgroups."""
+    shape = tuple(int(s) for s in shape)
+    size = np.array((1,) * (3 - len(shape)) + shape, dtype=np.intc)
+    tile, grid = np.zeros(3, dtype=np.intc), np.zeros(4, dtype=np.int64)
+    lds, verdict = C.c_longlong(0), C.c_int(0)
+    rc = _lib.load().prad_lbp2d_plan(_iptr(size), int(force2Ddimension), int(halo), _iptr(tile),
+                                     grid.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(lds), C.byref(verdict))
+    _lib.raise_for(rc, "lbp2d plan")
+    return {"tile": tuple(int(t) for t in tile), "grid": tuple(int(g) for g in grid[:3]), "groups": int(grid[3]),
+            "lds": int(lds.value), "verdict": int(verdict.value)}
+
+
+def lbp2d(tensor: torch.Tensor, radius=1, samples=8, method="uniform", force2Ddimension=0, out=None) -> torch.Tensor:
+    """The LBP2D image of a 3-D device tensor in ONE launch (prad_lbp2d_dev, csrc/kernels_lbp2d.h): the planes
+    tensor.swapaxes(0, force2Ddimension)[idx], codes in the tensor's own dtype (float32, float64, int32, int16), equal to
+    filters.lbp2d_host bit for bit.  A 2-D tensor is one plane (rows y, cols x) and comes back as float64, as in the reference.
+    out: a contiguous tensor of the result's shape, dtype and device to fill instead (not the input).  The call only enqueues
+    on the current stream.  NotImplementedError for `var`, for another dtype and beyond ceil(R) <= 8 (filters.lbp2d_host
+    computes those); ValueError outside 1 <= P <= 24 and where the codes do not fit an int16 image."""
+    if not tensor.is_cuda:
+        raise ValueError("engine.* expects CUDA/HIP tensors; use pyradiomics_amd.cmatrices for numpy input")
+    if tensor.dim() not in (2, 3):
+        raise ValueError("LBP2D takes 2-D and 3-D images")
+    axis = int(force2Ddimension) if tensor.dim() == 3 else 0
+    if not 0 <= axis <= 2:
+        raise ValueError("force2Ddimension must be 0, 1 or 2")
+    if tensor.dtype not in _DTYPE_CODES:
+        raise NotImplementedError("engine.lbp2d takes float32, float64, int32 and int16 tensors, not %s" % (tensor.dtype,))
+    x = tensor.to(torch.float64) if tensor.dim() == 2 else tensor
+    from .roi_batch import _NP_DTYPES
+    rp, cp, P, halo, code = _lbp2d_table(radius, samples, method, _NP_DTYPES[x.dtype])
+    x = x.contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    elif (out.dtype != x.dtype or out.device != x.device or tuple(out.shape) != tuple(x.shape) or not out.is_contiguous()
+          or out.data_ptr() == x.data_ptr()):
+        raise ValueError("out must be a contiguous %s tensor of shape %s on %s, and not the input"
+                         % (x.dtype, list(x.shape), x.device))
+    if x.numel() == 0:
+        return out
+    lib = _lib.load()
+    lib.prad_set_device(x.device.index or 0)
+    size = np.array((1,) * (3 - x.dim()) + tuple(x.shape), dtype=np.intc)
+    rc = lib.prad_lbp2d_dev(C.c_void_p(x.data_ptr()), _DTYPE_CODES[x.dtype], _iptr(size), axis, C.c_void_p(rp.ctypes.data),
+                            C.c_void_p(cp.ctypes.data), P, halo, code, C.c_void_p(out.data_ptr()), _stream_ptr())
+    _lib.raise_for(rc, "lbp2d")
+    return out
+
+
 # ---- many small ROIs in a few launches: the batch route lives in roi_batch.py; its public names are bound here too ----------
 from .roi_batch import (FEATURE_FAMILIES, ROI_FEATURE_CLASSES, batch_digitize_max_edges, batch_features_per_angle,  # noqa: E402,F401
                         batch_firstorder_max_roi, batch_glszm_max_vox, batch_max_vox, bin_batch, firstorder_batch,
@@ -1231,4 +1298,5 @@ from .roi_batch import (FEATURE_FAMILIES, ROI_FEATURE_CLASSES, batch_digitize_ma
                         RESAMPLE_EMPTY, ResamplePlan, batch_resample_max_vox, batch_resample_plan, mask_boxes_batch,
                         resample_batch, resample_boxes_batch, roi_features_batch_resampled,
                         INTENSITY_NONFINITE, INTENSITY_TYPES, INTENSITY_ZERO, batch_intensity_plan, gradient_batch,
-                        intensity_batch, roi_features_batch_types, RESEGMENT_EMPTY, RESEGMENT_TOO_FEW, resegment_batch)
+                        intensity_batch, roi_features_batch_types, RESEGMENT_EMPTY, RESEGMENT_TOO_FEW, resegment_batch,
+                        batch_lbp2d_plan, lbp2d_batch)

@@ -1,12 +1,12 @@
 """`RadiomicsFeatureExtractor`: the orchestration API of the reference's radiomics/featureextractor.py for the
-path this package accelerates -- image types Original / Wavelet / LoG / Square / SquareRoot / Logarithm / Exponential, feature classes firstorder / glcm / glrlm /
-glszm / gldm / ngtdm, segment-based and voxel-based extraction -- without SimpleITK / pykwalify (not installed on the build and
-GPU hosts).  Same constructor forms (parameter file, dict, or keyword settings), the same enable*/disable* methods,
+path this package accelerates -- image types Original / Wavelet / LoG / Square / SquareRoot / Logarithm / Exponential /
+Gradient / LBP2D, feature classes firstorder / glcm / glrlm / glszm / gldm / ngtdm, segment-based and voxel-based extraction --
+without SimpleITK / pykwalify / scikit-image (not installed on the build and GPU hosts).  Same constructor forms (parameter file, dict, or keyword settings), the same enable*/disable* methods,
 the same `execute(image, mask, label=None, voxelBased=False)` returning an OrderedDict keyed
 `<imageType>_<featureClass>_<featureName>` (featureextractor.py:241-396, 560-604).
 
 Not provided (out of scope): the shape classes,
-the remaining image types, parameter-file schema validation.  Enabling them raises/ warns instead of silently
+the image type LBP3D (and LBP2D's method `var`), parameter-file schema validation.  Enabling them raises/ warns instead of silently
 computing something else."""
 from __future__ import annotations
 
@@ -28,7 +28,7 @@ _FEATURE_CLASSES = ("firstorder", "glcm", "gldm", "glrlm", "glszm", "ngtdm")    
 _IMAGE_TYPES = {"Original": filters.getOriginalImage, "Wavelet": filters.getWaveletImage, "LoG": filters.getLoGImage,
                 "Square": filters.getSquareImage, "SquareRoot": filters.getSquareRootImage,
                 "Logarithm": filters.getLogarithmImage, "Exponential": filters.getExponentialImage,
-                "Gradient": filters.getGradientImage}
+                "Gradient": filters.getGradientImage, "LBP2D": filters.getLBP2DImage}
 
 
 _feature_classes = None

@@ -287,6 +287,125 @@ def getGradientImage(inputImage, inputMask, **kwargs):
     yield ref.like(np.sqrt(acc).astype(np.float32)), "gradient", kwargs
 
 
+# ---- LBP2D (imageoperations.py:1094-1166 on skimage.feature.local_binary_pattern) -------------------------------------------
+LBP2D_METHODS = ("uniform", "default", "ror")      # the C `method` code is the index
+LBP2D_MAX_SAMPLES = 24                              # the domain: the codes of `default` stay whole numbers in float32
+LBP2D_NATIVE_HALO = 8                               # ceil(R) the kernels stage (csrc/prad_lbp2d_plan.h); beyond it the host route
+
+
+def lbp2d_offsets(radius, samples):
+    """(rp, cp): the row and column offset of the samples on the circle, float64, rounded to 5 decimals as scikit-image does.
+    Computed here, on the host, once per call: the kernels get them as a table and do no trigonometry."""
+    i = np.arange(int(samples), dtype=np.float64)
+    rp = np.round(-float(radius) * np.sin(2 * np.pi * i / int(samples)), 5)
+    cp = np.round(float(radius) * np.cos(2 * np.pi * i / int(samples)), 5)
+    return rp, cp
+
+
+def lbp2d_settings(radius=1, samples=8, method="uniform", dtype=None):
+    """-> (R float, P int, method) checked.  NotImplementedError for `var` (its NaN for a flat neighbourhood, cast into an integer
+    image, is undefined in the reference and its formula differs between scikit-image releases); ValueError outside the domain
+    (R > 0 finite, 1 <= P <= 24, a known method) and where the codes do not fit an integer image of `dtype` (a numpy dtype) --
+    `default` / `ror` with more than 15 samples on int16; the reference wraps around there: a stated deviation."""
+    if method == "var":
+        raise NotImplementedError("lbp2DMethod 'var' is not provided (undefined on flat neighbourhoods of integer images)")
+    if method not in LBP2D_METHODS:
+        raise ValueError("lbp2DMethod must be one of %s, got %r" % (LBP2D_METHODS, method))
+    R, P = float(radius), int(samples)
+    if P != samples or not 1 <= P <= LBP2D_MAX_SAMPLES:
+        raise ValueError("lbp2DSamples must be an integer in 1 .. %d, got %r" % (LBP2D_MAX_SAMPLES, samples))
+    if not (R > 0 and np.isfinite(R)):
+        raise ValueError("lbp2DRadius must be positive and finite, got %r" % (radius,))
+    if dtype is not None and np.dtype(dtype).kind in "iu":
+        top = P + 1 if method == "uniform" else (1 << P) - 1
+        if top > np.iinfo(dtype).max:
+            raise ValueError("LBP2D codes up to %d (%d samples, %s) do not fit an image of %s" % (top, P, method, np.dtype(dtype)))
+    return R, P, method
+
+
+def lbp2d_host(array, radius=1, samples=8, method="uniform", force2Ddimension=0):
+    """The LBP2D image in numpy: serves deviceResident=False and whatever the device declines.  All planes
+    arr.swapaxes(0, force2Ddimension)[idx] at once over a zero-padded copy: for sample i, y = r + rp[i], x = c + cp[i], the four
+    corners at floor / ceil (outside the plane 0.0), top = (1 - dc) tl + dc tr, bottom = (1 - dc) bl + dc br, t = (1 - dr) top +
+    dr bottom, s_i = t - centre >= 0, every product and sum a ufunc of its own (rounded; numpy fuses nothing).  3-D arrays come
+    back in their own dtype (the reference writes each slice back into the input array), a 2-D array as float64."""
+    a = np.asarray(array)
+    if a.ndim not in (2, 3):
+        raise ValueError("LBP2D takes 2-D and 3-D images")
+    R, P, method = lbp2d_settings(radius, samples, method, a.dtype if a.ndim == 3 else None)
+    axis = int(force2Ddimension) if a.ndim == 3 else 0
+    if not 0 <= axis <= 2:
+        raise ValueError("force2Ddimension must be 0, 1 or 2")
+    planes = (a[None] if a.ndim == 2 else a.swapaxes(0, axis)).astype(np.float64)
+    n, rows, cols = planes.shape
+    h = int(np.ceil(R))
+    padded = np.zeros((n, rows + 2 * h, cols + 2 * h), dtype=np.float64)
+    padded[:, h:h + rows, h:h + cols] = planes
+    rp, cp = lbp2d_offsets(R, P)
+    r, c = np.arange(rows, dtype=np.float64), np.arange(cols, dtype=np.float64)
+    word = np.zeros(planes.shape, dtype=np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for i in range(P):
+            y, x = r + rp[i], c + cp[i]
+            minr, maxr, minc, maxc = np.floor(y), np.ceil(y), np.floor(x), np.ceil(x)
+            dr, dc = (y - minr)[None, :, None], (x - minc)[None, None, :]
+            r0, r1 = (minr.astype(np.int64) + h)[:, None], (maxr.astype(np.int64) + h)[:, None]
+            c0, c1 = (minc.astype(np.int64) + h)[None, :], (maxc.astype(np.int64) + h)[None, :]
+            top = (1.0 - dc) * padded[:, r0, c0] + dc * padded[:, r0, c1]
+            bottom = (1.0 - dc) * padded[:, r1, c0] + dc * padded[:, r1, c1]
+            t = (1.0 - dr) * top + dr * bottom
+            word |= ((t - planes) >= 0).astype(np.int64) << i
+    full = (1 << P) - 1
+    if method == "uniform":
+        ones = np.zeros(word.shape, dtype=np.int64)
+        for i in range(P):
+            ones += (word >> i) & 1
+        flips = (word ^ (word >> 1)) & (full >> 1)
+        changes = np.zeros(word.shape, dtype=np.int64)
+        for i in range(P - 1):
+            changes += (flips >> i) & 1
+        code = np.where(changes <= 2, ones, P + 1)
+    elif method == "default":
+        code = word
+    else:
+        code = word.copy()
+        for k in range(1, P):
+            np.minimum(code, ((word >> k) | (word << (P - k))) & full, out=code)
+    if a.ndim == 2:
+        return code[0].astype(np.float64)
+    return np.ascontiguousarray(code.astype(a.dtype).swapaxes(0, axis))
+
+
+def getLBP2DImage(inputImage, inputMask, **kwargs):
+    """Local binary patterns by plane (imageoperations.py:1094-1166): settings lbp2DRadius [1], lbp2DSamples [8 -- what the
+    reference's code says; its docstring says 9], lbp2DMethod ['uniform'] and force2Ddimension [0], the axis the planes are
+    stacked along; yields the image as "lbp-2D".  Without force2D one warning is logged, as in the reference.  The image does
+    not depend on the mask.  The arithmetic of scikit-image's local_binary_pattern is restated from its published algorithm
+    (lbp2d_host above, csrc/kernels_lbp2d.h on the device; DESIGN.md "LBP2D"): scikit-image is no dependency of this package
+    and parity with one of its wheels is not pinned by a golden vector, as for getGradientImage and ITK.  `var` raises
+    NotImplementedError, codes that do not fit an integer image raise ValueError (lbp2d_settings), both before any device work.
+    By default the image is made on the device (engine.lbp2d: float32, float64, int32 and int16 tensors, ceil(R) <= 8); any
+    other dtype or radius, and deviceResident=False, take the numpy route."""
+    ref = as_image(inputImage)
+    nd = len(ref.shape)
+    if nd not in (2, 3):
+        logger.warning("LBP 2D is only available for 2D or 3D with forced 2D extraction")
+        return
+    radius, samples = kwargs.get("lbp2DRadius", 1), kwargs.get("lbp2DSamples", 8)
+    method = kwargs.get("lbp2DMethod", "uniform")
+    axis = kwargs.get("force2Ddimension", 0) if nd == 3 else 0
+    lbp2d_settings(radius, samples, method)
+    if nd == 3 and not kwargs.get("force2D", False):
+        logger.warning("Calculating Local Binary Pattern in 2D, but extracting features in 3D. Use with caution!")
+    if kwargs.get("deviceResident", True):
+        from . import engine
+        x = ref.device_tensor()
+        if engine.lbp2d_native(x.dtype, radius, samples):
+            yield ref.like(tensor=engine.lbp2d(x, radius, samples, method, axis)), "lbp-2D", kwargs
+            return
+    yield ref.like(lbp2d_host(ref.array, radius, samples, method, axis)), "lbp-2D", kwargs
+
+
 def getOriginalImage(inputImage, inputMask, **kwargs):
     """imageoperations.py:745-753"""
     yield inputImage, "original", kwargs

@@ -1171,6 +1171,75 @@ def gradient_batch(images, sizes=None, spacing=(1.0, 1.0, 1.0), gradientUseSpaci
     return image, "gradient", rois.sizes
 
 
+# ---- LBP2D images of the boxes (prad_batch_lbp2d_dev, csrc/kernels_batch_lbp2d.h) ---------------------------------------------
+def batch_lbp2d_plan(sizes, force2Ddimension=0, halo=1):
+    """Host-side plan of the batched LBP2D launch (prad_batch_lbp2d_plan; pure, needs no device).  sizes: int [B, 3]; halo =
+    ceil(lbp2DRadius).  -> (items int32 [n, 4]: per workgroup the ROI and the first output voxel (z0, y0, x0) of its tile inside
+    the box; tile (tz, ty, tx): the one tile shape of the launch, that of the largest extent per axis; lds: the bytes of dynamic
+    LDS; verdict: 0 native, 1 halo beyond the domain, 2 too many workgroups -- then no items).  The tiles of a box cover its
+    voxels exactly once."""
+    sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.intc).reshape(-1, 3))
+    B = int(sizes.shape[0])
+    lib = _lib.load()
+    tile = np.zeros(3, dtype=np.intc)
+    n, lds, verdict = C.c_longlong(0), C.c_longlong(0), C.c_int(0)
+    args = (_iptr(sizes), B, int(force2Ddimension), int(halo), _iptr(tile), C.byref(n))
+    _lib.raise_for(lib.prad_batch_lbp2d_plan(*args, None, C.byref(lds), C.byref(verdict)), "batch lbp2d plan")
+    items = np.zeros((max(int(n.value), 1), 4), dtype=np.intc)
+    if verdict.value == 0:
+        _lib.raise_for(lib.prad_batch_lbp2d_plan(*args, _iptr(items), C.byref(lds), C.byref(verdict)), "batch lbp2d plan")
+    return (items[:int(n.value) if verdict.value == 0 else 0], tuple(int(t) for t in tile), int(lds.value), int(verdict.value))
+
+
+def _lbp2d(rois, radius, samples, method, axis, out):
+    """the C call, or -- beyond the kernel's domain -- the host route box by box; `out` has been checked but for its device"""
+    from . import filters
+    W = rois.data.numel()
+    axis = int(axis)
+    if not 0 <= axis <= 2:
+        raise ValueError("force2Ddimension must be 0, 1 or 2")
+    rp, cp, P, halo, code = _eng._lbp2d_table(radius, samples, method, None)
+    if out is None:
+        out = torch.empty(W, dtype=torch.float64, device=rois.device)
+    elif out.device != rois.device:
+        raise ValueError("out must live on %s" % (rois.device,))
+    if _eng.lbp2d_native(rois.data.dtype, radius, samples):
+        rc = rois.lib.prad_batch_lbp2d_dev(_vp(rois.data), _eng._DTYPE_CODES[rois.data.dtype], _iptr(rois.sizes), _lp(rois.off),
+                                           rois.B, axis, C.c_void_p(rp.ctypes.data), C.c_void_p(cp.ctypes.data), P, halo, code,
+                                           _vp(out), _eng._stream_ptr())
+        if rc != _lib.PRAD_E_UNSUPPORTED:
+            _lib.raise_for(rc, "batched LBP2D")
+            _cm._set_batch_route(_route(0, rois.B))
+            return out
+    host = rois.data.cpu().numpy()
+    for b in range(rois.B):
+        o, n = int(rois.off[b]), int(rois.nvox[b])
+        box = host[o:o + n].reshape(tuple(rois.sizes[b])).astype(np.float64)
+        out[o:o + n] = torch.from_numpy(filters.lbp2d_host(box, radius, samples, method, axis).reshape(-1)).to(rois.device)
+    _cm._set_batch_route(_route(rois.B, rois.B))
+    return out
+
+
+def lbp2d_batch(images, sizes=None, lbp2DRadius=1, lbp2DSamples=8, lbp2DMethod="uniform", force2Ddimension=0, out=None):
+    """The LBP2D images of B boxes in ONE launch, boxes of any size: per box what filters.getLBP2DImage computes on the box ALONE
+    -- a sample beyond the box's edge reads 0, not the scan the box was cut from: the values are those of `execute` on the box,
+    the reference's with preCrop --, equal to engine.lbp2d on that box bit for bit (the same device function runs both).  images:
+    as wavelet_batch takes them (a list of 3-D device tensors of one dtype -- float32, float64, int32, int16; anything else is
+    widened to float64 --, or a flat device tensor plus `sizes` int [B, 3]).  -> (image float64 [W] on the device, W the voxels
+    of the batch -- a flat batch tensor that roi_features_batch takes as `images` --, "lbp-2D", sizes int32 [B, 3]).  out: a
+    preallocated float64 [W] tensor to fill instead.  Work is divided by output tiles from a host-built item table
+    (batch_lbp2d_plan).  Native: ceil(lbp2DRadius) <= 8; a wider radius fills every box from filters.lbp2d_host
+    (last_batch_route() says "batch" or "looped").  `var` raises NotImplementedError, argument errors are raised before any
+    device work."""
+    W = _flat_voxels(images, sizes, "lbp2d_batch")
+    _check_out(out, torch.float64, (W,), "lbp2d_batch")
+    from . import filters
+    filters.lbp2d_settings(lbp2DRadius, lbp2DSamples, lbp2DMethod)
+    rois = _image_batch(images, sizes)
+    image = _lbp2d(rois, lbp2DRadius, lbp2DSamples, lbp2DMethod, force2Ddimension, out)
+    return image, "lbp-2D", rois.sizes
+
+
 def _tight_boxes(rois):
     """The box the feature classes of the reference see -- computeFeatures crops every derived image to the ROI's bounding box
     (featureextractor.py:560-604), here cropToTumorMask(padDistance=0)'s box: the bounding box of the mask with its x extent
@@ -1260,7 +1329,9 @@ def roi_features_batch_derived(images, masks, sizes=None, imageTypes=None, class
     return _roi_features_images(images, masks, sizes, imageTypes, classes, settings)
 
 
-_ALL_TYPES = _DERIVED_TYPES + INTENSITY_TYPES + ("Gradient",)       # what roi_features_batch_types takes: every image type
+_LBP2D_SETTINGS = ("lbp2DRadius", "lbp2DSamples", "lbp2DMethod")
+# what roi_features_batch_types takes: every image type
+_ALL_TYPES = _DERIVED_TYPES + INTENSITY_TYPES + ("Gradient", "LBP2D")
 
 
 def roi_features_batch_types(images, masks, sizes=None, imageTypes=None, classes=ROI_FEATURE_CLASSES, **settings):
@@ -1273,12 +1344,17 @@ def roi_features_batch_types(images, masks, sizes=None, imageTypes=None, classes
     from the settings; the latter is read here and handed to no feature call.  The images go in the reference's order, that
     of imageTypes' keys, under the reference's image names ("square", "squareroot", "logarithm", "exponential", "gradient").  A ROI
     whose box is all zeros or holds a value that is not finite gets the single route's images (intensity_batch).  Any name
-    that is no image type: NotImplementedError.  -> as roi_features_batch_images."""
+    that is no image type: NotImplementedError.  -> as roi_features_batch_images.
+    "LBP2D" is the ninth type: ONE prad_batch_lbp2d_dev launch for all boxes (lbp2d_batch), image name "lbp-2D".  Its settings
+    lbp2DRadius, lbp2DSamples and lbp2DMethod are read here and handed to no feature call; force2Ddimension, which the feature
+    calls read as well, names the axis the planes are stacked along.  Again the image is that of the box alone: a sample beyond
+    the box's edge reads 0."""
     imageTypes = {"Original": {}} if imageTypes is None else dict(imageTypes)
     for t in imageTypes:
         if t not in _ALL_TYPES:
             raise NotImplementedError("roi_features_batch_types: %r is not an image type (%s)" % (t, ", ".join(_ALL_TYPES)))
-    return _roi_features_images(images, masks, sizes, imageTypes, classes, settings, own=("gradientUseSpacing",))
+    return _roi_features_images(images, masks, sizes, imageTypes, classes, settings,
+                                own=("gradientUseSpacing",) + _LBP2D_SETTINGS)
 
 
 def _roi_features_images(images, masks, sizes, imageTypes, classes, settings, own=()):
@@ -1330,8 +1406,15 @@ def _roi_features_images(images, masks, sizes, imageTypes, classes, settings, ow
     for t, custom in imageTypes.items():
         kw = dict(settings)
         kw.update(custom or {})
+        lbp = {k: kw[k] for k in _LBP2D_SETTINGS if k in kw}
         for k in tuple(own) + ("resegmentRange", "resegmentMode"):      # (per call, not per image type: done above)
             kw.pop(k, None)
+        if t == "LBP2D":
+            image = _lbp2d(rois, lbp.get("lbp2DRadius", 1), lbp.get("lbp2DSamples", 8), lbp.get("lbp2DMethod", "uniform"),
+                           kw.get("force2Ddimension", 0), None)
+            routes.append(last_batch_route())
+            features("lbp-2D", image, kw)
+            continue
         if t in INTENSITY_TYPES or t == "Gradient":
             features(t.lower(), transformed()[t], kw)
             continue
